@@ -14,16 +14,20 @@ figure (every rank walks its own 1M-topic batch per step, SURVEY's "also
 headline.  Steps rotate over `--batches` distinct batches (no batch is
 replayed back to back, so L2 / MALL never hold the previous step's topics).
 No collective on the data path.  `value` = topics matched per second over
-all ranks (max-over-ranks step time).  Every rank checks its own lists
-against the oracle; `parity_check` is the AND over ranks.
+all ranks (max-over-ranks step time).
 
-Extra legs at N = 1 (not `value`): the CPU baseline (O1 = C restatement of
-emqx_trie, on all host threads and on one; O3 = the same algorithm over
-interned ids), the host-buffer path tm_match_batch (PCIe both ways
-included), and the micro-batcher driven by 16 producer threads with one
+A plain run does what `value` needs and no more: build the trie, size the
+outputs, warm up, time the steps, write `--dump-outputs`, print the line.
+`--full` adds everything else, beside `value` and never part of it: the
+walk's statistics and per-kernel times (the roofline), the weak-scaling
+figure, the bit-exact check of every rank's lists against the oracle
+(`parity_check` is the AND over ranks), and at N = 1 the CPU baseline (O1 =
+C restatement of emqx_trie, on all host threads and on one; O3 = the same
+algorithm over interned ids), the host-buffer path tm_match_batch (PCIe both
+ways included), and the micro-batcher driven by 16 producer threads with one
 submit per publish (the NIF's path).
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
      torchrun --nproc-per-node N bench.py --gpus N ...
      python bench.py --single-process --gpus N   (one process, one engine over N GPUs: tm_open_devices)
 """
@@ -34,6 +38,7 @@ import os
 import platform
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -50,7 +55,9 @@ from emqx_amd import workload as W  # noqa: E402
 METRIC = "topic matches/sec (whole node) at 10M wildcard filters; % HBM roofline"
 # micro-batcher leg: the NIF's configuration, among the best points of tools/bench_batcher.py (profiles/r02_b)
 BATCHER = {"producers": 16, "deadline_us": 200, "max_topics": 262144, "lanes_per_replica": 4, "callback_threads": 8}
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+# --dump-outputs: at most this many topics (counts, offsets) and ids, 8 B each: 48 MB in all
+DUMP_TOPICS, DUMP_IDS, DUMP_SEED = 1_000_000, 4_000_000, 0xD0C5
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (8 TB/s)
 
 
 def log(*a):
@@ -60,6 +67,14 @@ def log(*a):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is not the headline figure: walk statistics and per-kernel "
+                         "times (roofline), weak scaling, the parity check against the oracle, the CPU baseline, "
+                         "the host-buffer and micro-batcher legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (counts, offsets, ids of "
+                         "its batch; a fixed seeded sample of each past %d entries) as DIR/<name>.npy (float64)"
+                         % DUMP_TOPICS)
     ap.add_argument("--steps", type=int, default=500)   # ~5 s timed at C3 8M: long enough for a busy sampler
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=3, help="SURVEY §8(d) config (3 = the metric's)")
@@ -71,9 +86,9 @@ def parse():
                     help="topics per batch (strong, default the config's: 8M at C3) or per GPU (weak, default "
                          "--weak-topics)")
     ap.add_argument("--weak-topics", type=int, default=1_000_000,
-                    help="topics per GPU of the weak-scaling figure reported beside the strong one (0 = skip)")
+                    help="--full: topics per GPU of the weak-scaling figure reported beside the strong one (0 = skip)")
     ap.add_argument("--check-rank", type=int, default=2_000,
-                    help="topics of each batch every rank > 0 checks bit-exactly vs O3")
+                    help="--full: topics of each batch every rank > 0 checks bit-exactly vs O3")
     ap.add_argument("--batches", type=int, default=2, help="distinct batches the steps rotate over")
     ap.add_argument("--mode", choices=["replicated", "sharded", "routed"], default=None,
                     help="replicated trie per GPU (default), filter shards per GPU with a list exchange (sharded), "
@@ -88,28 +103,31 @@ def parse():
                     help="one process drives --gpus GPUs through ONE engine (tm_open_devices)")
     ap.add_argument("--replicas", default=None,
                     help="single-process: comma list of HIP ordinals (repeats allowed), default 0..gpus-1")
-    ap.add_argument("--cpu-sample", type=int, default=1_500_000, help="topics timed on the host (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=1_500_000, help="--full: topics timed on the host (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=None)
-    ap.add_argument("--check", type=int, default=20_000, help="topics of each batch checked bit-exactly vs O1")
+    ap.add_argument("--check", type=int, default=20_000, help="--full: topics of each batch checked bit-exactly vs O1")
     ap.add_argument("--stream-kind", choices=["pool", "prio"], default="prio",
                     help="lane streams: high priority (default: a hardware queue each) or torch's pool (normal "
                          "priority: two of three lanes shared a queue, profiles/r05_u)")
     ap.add_argument("--streams", type=int, default=3,
                     help="streams the steps alternate over (batches overlap on the GPU; 1 = strictly serial)")
     ap.add_argument("--roof-steps", type=int, default=20,
-                    help="serial steps after the timed region that time each kernel for the roofline")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-buffer and batcher legs")
+                    help="--full: serial steps after the timed region that time each kernel for the roofline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the host-buffer and batcher legs")
     ap.add_argument("--walk", default=None, help="walk variant (queue|queue_xcd)")
     ap.add_argument("--stage-k", type=int, default=None)
     ap.add_argument("--lib", default=None, help="EXPERIMENT: alternative build of libtopicmatch.so (A/B of build options)")
-    ap.add_argument("--hist", action="store_true", help="log per-level visit/probe histogram (diagnostic)")
+    ap.add_argument("--hist", action="store_true", help="--full: log per-level visit/probe histogram (diagnostic)")
     ap.add_argument("--layout", type=int, default=None, help="1 = DFS relayout on commit (default), 0 = off")
     ap.add_argument("--opt", action="append", default=[], help="EXPERIMENT: engine option name=value (repeatable)")
     ap.add_argument("--presort", default=None, help="EXPERIMENT: batches sorted on the host: bytes | hN (N-bit word hashes)")
     ap.add_argument("--ab-opt", action="append", default=[],
                     help="EXPERIMENT: after the headline region, time the same batches again with these engine options "
                          "(name=value[,name=value]; repeatable; one trie build for every variant), reported under ab")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.ab_opt and not a.full:
+        ap.error("--ab-opt compares each variant's lists and kernel times with the headline's: add --full")
+    return a
 
 
 def kernel_src_sha():
@@ -152,16 +170,30 @@ def host_threads(a):
     return a.cpu_threads or len(os.sched_getaffinity(0))
 
 
-def insert_progress(eng, fb, fo, rank, chunk=10_000_000):
-    """insert_many in slices of `chunk` filters with a log line per slice
-    (a 100M-filter build takes minutes: the GPU job runner wants output)"""
-    n = len(fo) - 1
+def generate_and_insert(eng, config, n, rank, chunk=10_000_000):
+    """the n filters of `config`, generated and inserted in their order;
+    returns them.  The generator draws one sequence whatever n is, so
+    W.filters(config, n=k) is the first k filters of W.filters(config, n=n):
+    growing prefixes (n/8, n/4, n/2, n) are generated side by side on threads
+    and each is inserted, from where the one before it ended, as soon as it is
+    there.  Insertion, the longer job, so starts after an eighth of the
+    generator's time instead of all of it; the filters, their order and with
+    it their ids are those of one insert_many of all n.  Slices of at most
+    `chunk` filters with a log line each (a 100M-filter build takes minutes:
+    a job runner wants output)"""
+    sizes = sorted({max(1, n // d) for d in (8, 4, 2, 1)})
     t0 = time.time()
-    for lo in range(0, n, chunk):
-        hi = min(n, lo + chunk)
-        eng.insert_many(fb[int(fo[lo]):int(fo[hi])], (fo[lo:hi + 1] - fo[lo]).astype(np.uint64))
-        if n > chunk:
-            log("rank %d: inserted %d / %d filters (%.0fs)" % (rank, hi, n, time.time() - t0))
+    hi = 0
+    with ThreadPoolExecutor(len(sizes)) as pool:
+        for job in [pool.submit(W.filters, config, n=k) for k in sizes]:
+            fb, fo = job.result()
+            k = len(fo) - 1
+            while hi < k:
+                lo, hi = hi, min(k, hi + chunk)
+                eng.insert_many(fb[int(fo[lo]):int(fo[hi])], (fo[lo:hi + 1] - fo[lo]).astype(np.uint64))
+                if n > chunk:
+                    log("rank %d: inserted %d / %d filters (%.0fs)" % (rank, hi, n, time.time() - t0))
+    return fb, fo
 
 
 def make_batches(a, cfg, rank, world):
@@ -355,6 +387,9 @@ def main():
         from emqx_amd import _lib
         _lib.LIB_PATH = os.path.abspath(a.lib)
     rank, world, local = multi.env_rank()
+    replicated = not a.single_process and (a.mode or "replicated") == "replicated"
+    if a.dump_outputs and not replicated:
+        sys.exit("--dump-outputs writes the replicated mode's outputs (not --mode %s / --single-process)" % a.mode)
     if a.single_process and a.mode == "routed":
         return main_routed_single(a)
     if a.single_process:
@@ -370,13 +405,8 @@ def main():
     dev = torch.device("cuda", local)
     # replicated whenever the trie fits one GPU's HBM (north_star): C4's 100M
     # filters (252M nodes) included; --mode sharded for filter sets beyond it
-    if (a.mode or "replicated") == "sharded":
-        main_sharded(a, rank, world, local, dev)
-        if world > 1:
-            dist.destroy_process_group()
-        return
-    if a.mode == "routed":
-        main_routed(a, rank, world, local, dev)
+    if not replicated:
+        (main_sharded if a.mode == "sharded" else main_routed)(a, rank, world, local, dev)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -384,9 +414,9 @@ def main():
     # per step: the whole batch (strong) or each rank's (weak)
     a.topics = a.topics or (cfg["topics"] if a.scaling == "strong" else a.weak_topics)
     n_filters = a.filters or cfg["filters"]
-    t0 = time.time()
-    fb, fo = W.filters(a.config, n=n_filters)
-    log("rank %d: generated %d filters (%.1f MB) in %.1fs" % (rank, n_filters, fo[-1] / 1e6, time.time() - t0))
+    # the topic batches are generated on a thread beside the trie build
+    # (strong = this rank's slice of each global batch, weak = its own batches)
+    batches_job = ThreadPoolExecutor(1).submit(make_batches, a, cfg, rank, world)
     t0 = time.time()
     eng = Engine(device=local, filters_hint=n_filters)
     if a.walk:
@@ -398,36 +428,72 @@ def main():
     for kv in a.opt:
         k, x = kv.split("=")
         eng.set_option(k, int(x))
-    insert_progress(eng, fb, fo, rank)
+    fb, fo = generate_and_insert(eng, a.config, n_filters, rank)
     eng.commit()
-    log("rank %d: trie built + committed in %.1fs: %d filters, %d nodes, image %.2f GB" % (
-        rank, time.time() - t0, eng.filter_count, eng.node_count, eng.image_bytes / 1e9))
+    log("rank %d: %d filters (%.1f MB) generated, trie built + committed in %.1fs: %d filters, %d nodes, "
+        "image %.2f GB" % (rank, n_filters, fo[-1] / 1e6, time.time() - t0, eng.filter_count, eng.node_count,
+                           eng.image_bytes / 1e9))
     eng.set_option("slots", min(4, max(2, a.streams)))
 
     # the headline region: strong = this rank's slice of each global batch,
     # weak = this rank's own batches (--scaling weak)
-    t0 = time.time()
-    batches = make_batches(a, cfg, rank, world)
-    log("rank %d: %d batches of %d topics generated in %.1fs" % (rank, len(batches), len(batches[0][1]) - 1,
-                                                                 time.time() - t0))
+    batches = batches_job.result()
+    log("rank %d: %d batches of %d topics" % (rank, len(batches), len(batches[0][1]) - 1))
     # the lanes' streams, made once and shared by every region of the run:
     # a second set of high-priority streams (the weak leg's) shared the
     # process's few high-priority hardware queues with the first, and the
     # weak 1M step took 1.59 instead of 1.51 ms (profiles/r06_ab/ab_r04.jsonl)
     lane_streams = [Region.make_stream(dev, a.stream_kind) for _ in range(max(1, a.streams))]
-    reg = Region(eng, dev, batches, lane_streams, stats=True, hist=a.hist)
-    stats, fanout = reg.stats, reg.fanout
-    log("fan-out per topic: %s" % fanout)
+    reg = Region(eng, dev, batches, lane_streams, stats=a.full, hist=a.full and a.hist)
     reg.warm(a.warmup)
     # ---- timed region: K steps; barrier + sync on both sides, max over ranks
     dt = reg.timed(a.steps)
+    if a.dump_outputs:
+        reg.dump_last_step(a.dump_outputs, rank)
+    n0 = reg.dbat[0][2]
+    topics_per_step = a.topics if a.scaling == "strong" else n0 * world
+    topics_per_s = topics_per_step * a.steps / dt
+    out = {
+        "metric": METRIC,
+        "value": topics_per_s,
+        "unit": "topics/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": a.scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+        "config": {"workload": "C%d: %d distinct wildcard filters replicated per GPU, %d-level topics, "
+                               "%s, steps rotating over %d distinct batches and %d streams" % (
+                                   a.config, n_filters, cfg["levels"],
+                                   ("one %d-topic batch per step split over %d GPU(s)" % (a.topics, world))
+                                   if a.scaling == "strong" else "%d topics per GPU per step" % a.topics,
+                                   a.batches, a.streams),
+                   "filters": n_filters, "topics_per_step": int(topics_per_step),
+                   "topics_per_gpu_step": n0, "levels": cfg["levels"],
+                   "parallelism": "replicated trie x %d, %s" % (
+                       world, "topic batch split by rank" if a.scaling == "strong" else "a topic batch per rank")},
+        "full": a.full,
+    }
+    if not a.full:   # the plain run ends here
+        if rank == 0:
+            emit(out)
+        eng.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    stats, fanout = reg.stats, reg.fanout
+    log("fan-out per topic: %s" % fanout)
     kms = reg.kernel_times(a.roof_steps)
     xcd = reg.walk_clocks()
     if xcd:
         log("walk per XCD (ms): " + " | ".join("%d: %.3f %.3f %.3f %d" % (i, x["start"], x["home_done"], x["end"],
                                                                           x["stolen_chunks"]) for i, x in enumerate(xcd)))
     results = reg.results()
-    n0 = reg.dbat[0][2]
 
     # in-process A/B of engine options over the same trie and batches
     ab = []
@@ -496,8 +562,6 @@ def main():
             check_desc += ", the weak-scaling batches likewise"
 
     if rank == 0:
-        topics_per_step = a.topics if a.scaling == "strong" else n0 * world
-        topics_per_s = topics_per_step * a.steps / dt
         levels = stats["levels"]
         B = 8 * levels + 16 * stats["edge_reads"] + 4 * stats["matches"]   # SURVEY §8(d), per launch of batch 0
         kname = max(kms, key=kms.get) if kms else None
@@ -514,29 +578,7 @@ def main():
             if same_kernel and tc.get("filters") == n_filters and tc.get("topics_per_gpu_step") == n0 and \
                     tc.get("levels") == cfg["levels"]:
                 traffic = tj["traffic_bytes_per_launch"] / (walk_ms * 1e-3) / 1e9
-        out = {
-            "metric": METRIC,
-            "value": topics_per_s,
-            "unit": "topics/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": a.scaling,
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic",
-            "config": {"workload": "C%d: %d distinct wildcard filters replicated per GPU, %d-level topics, "
-                                   "%s, steps rotating over %d distinct batches and %d streams" % (
-                                       a.config, n_filters, cfg["levels"],
-                                       ("one %d-topic batch per step split over %d GPU(s)" % (a.topics, world))
-                                       if a.scaling == "strong" else "%d topics per GPU per step" % a.topics,
-                                       a.batches, a.streams),
-                       "filters": n_filters, "topics_per_step": int(topics_per_step),
-                       "topics_per_gpu_step": n0, "levels": cfg["levels"],
-                       "parallelism": "replicated trie x %d, %s" % (
-                           world, "topic batch split by rank" if a.scaling == "strong" else "a topic batch per rank")},
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
                          "traffic_frac": (traffic / HBM_PEAK_GBS) if traffic else None,
@@ -561,7 +603,7 @@ def main():
             "fanout": fanout,
             "parity_check": check_ok,
             "parity_scope": check_desc,
-        }
+        })
         if weak:
             out["weak"] = weak
         if ab:
@@ -659,6 +701,32 @@ class Region:
         for li, bi in self.last.items():   # every lane's last result is complete and exact
             assert int(self.lanes[li][4].item()) == self.totals[bi], "match total changed between steps"
         return dt
+
+    def dump_last_step(self, out_dir, rank):
+        """what the last step returned to its caller, as <out_dir>/<name>.npy
+        (float64; ranks > 0 write <name>_rank<r>.npy): `total`, the batch's
+        match count; `counts` and `offsets` of its topics; `ids`, the
+        concatenated match lists.  Past DUMP_TOPICS topics / DUMP_IDS ids a
+        sorted sample at positions drawn from DUMP_SEED, the same from run to
+        run for the same batch sizes and totals"""
+        li = (self.k - 1) % len(self.lanes)
+        s_, c_, oo_, i_, t_ = self.lanes[li]
+        n = self.dbat[self.last[li]][2]
+        total = check_total(t_, self.cap, "last step")
+        rng = np.random.default_rng(DUMP_SEED)
+
+        def sample(d, m, limit):
+            d = d[:m]
+            if m > limit:
+                d = d[torch.from_numpy(np.sort(rng.integers(0, m, size=limit))).to(self.dev)]
+            return d.cpu().numpy()
+        arrays = {"total": np.array([total]),
+                  "counts": sample(c_, n, DUMP_TOPICS).view(np.uint32),
+                  "offsets": sample(oo_, n + 1, DUMP_TOPICS).view(np.uint64),
+                  "ids": sample(i_, total, DUMP_IDS).view(np.uint32)}
+        os.makedirs(out_dir, exist_ok=True)
+        for name, x in arrays.items():
+            np.save(os.path.join(out_dir, name + ("_rank%d" % rank if rank else "") + ".npy"), x.astype(np.float64))
 
     def kernel_times(self, steps):
         """per-kernel durations for the roofline: with batches overlapping, a

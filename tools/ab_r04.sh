@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/${TAG:-ab_r04}
 mkdir -p "$OUT"
-ARGS="--steps ${STEPS_N:-20} --warmup ${WARM_N:-5} --cpu-sample 0 --check 2000 --no-extras ${BENCH_ARGS}"
+ARGS="--full --steps ${STEPS_N:-20} --warmup ${WARM_N:-5} --cpu-sample 0 --check 2000 --no-extras ${BENCH_ARGS}"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in ${VARIANTS:-head_prio head_pool r04}; do
     case $v in

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-r04_c4}
 mkdir -p "$OUT"
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout -k 10 ${T_BENCH:-1000} python -u bench.py --config 4 ${C4_AB:---ab-opt presort=0 --ab-opt presort=2 --ab-opt sort_bits=32} --steps 10 \
+  timeout -k 10 ${T_BENCH:-1000} python -u bench.py --full --config 4 ${C4_AB:---ab-opt presort=0 --ab-opt presort=2 --ab-opt sort_bits=32} --steps 10 \
     --warmup 2 --roof-steps 10 --no-extras --cpu-sample 0 --check 2000 --weak-topics 0 \
     > "$OUT/bench_c4_ab.json" 2> "$OUT/bench_c4_ab.log" || exit $?
 fi
