@@ -220,6 +220,32 @@ SIGNATURES = [
                                                         ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_sub_add", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                  ctypes.c_char_p, ctypes.c_uint32]),
+    ("tm_sub_del", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                  ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_sub_add_batch", ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint32]),
+    ("tm_sub_del_batch", ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_uint32]),
+    ("tm_subscribers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_sub_group_bytes", ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_sub_count", ctypes.c_uint64, [ctypes.c_void_p]),
+    ("tm_set_local_node", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32]),
+    ("tm_match_dispatch_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                               ctypes.c_void_p]),
+    ("tm_match_dispatch_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
+    ("tm_dispatch_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_void_p]),
     ("tm_batcher_open", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,

@@ -244,6 +244,8 @@ struct Image {
     // always come from one commit
     DevBuf d_rslots, d_rarena, d_rdest, d_fr_meta, d_rank_src, d_dt, d_rank_tg;
     DevBuf d_fshape;   // option "shape_keys": filter id -> order key
+    // subscriber image (dispatch.hip), same epoch as the trie and the routes
+    DevBuf d_sslots, d_sarena, d_spool, d_fs_meta;
     DevBuf d_wheat;    // word id -> heat (option "presort" 2: the tail order's cost estimate)
     size_t arena_uploaded = 0, woff_uploaded = 0;
     uint64_t heat_uploaded = ~0ull;   // word_heat version in d_wheat
@@ -257,9 +259,11 @@ struct Image {
     ImageView iv{};
     RouteView rv{};
     AggreView av{};
+    SubView sv{};
     void release() {
         for (DevBuf* b : {&d_nodes, &d_edges, &d_hedges, &d_dict, &d_arena, &d_woff, &d_inner, &d_leaf, &d_rslots,
-                          &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat})
+                          &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat,
+                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta})
             b->release();
         for (hipEvent_t ev : uses) (void)hipEventDestroy(ev);
         uses.clear();
@@ -349,6 +353,9 @@ struct DevState {
     // workspaces: route / aggre (w_r*, w_d*, w_a*), host-buffer batches, merge
     DevBuf w_rexact, w_rscan, w_rids, w_rcounts, w_roff;
     DevBuf w_dsrc, w_dcount, w_akey, w_alarge;
+    // dispatch (dispatch.hip): per-slot plain counts, segments and prefix, and
+    // the host-buffer call's deliveries / pairs before they go back
+    DevBuf w_xpcnt, w_xpseg, w_xpre, w_xscan, w_xto, w_xscount, w_xsoff, w_xsub;
     DevBuf w_mpre, w_mscan, w_bytes, w_off, w_counts, w_outoff, w_ids, w_total;
     // the route / aggre workspaces are shared by every stream:
     // rw_done is recorded after the last route or aggre kernel of a batch;
@@ -389,6 +396,7 @@ struct DevState {
         ev_spare.clear();
         for (DevBuf* b : {&stage_dev, &w_rexact, &w_rscan, &w_rids, &w_rcounts, &w_roff, &w_dsrc, &w_dcount, &w_akey,
                           &w_alarge, &w_mpre, &w_mscan, &w_bytes, &w_off, &w_counts, &w_outoff, &w_ids, &w_total,
+                          &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -657,6 +665,49 @@ struct tm_engine {
     std::vector<uint2> dt;                  // dest id -> {target rank, target id | group << 31}
     std::vector<uint32_t> rank_tg;          // target rank -> target id
     bool targets_dirty = true;              // a dest or a dest's target was added: re-rank the targets
+
+    // ---- subscriber table: the emqx_subscriber duplicate_bag ----
+    // (src/emqx_broker_sup.erl:55-67; insert_subscriber/3 src/emqx_broker.erl:398-415,
+    // subscribers/1 :245-247).  A subscriber is a caller-chosen u32; a shared
+    // entry {shared, Group, Sub} carries an interned group id.
+    static constexpr uint32_t NO_GROUP = 0xFFFFFFFFu;
+    std::unordered_map<std::string, uint32_t> group_index;
+    std::vector<std::string> group_names;
+    struct SubRec {
+        std::vector<std::pair<uint32_t, uint32_t>> bag;   // (sub, group | NO_GROUP), insertion order
+        // the plain subscribers once the bag passes BAG_INDEX_MIN entries (scanned below that)
+        std::unique_ptr<std::unordered_set<uint32_t>> index;
+        uint32_t n_plain = 0;
+        const std::string* key = nullptr;     // the sub_bag key (node-stable)
+        uint32_t slot = SLOT_NONE;            // exact-table slot (sx_slots)
+        uint32_t fid = FILTER_NONE;           // trie filter of a wildcard topic, while both exist
+        uint32_t off = 0, cap = 0;            // plain segment in sx_pool
+        uint64_t arena = 0, words = 0;        // topic bytes in sx_arena (u64 words)
+        bool has_plain(uint32_t sub) const {
+            if (index) return index->count(sub) != 0;
+            for (const auto& x : bag)
+                if (x.first == sub && x.second == NO_GROUP) return true;
+            return false;
+        }
+    };
+    std::unordered_map<std::string, SubRec> sub_bag;   // topic -> its subscribers
+    size_t sub_total = 0;
+    // The subscriber image, kept in place like the route image: an exact
+    // table over every topic with subscribers (sx_slots / sx_arena), the pool
+    // of plain subscriber segments (sx_pool) and fs_meta: filter id ->
+    // {segment, n_plain, n_all, 0}
+    std::vector<SubSlot> sx_slots = std::vector<SubSlot>(16, SubSlot{0, 0, 0, 0, 0, 0});
+    std::vector<SubRec*> sx_slot_rec = std::vector<SubRec*>(16, nullptr);
+    size_t sx_used = 0;
+    std::vector<uint64_t> sx_arena;
+    size_t sx_arena_garbage = 0;
+    std::vector<uint32_t> sx_pool;
+    size_t sx_pool_garbage = 0;
+    std::vector<uint4> fs_meta;
+    std::vector<SubRec*> fs_rec;   // filter id -> linked topic
+    Track t_sslots, t_sarena, t_spool, t_fs_meta;
+    bool local_set = false;        // tm_set_local_node: the target that is node()
+    uint32_t local_target = 0;
 
     // ---- batch pipeline knobs ----
     int nslots = 2;                     // option "slots"
@@ -1113,10 +1164,12 @@ struct tm_engine {
         t_fshape.cur.mark(id);
         ++live_filters;
         on_filter_new(p, len, id);
+        on_filter_new_subs(p, len, id);
         return id;
     }
     void free_filter(uint32_t id) {
         on_filter_free(id);
+        on_filter_free_subs(id);
         filters[id].node = NODE_NONE;   // off / len stay: the gather serves the id until it is reused
         quarantine.emplace_back(epoch.load() + 1, id);   // the next commit drops it from the images
         quarantined[id] = epoch.load() + 1;
@@ -1448,6 +1501,268 @@ struct tm_engine {
     }
     void on_filter_free(uint32_t fid) {
         if (fid < fr_rec.size() && fr_rec[fid]) fr_unlink(fr_rec[fid]);
+    }
+    void on_filter_new_subs(const uint8_t* p, uint32_t len, uint32_t fid) {
+        if (sub_bag.empty() || !tm_topic_wildcard(p, len)) return;
+        auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(p), len));
+        if (it != sub_bag.end() && it->second.fid == FILTER_NONE) fs_link(&it->second, fid);
+    }
+    void on_filter_free_subs(uint32_t fid) {
+        if (fid < fs_rec.size() && fs_rec[fid]) fs_unlink(fs_rec[fid]);
+    }
+
+    // ------------------------------------------------------------------
+    // subscribers (emqx_broker.erl): the emqx_subscriber bag and the image
+    // dispatch/2 reads on the device.  Never the trie or the route bag: those
+    // are the caller's add_route / del_route.
+    uint32_t intern_group(const uint8_t* g, uint32_t glen) {
+        std::string k(reinterpret_cast<const char*>(g), glen);
+        auto it = group_index.find(k);
+        if (it != group_index.end()) return it->second;
+        if (group_names.size() >= 0xFFFFFFF0ull) throw RangeError("group ids exhausted");
+        const uint32_t id = (uint32_t)group_names.size();
+        group_names.push_back(k);
+        group_index.emplace(std::move(k), id);
+        return id;
+    }
+    void sub_reindex(SubRec& r) {
+        if (r.bag.size() < BAG_INDEX_MIN) {
+            r.index.reset();
+        } else if (!r.index) {
+            r.index.reset(new std::unordered_set<uint32_t>());
+            for (const auto& x : r.bag)
+                if (x.second == NO_GROUP) r.index->insert(x.first);
+        }
+    }
+    // insert_subscriber/3 (:398-415): the membership test is on the bare
+    // Subscriber (:399-405), so only a plain entry suppresses an add, whatever
+    // the group; a repeated shared add duplicates the entry (duplicate_bag)
+    void sub_add(const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+        std::string key(reinterpret_cast<const char*>(t), tlen);
+        auto it = sub_bag.find(key);
+        if (it != sub_bag.end() && it->second.has_plain(sub)) return;
+        const uint32_t gid = g ? intern_group(g, glen) : NO_GROUP;
+        if (it == sub_bag.end()) {
+            it = sub_bag.emplace(std::move(key), SubRec{}).first;
+            SubRec& r = it->second;
+            r.key = &it->first;
+            sx_arena_put(r);
+            sx_slot_put(&r);
+            if (tm_topic_wildcard(t, tlen)) fs_link(&r, filter_of(t, tlen));
+        }
+        SubRec& r = it->second;
+        r.bag.emplace_back(sub, gid);
+        if (gid == NO_GROUP) {
+            ++r.n_plain;
+            if (r.index) r.index->insert(sub);
+        }
+        sub_reindex(r);
+        if (gid == NO_GROUP) sseg_append(r, sub);
+        else sx_sync(r);
+        ++sub_total;
+        dev_dirty = true;
+    }
+    // ets:delete_object(?SUBSCRIBER, {Topic, shared(Group, Sub)}) (:447-448):
+    // every equal object goes, an absent one is a no-op; returns the entries left
+    uint32_t sub_del(const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+        auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
+        if (it == sub_bag.end()) return 0;
+        SubRec& r = it->second;
+        uint32_t gid = NO_GROUP;
+        if (g) {
+            auto gi = group_index.find(std::string(reinterpret_cast<const char*>(g), glen));
+            if (gi == group_index.end()) return (uint32_t)r.bag.size();
+            gid = gi->second;
+        }
+        const std::pair<uint32_t, uint32_t> obj(sub, gid);
+        const size_t before = r.bag.size();
+        r.bag.erase(std::remove(r.bag.begin(), r.bag.end(), obj), r.bag.end());
+        const size_t gone = before - r.bag.size();
+        if (!gone) return (uint32_t)before;
+        sub_total -= gone;
+        dev_dirty = true;
+        if (gid == NO_GROUP) {
+            r.n_plain -= (uint32_t)gone;
+            if (r.index) r.index->erase(sub);
+        }
+        sub_reindex(r);
+        if (!r.bag.empty()) {
+            if (gid == NO_GROUP) sseg_rewrite(r);
+            else sx_sync(r);
+            return (uint32_t)r.bag.size();
+        }
+        fs_unlink(&r);
+        sx_slot_del(&r);
+        sx_pool_garbage += r.cap;
+        sx_arena_garbage += r.words;
+        sub_bag.erase(it);
+        maybe_compact_subs();
+        return 0;
+    }
+    const SubRec* subscribers(const uint8_t* t, uint32_t tlen) const {
+        auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
+        return it == sub_bag.end() ? nullptr : &it->second;
+    }
+
+    // ---- subscriber image maintenance ----
+    void sx_sync(const SubRec& r) {
+        const uint32_t n_all = (uint32_t)r.bag.size();
+        if (r.slot != SLOT_NONE) {
+            SubSlot& s = sx_slots[r.slot];
+            s.n_plain = r.n_plain;
+            s.n_all = n_all;
+            s.seg = r.off;
+            s.arena = r.arena * 8;
+            t_sslots.cur.mark(r.slot);
+        }
+        if (r.fid != FILTER_NONE) {
+            fs_meta[r.fid] = make_uint4(r.off, r.n_plain, n_all, 0u);
+            t_fs_meta.cur.mark(r.fid);
+        }
+    }
+    // the plain subscribers of r into its segment, from the bag (a new,
+    // doubled segment at the pool's end when they no longer fit)
+    void sseg_rewrite(SubRec& r) {
+        if (r.n_plain > r.cap) {
+            sx_pool_garbage += r.cap;
+            uint32_t cap = std::max<uint32_t>(r.cap * 2, 2);
+            while (cap < r.n_plain) cap *= 2;
+            if (sx_pool.size() + cap >= 0xFFFFFFF0ull) throw RangeError("subscriber pool past 2^32 entries");
+            r.off = (uint32_t)sx_pool.size();
+            r.cap = cap;
+            sx_pool.resize(sx_pool.size() + cap, 0);
+        }
+        size_t k = r.off;
+        for (const auto& x : r.bag)
+            if (x.second == NO_GROUP) sx_pool[k++] = x.first;
+        t_spool.mark_range(r.off, k);
+        sx_sync(r);
+    }
+    void sseg_append(SubRec& r, uint32_t sub) {   // sub is r's last plain entry
+        if (r.n_plain > r.cap) return sseg_rewrite(r);
+        sx_pool[r.off + r.n_plain - 1] = sub;
+        t_spool.cur.mark(r.off + r.n_plain - 1);
+        sx_sync(r);
+    }
+    void sx_arena_put(SubRec& r) {
+        const uint32_t len = (uint32_t)r.key->size();
+        r.words = std::max<uint64_t>(1, (len + 7) / 8);
+        r.arena = sx_arena.size();
+        sx_arena.resize(sx_arena.size() + r.words, 0);
+        if (len) std::memcpy(&sx_arena[r.arena], r.key->data(), len);
+        t_sarena.mark_range(r.arena, r.arena + r.words);
+    }
+    void sx_slot_put(SubRec* r) {
+        if ((sx_used + 1) * 2 > sx_slots.size()) sx_regrow(sx_slots.size() * 2);
+        const uint8_t* t = reinterpret_cast<const uint8_t*>(r->key->data());
+        const uint64_t h = word_hash(t, (uint32_t)r->key->size());
+        const size_t mask = sx_slots.size() - 1;
+        size_t s = h & mask;
+        while (sx_slots[s].hash) s = (s + 1) & mask;
+        sx_slots[s] = SubSlot{h, (uint32_t)r->key->size(), 0, r->arena * 8, 0, 0};
+        sx_slot_rec[s] = r;
+        r->slot = (uint32_t)s;
+        ++sx_used;
+        t_sslots.cur.mark(s);
+    }
+    void sx_slot_del(SubRec* r) {   // backward-shift deletion, as rt_slot_del
+        const size_t mask = sx_slots.size() - 1;
+        size_t i = r->slot;
+        for (size_t j = (i + 1) & mask; sx_slots[j].hash; j = (j + 1) & mask) {
+            const size_t home = sx_slots[j].hash & mask;
+            const bool stays = i <= j ? (home > i && home <= j) : (home > i || home <= j);
+            if (stays) continue;
+            sx_slots[i] = sx_slots[j];
+            sx_slot_rec[i] = sx_slot_rec[j];
+            sx_slot_rec[i]->slot = (uint32_t)i;
+            t_sslots.cur.mark(i);
+            i = j;
+        }
+        sx_slots[i] = SubSlot{0, 0, 0, 0, 0, 0};
+        sx_slot_rec[i] = nullptr;
+        t_sslots.cur.mark(i);
+        r->slot = SLOT_NONE;
+        --sx_used;
+    }
+    void sx_regrow(size_t cap) {
+        std::vector<SubRec*> recs;
+        recs.reserve(sx_used);
+        for (SubRec* r : sx_slot_rec)
+            if (r) recs.push_back(r);
+        sx_slots.assign(cap, SubSlot{0, 0, 0, 0, 0, 0});
+        sx_slot_rec.assign(cap, nullptr);
+        sx_used = 0;
+        for (SubRec* r : recs) {
+            sx_slot_put(r);
+            sx_sync(*r);
+        }
+        t_sslots.cur.all = true;
+    }
+    // the pool and the arena rewritten without garbage (option "route_gc"
+    // sets the threshold of both images)
+    void maybe_compact_subs() {
+        const bool pool_gc = sx_pool_garbage > route_gc_min && sx_pool_garbage * 2 > sx_pool.size();
+        const bool arena_gc = sx_arena_garbage > route_gc_min / 4 && sx_arena_garbage * 2 > sx_arena.size();
+        if (!pool_gc && !arena_gc) return;
+        std::vector<uint32_t> np;
+        std::vector<uint64_t> na;
+        if (pool_gc) np.reserve(sx_pool.size() - sx_pool_garbage);
+        if (arena_gc) na.reserve(sx_arena.size() - sx_arena_garbage);
+        for (auto& kv : sub_bag) {
+            SubRec& r = kv.second;
+            if (pool_gc) {
+                const uint32_t off = (uint32_t)np.size();
+                np.insert(np.end(), sx_pool.begin() + r.off, sx_pool.begin() + r.off + r.cap);
+                r.off = off;
+            }
+            if (arena_gc) {
+                const uint64_t a = na.size();
+                na.insert(na.end(), sx_arena.begin() + r.arena, sx_arena.begin() + r.arena + r.words);
+                r.arena = a;
+            }
+            sx_sync(r);
+        }
+        if (pool_gc) {
+            sx_pool.swap(np);
+            sx_pool_garbage = 0;
+            t_spool.cur.all = true;
+        }
+        if (arena_gc) {
+            sx_arena.swap(na);
+            sx_arena_garbage = 0;
+            t_sarena.cur.all = true;
+        }
+    }
+    // a wildcard topic's filter id <-> its bag
+    void fs_link(SubRec* r, uint32_t fid) {
+        if (fid == FILTER_NONE) return;
+        if (fid >= fs_meta.size()) {
+            const size_t old = fs_meta.size(), n = std::max<size_t>(fid + 1, filters.size());
+            fs_meta.resize(n, make_uint4(0, 0, 0, 0));
+            fs_rec.resize(n, nullptr);
+            t_fs_meta.mark_range(old, n);
+        }
+        r->fid = fid;
+        fs_rec[fid] = r;
+        sx_sync(*r);
+    }
+    void fs_unlink(SubRec* r) {
+        if (r->fid == FILTER_NONE) return;
+        fs_meta[r->fid] = make_uint4(0, 0, 0, 0);
+        fs_rec[r->fid] = nullptr;
+        t_fs_meta.cur.mark(r->fid);
+        r->fid = FILTER_NONE;
+    }
+    SubView make_sub_view(const Image& g) const {
+        SubView sv;
+        sv.fs_meta = g.d_fs_meta.as<const uint4>();
+        sv.n_filters = (uint32_t)fs_meta.size();
+        sv.local_target = local_target;
+        sv.sx_slots = g.d_sslots.as<const SubSlot>();
+        sv.sx_slot_mask = sx_slots.size() - 1;
+        sv.sx_arena = g.d_sarena.as<const uint8_t>();
+        sv.pool = g.d_spool.as<const uint32_t>();
+        return sv;
     }
 
     // ---- to_rank labels (order maintenance) ----
@@ -1823,10 +2138,12 @@ struct tm_engine {
     static const ImageView& view(const DevState& d) { return d.img[d.bimg].iv; }
     static const RouteView& route_view(const DevState& d) { return d.img[d.bimg].rv; }
     static const AggreView& aggre_view(const DevState& d) { return d.img[d.bimg].av; }
+    static const SubView& sub_view(const DevState& d) { return d.img[d.bimg].sv; }
     void capture_views(Image& g) const {
         g.iv = make_view(g);
         g.rv = make_route_view(g);
         g.av = make_aggre_view(g);
+        g.sv = make_sub_view(g);
     }
     // the views of image g, from the host tables it was just written from
     ImageView make_view(const Image& g) const {
@@ -1958,6 +2275,10 @@ struct tm_engine {
             upload_table(d, g, g.d_rank_src, rank_src, t_rank_src.cur, t_rank_src.prev);
             upload_table(d, g, g.d_dt, dt, t_dt.cur, t_dt.prev);
             upload_table(d, g, g.d_rank_tg, rank_tg, t_rank_tg.cur, t_rank_tg.prev);
+            upload_table(d, g, g.d_sslots, sx_slots, t_sslots.cur, t_sslots.prev);
+            upload_table(d, g, g.d_sarena, sx_arena, t_sarena.cur, t_sarena.prev);
+            upload_table(d, g, g.d_spool, sx_pool, t_spool.cur, t_spool.prev);
+            upload_table(d, g, g.d_fs_meta, fs_meta, t_fs_meta.cur, t_fs_meta.prev);
             if (shape_keys) upload_table(d, g, g.d_fshape, fshape, t_fshape.cur, t_fshape.prev);
             flush_stage(d);
             // append-only arrays: upload the new tail (or all after a realloc)
@@ -2015,6 +2336,10 @@ struct tm_engine {
         t_dt.rotate(dt.size());
         t_rank_tg.rotate(rank_tg.size());
         t_fshape.rotate(fshape.size());
+        t_sslots.rotate(sx_slots.size());
+        t_sarena.rotate(sx_arena.size());
+        t_spool.rotate(sx_pool.size());
+        t_fs_meta.rotate(fs_meta.size());
         dev_dirty = false;
         ++epoch;
         release_quarantine();   // also for engines that only take forced ids (never reach new_filter's release)
@@ -2373,7 +2698,8 @@ struct tm_engine {
     // an overflow re-emits the routes, never re-walks), aggre.hip writes each
     // topic's list at its route offset; *total = route total
     void deliveries_routes(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, uint64_t nbytes,
-                           uint64_t* out_off, uint64_t* total, hipStream_t st, uint64_t& rcap) {
+                           uint64_t* out_off, uint64_t* total, hipStream_t st, uint64_t& rcap,
+                           uint64_t* rtotal_out = nullptr) {
         d.rw_drain();   // w_d* / w_a* may be reallocated below
         d.w_dcount.ensure((size_t)n * 4 + 4);
         const uint64_t want = std::max<uint64_t>(d.w_dsrc.bytes / 8, (uint64_t)n * 16 + 1024);
@@ -2394,6 +2720,7 @@ struct tm_engine {
             rcap = std::min(d.w_dsrc.bytes / 8, d.w_akey.bytes / 8);
         }
         d.w_alarge.ensure((size_t)n * 4 + 16);
+        if (rtotal_out) *rtotal_out = rtotal;
     }
     void aggre_out(DevState& d, uint32_t n, const uint64_t* out_off, uint64_t rcap, uint32_t* counts, uint32_t* to,
                    uint32_t* target, uint64_t cap, hipStream_t st) {
@@ -2407,6 +2734,45 @@ struct tm_engine {
         uint64_t rcap = 0;
         deliveries_routes(d, bytes, off, n, nbytes, out_off, total, st, rcap);
         aggre_out(d, n, out_off, rcap, counts, to, target, cap, st);
+        d.rw_release(st);
+    }
+
+    // emqx_broker:dispatch/2 over the deliveries CSR of a batch (dispatch.hip):
+    // count + scan + per-topic offsets; the slot prefix stays in d.w_xpre for
+    // dispatch_emit (its last entry is the pair total).  slots = min(route
+    // total, the deliveries' capacity)
+    void dispatch_count(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, const uint32_t* acount,
+                        const uint64_t* aoff, const uint32_t* to, const uint32_t* tg, uint64_t slots, uint32_t* ndisp,
+                        uint32_t* sub_count, uint64_t* sub_off, hipStream_t st) {
+        if (slots >= 0xFFFFFFFEull) throw RangeError("dispatch: more than 2^32 - 2 delivery slots in one batch");
+        d.w_xpcnt.ensure((size_t)slots * 4 + 4);
+        d.w_xpseg.ensure((size_t)slots * 4 + 4);
+        d.w_xpre.ensure((size_t)(slots + 1) * 8);
+        d.w_xscan.ensure(scan_tmp_elems((uint32_t)slots) * 8 + 8);
+        uint64_t* P = d.w_xpre.as<uint64_t>();
+        HIPCHK(launch_dispatch_count(sub_view(d), bytes, off, n, acount, aoff, to, tg, slots, ndisp,
+                                     d.w_xpcnt.as<uint32_t>(), d.w_xpseg.as<uint32_t>(), st));
+        HIPCHK(launch_scan0(d.w_xpcnt.as<uint32_t>(), (uint32_t)slots, P, P + slots, d.w_xscan.as<uint64_t>(), st));
+        HIPCHK(launch_dispatch_offsets(P, slots, aoff, n, sub_count, sub_off, st));
+    }
+    void dispatch_emit(DevState& d, uint64_t slots, const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
+                       uint64_t pairs_bound, hipStream_t st) {
+        HIPCHK(launch_dispatch_emit(sub_view(d), d.w_xpre.as<uint64_t>(), slots, d.w_xpseg.as<uint32_t>(), to, sub_to,
+                                    sub_id, cap, pairs_bound, st));
+    }
+    // publish/1's route(aggre(match_routes(T))) with the local dispatch, device buffers
+    void run_dispatch(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, uint64_t nbytes,
+                      uint32_t* counts, uint64_t* out_off, uint32_t* to, uint32_t* target, uint32_t* ndisp, uint64_t cap,
+                      uint64_t* total, uint32_t* sub_count, uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id,
+                      uint64_t sub_cap, uint64_t* sub_total, hipStream_t st) {
+        uint64_t rcap = 0, rtotal = 0;
+        deliveries_routes(d, bytes, off, n, nbytes, out_off, total, st, rcap, &rtotal);
+        aggre_out(d, n, out_off, rcap, counts, to, target, cap, st);
+        const uint64_t slots = std::min(rtotal, cap);
+        dispatch_count(d, bytes, off, n, counts, out_off, to, target, slots, ndisp, sub_count, sub_off, st);
+        dispatch_emit(d, slots, to, sub_to, sub_id, sub_cap, sub_cap, st);
+        HIPCHK(hipMemcpyAsync(sub_total, d.w_xpre.as<uint64_t>() + slots, 8, hipMemcpyDeviceToDevice, st));
+        d.note_use(st);   // the dispatch kernels read the pinned subscriber image after the walk's use
         d.rw_release(st);
     }
 
@@ -3517,6 +3883,270 @@ int tm_match_deliveries_batch(tm_engine* e, const uint8_t* topic_bytes, const ui
                           out_cap, out_needed);
 }
 
+// ---- subscribers and local dispatch (emqx_broker) ----------------------------
+int tm_sub_add(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group, uint32_t glen) {
+    if ((!topic && tlen) || sub == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        e->sub_add(topic, tlen, sub, group, glen);
+        return TM_OK;
+    });
+}
+
+int tm_sub_del(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group, uint32_t glen,
+               uint32_t* remaining) {
+    if ((!topic && tlen) || sub == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        const uint32_t left = e->sub_del(topic, tlen, sub, group, glen);
+        if (remaining) *remaining = left;
+        return TM_OK;
+    });
+}
+
+extern "C++" {
+namespace {
+template <class F>
+int sub_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+              const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared, uint32_t n, F&& one) {
+    if (n && (!topic_off || !subs || (shared && !group_off))) return TM_EINVAL;
+    return chunked(e, n, [&](uint32_t i) {
+        if (topic_off[i + 1] < topic_off[i] || topic_off[i + 1] - topic_off[i] > 0xFFFFFFFFull)
+            throw ArgError("bad offsets");
+        const bool sh = shared && shared[i];
+        if (sh && (group_off[i + 1] < group_off[i] || group_off[i + 1] - group_off[i] > 0xFFFFFFFFull))
+            throw ArgError("bad offsets");
+        if (subs[i] == 0xFFFFFFFFu) throw ArgError("subscriber id 0xFFFFFFFF is reserved");
+        static const uint8_t none = 0;
+        const uint8_t* t = topics ? topics + topic_off[i] : &none;
+        const uint8_t* g = !sh ? nullptr : groups ? groups + group_off[i] : &none;
+        one(t, (uint32_t)(topic_off[i + 1] - topic_off[i]), subs[i], g, sh ? (uint32_t)(group_off[i + 1] - group_off[i]) : 0u);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+int tm_sub_add_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                     const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared, uint32_t n) {
+    return sub_batch(e, topics, topic_off, subs, groups, group_off, shared, n,
+                     [&](const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+                         e->sub_add(t, tlen, sub, g, glen);
+                     });
+}
+
+int tm_sub_del_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                     const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared, uint32_t n) {
+    return sub_batch(e, topics, topic_off, subs, groups, group_off, shared, n,
+                     [&](const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+                         (void)e->sub_del(t, tlen, sub, g, glen);
+                     });
+}
+
+int tm_subscribers(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t* out_sub, uint32_t* out_group,
+                   uint32_t cap, uint32_t* out_n) {
+    if ((!topic && tlen) || !out_n) return TM_EINVAL;
+    return guarded(e, [&] {
+        const tm_engine::SubRec* r = e->subscribers(topic, tlen);
+        const uint32_t k = r ? (uint32_t)r->bag.size() : 0u;
+        *out_n = k;
+        for (uint32_t i = 0; i < k && i < cap; ++i) {
+            if (out_sub) out_sub[i] = r->bag[i].first;
+            if (out_group) out_group[i] = r->bag[i].second;
+        }
+        return k > cap ? TM_ENOSPC : TM_OK;
+    });
+}
+
+const uint8_t* tm_sub_group_bytes(tm_engine* e, uint32_t group_id, uint32_t* len) {
+    if (!e) return nullptr;
+    std::lock_guard<std::recursive_mutex> lk(e->mu);
+    if (group_id >= e->group_names.size()) return nullptr;
+    if (len) *len = (uint32_t)e->group_names[group_id].size();
+    return reinterpret_cast<const uint8_t*>(e->group_names[group_id].data());
+}
+
+uint64_t tm_sub_count(tm_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::recursive_mutex> lk(e->mu);
+    return e->sub_total;
+}
+
+int tm_set_local_node(tm_engine* e, const uint8_t* node, uint32_t len) {
+    if (!node && len) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        const uint32_t t = e->intern_target(TM_TARGET_NODE, node, len);
+        if (!e->local_set || e->local_target != t) {
+            e->local_set = true;
+            e->local_target = t;
+            e->targets_dirty = true;
+            e->dev_dirty = true;   // the views carry it: the next commit publishes it
+        }
+        return TM_OK;
+    });
+}
+
+namespace {
+int local_node_unset(tm_engine* e) {
+    return guarded(e, [&]() -> int {
+        if (e->local_set) return TM_OK;
+        e->last_error = "dispatch: tm_set_local_node has not been called";
+        return TM_EINVAL;
+    });
+}
+}  // namespace
+
+int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                   uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                   uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                   uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                   uint64_t sub_cap, uint64_t* d_sub_total, void* hip_stream) {
+    if (!d_off || !d_out_off || !d_total || !d_sub_off || !d_sub_total || (n && (!d_count || !d_sub_count)) ||
+        (out_cap && (!d_to || !d_target || !d_ndisp)) || (sub_cap && (!d_sub_to || !d_sub_id)))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "dispatch");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->replica_for(d_off);
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (n == 0) {
+            HIPCHK(hipMemsetAsync(d_out_off, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_total, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_sub_off, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_sub_total, 0, 8, st));
+            return TM_OK;
+        }
+        e->run_dispatch(d, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
+                        d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, st);
+        return TM_OK;
+    }, [&] { e->finish_batch(n); });
+}
+
+int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                            uint64_t* sub_needed) {
+    if (!topic_off || !out_off || !sub_off || (n && (!out_count || !sub_count)) ||
+        (out_cap && (!out_to || !out_target || !out_ndisp)) || (sub_cap && (!sub_to || !sub_id)))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "dispatch");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->devs[0];
+    return batch_call(e, {&d}, [&]() -> int {
+        for (uint32_t i = 0; i < n; ++i)
+            if (topic_off[i + 1] < topic_off[i]) throw ArgError("topic offsets not monotone");
+        if (n && topic_off[n] > topic_off[0] && !topic_bytes) throw ArgError("null topic bytes");
+        if (out_needed) *out_needed = 0;
+        if (sub_needed) *sub_needed = 0;
+        out_off[0] = 0;
+        sub_off[0] = 0;
+        if (n == 0) return TM_OK;
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        const uint64_t base = topic_off[0], nb = topic_off[n] - base;
+        d.rw_drain();
+        d.w_bytes.ensure(nb + 16);
+        d.w_off.ensure((size_t)(n + 1) * 8);
+        d.w_counts.ensure((size_t)n * 4 + 4);
+        d.w_outoff.ensure((size_t)(n + 1) * 8);
+        d.w_total.ensure(64);
+        d.w_xscount.ensure((size_t)n * 4 + 4);
+        d.w_xsoff.ensure((size_t)(n + 1) * 8);
+        std::vector<uint64_t> rel(topic_off, topic_off + n + 1);
+        for (auto& x : rel) x -= base;
+        if (nb) HIPCHK(hipMemcpyAsync(d.w_bytes.p, topic_bytes + base, nb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.w_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        const uint8_t* b = d.w_bytes.as<uint8_t>();
+        const uint64_t* o = d.w_off.as<uint64_t>();
+        uint64_t rcap = 0, rtotal = 0, pairs = 0;
+        e->deliveries_routes(d, b, o, n, nb, d.w_outoff.as<uint64_t>(), d.w_total.as<uint64_t>(), s, rcap, &rtotal);
+        // the whole lists in replica workspace (three planes: To, target,
+        // ndisp), so the dispatch is that of every delivery whatever out_cap
+        const uint64_t plane = std::max<uint64_t>(rtotal, 1);
+        d.w_xto.ensure(plane * 12);
+        uint32_t* to = d.w_xto.as<uint32_t>();
+        e->aggre_out(d, n, d.w_outoff.as<uint64_t>(), rcap, d.w_counts.as<uint32_t>(), to, to + plane, rtotal, s);
+        e->dispatch_count(d, b, o, n, d.w_counts.as<uint32_t>(), d.w_outoff.as<uint64_t>(), to, to + plane, rtotal,
+                          to + 2 * plane, d.w_xscount.as<uint32_t>(), d.w_xsoff.as<uint64_t>(), s);
+        HIPCHK(hipMemcpyAsync(&pairs, d.w_xpre.as<uint64_t>() + rtotal, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t splane = std::max<uint64_t>(pairs, 1);
+        d.w_xsub.ensure(splane * 8);
+        uint32_t* sp = d.w_xsub.as<uint32_t>();
+        e->dispatch_emit(d, rtotal, to, sp, sp + splane, pairs, pairs, s);
+        d.rw_release(s);
+        HIPCHK(hipMemcpyAsync(out_count, d.w_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_off, d.w_outoff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sub_count, d.w_xscount.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sub_off, d.w_xsoff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        const uint64_t c = std::min(rtotal, out_cap), pc = std::min(pairs, sub_cap);
+        if (c) {
+            HIPCHK(hipMemcpyAsync(out_to, to, c * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_target, to + plane, c * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out_ndisp, to + 2 * plane, c * 4, hipMemcpyDeviceToHost, s));
+        }
+        if (pc) {
+            HIPCHK(hipMemcpyAsync(sub_to, sp, pc * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(sub_id, sp + splane, pc * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        if (out_needed) *out_needed = rtotal;
+        if (sub_needed) *sub_needed = pairs;
+        return rtotal > out_cap || pairs > sub_cap ? TM_ENOSPC : TM_OK;
+    }, [&] { e->finish_batch(n); });
+}
+
+int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
+                      uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed) {
+    if (!to_off || !sub_off || (n && !ndisp) || (cap && !sub_id)) return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "dispatch");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->devs[0];
+    return batch_call(e, {&d}, [&]() -> int {
+        for (uint32_t i = 0; i < n; ++i)
+            if (to_off[i + 1] < to_off[i]) throw ArgError("topic offsets not monotone");
+        if (n && to_off[n] > to_off[0] && !to_bytes) throw ArgError("null topic bytes");
+        if (needed) *needed = 0;
+        sub_off[0] = 0;
+        if (n == 0) return TM_OK;
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        const uint64_t base = to_off[0], nb = to_off[n] - base;
+        d.rw_drain();
+        d.w_bytes.ensure(nb + 16);
+        d.w_off.ensure((size_t)(n + 1) * 8);
+        d.w_counts.ensure((size_t)n * 4 + 4);
+        d.w_xpcnt.ensure((size_t)n * 4 + 4);
+        d.w_xpseg.ensure((size_t)n * 4 + 4);
+        d.w_xpre.ensure((size_t)(n + 1) * 8);
+        d.w_xscan.ensure(scan_tmp_elems(n) * 8 + 8);
+        std::vector<uint64_t> rel(to_off, to_off + n + 1);
+        for (auto& x : rel) x -= base;
+        if (nb) HIPCHK(hipMemcpyAsync(d.w_bytes.p, to_bytes + base, nb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.w_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        uint64_t* P = d.w_xpre.as<uint64_t>();
+        HIPCHK(launch_dispatch_lookup(tm_engine::sub_view(d), d.w_bytes.as<uint8_t>(), d.w_off.as<uint64_t>(), n,
+                                      d.w_counts.as<uint32_t>(), d.w_xpcnt.as<uint32_t>(), d.w_xpseg.as<uint32_t>(), s));
+        HIPCHK(launch_scan0(d.w_xpcnt.as<uint32_t>(), n, P, P + n, d.w_xscan.as<uint64_t>(), s));
+        HIPCHK(hipMemcpyAsync(sub_off, P, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(ndisp, d.w_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t pairs = sub_off[n];
+        const uint64_t splane = std::max<uint64_t>(pairs, 1);
+        d.w_xsub.ensure(splane * 4);
+        e->dispatch_emit(d, n, nullptr, nullptr, d.w_xsub.as<uint32_t>(), pairs, pairs, s);
+        d.note_use(s);
+        d.rw_release(s);
+        const uint64_t pc = std::min(pairs, cap);
+        if (pc) HIPCHK(hipMemcpyAsync(sub_id, d.w_xsub.p, pc * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (needed) *needed = pairs;
+        return pairs > cap ? TM_ENOSPC : TM_OK;
+    }, [&] {});
+}
+
 int tm_match_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
                           uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_ids,
                           uint64_t out_cap, uint64_t* d_total, void* hip_stream) {
@@ -3803,6 +4433,69 @@ extern "C" int tm_debug_check_routes(tm_engine* e) {
             if (prev && !(prev->label < r->label && *prev->key < *r->key)) return fail("label order at " + *r->key);
             prev = r;
         }
+        return TM_OK;
+    });
+}
+
+// diagnostics (not part of include/topicmatch.h): the in-place subscriber
+// image against the bags it mirrors -- every topic found in the exact table
+// by the kernel's probe, its segment equal to the bag's plain entries in bag
+// order, the counts, its filter entry -- TM_OK or TM_EINVAL with the first
+// inconsistency in tm_last_error
+extern "C" int tm_debug_check_subs(tm_engine* e) {
+    return guarded(e, [&]() -> int {
+        auto fail = [&](const std::string& what) -> int { throw ArgError("subscriber image: " + what); };
+        size_t used = 0;
+        for (size_t s = 0; s < e->sx_slots.size(); ++s)
+            if (e->sx_slots[s].hash) {
+                ++used;
+                if (!e->sx_slot_rec[s] || e->sx_slot_rec[s]->slot != s) return fail("slot owner");
+            }
+        if (used != e->sx_used || used != e->sub_bag.size()) return fail("slot count");
+        size_t total = 0, live_cap = 0, live_words = 0;
+        for (auto& kv : e->sub_bag) {
+            const tm_engine::SubRec& r = kv.second;
+            const uint8_t* t = reinterpret_cast<const uint8_t*>(kv.first.data());
+            const uint32_t len = (uint32_t)kv.first.size();
+            total += r.bag.size();
+            live_cap += r.cap;
+            live_words += r.words;
+            if (r.key != &kv.first || r.bag.empty()) return fail("record of " + kv.first);
+            // the probe the kernel runs (dispatch.hip sub_exact_lookup)
+            const uint64_t h = word_hash(t, len);
+            const size_t mask = e->sx_slots.size() - 1;
+            size_t s = h & mask;
+            while (e->sx_slots[s].hash && !(e->sx_slots[s].hash == h && e->sx_slots[s].len == len &&
+                                             std::memcmp(&e->sx_arena[e->sx_slots[s].arena / 8], t, len) == 0))
+                s = (s + 1) & mask;
+            if (!e->sx_slots[s].hash || s != r.slot) return fail("probe of " + kv.first);
+            const SubSlot& x = e->sx_slots[s];
+            std::vector<uint32_t> plain;
+            for (const auto& b : r.bag)
+                if (b.second == tm_engine::NO_GROUP) plain.push_back(b.first);
+            if (plain.size() != r.n_plain) return fail("plain count of " + kv.first);
+            if (x.n_plain != r.n_plain || x.n_all != r.bag.size() || x.seg != r.off) return fail("slot of " + kv.first);
+            if (len % 8 && (e->sx_arena[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) return fail("arena padding");
+            if (r.cap < r.n_plain || (uint64_t)r.off + r.cap > e->sx_pool.size() ||
+                !std::equal(plain.begin(), plain.end(), e->sx_pool.begin() + r.off))
+                return fail("segment of " + kv.first);
+            const bool wild = tm_topic_wildcard(t, len);
+            const uint32_t fid = wild ? e->filter_of(t, len) : FILTER_NONE;
+            if (r.fid != fid) return fail("filter link of " + kv.first);
+            if (fid != FILTER_NONE) {
+                const uint4 m = e->fs_meta[fid];
+                if (m.x != r.off || m.y != r.n_plain || m.z != r.bag.size() || e->fs_rec[fid] != &r)
+                    return fail("fs_meta of " + kv.first);
+            }
+            if ((r.index != nullptr) != (r.bag.size() >= tm_engine::BAG_INDEX_MIN)) return fail("bag index");
+            if (r.index && r.index->size() != r.n_plain) return fail("bag index size");
+        }
+        if (total != e->sub_total) return fail("subscriber total");
+        if (live_cap + e->sx_pool_garbage != e->sx_pool.size()) return fail("pool accounting");
+        if (live_words + e->sx_arena_garbage != e->sx_arena.size()) return fail("arena accounting");
+        for (size_t f = 0; f < e->fs_meta.size(); ++f)
+            if ((e->fs_meta[f].y || e->fs_meta[f].z) && (!e->fs_rec[f] || e->fs_rec[f]->fid != f))
+                return fail("stale fs_meta");
         return TM_OK;
     });
 }

@@ -172,6 +172,34 @@ struct AggreView {
     const uint32_t* rank_tg;        // target rank -> target id
 };
 
+// ---- subscriber image (emqx_subscriber bag, src/emqx_broker.erl:245-247) ----
+// The local dispatch of emqx_broker:dispatch/2 (dispatch.hip).  Each topic
+// with subscribers owns a segment of one pool of plain subscriber ids (bag
+// order, shared entries left out: dispatch/2 only counts those).  The bag of
+// a trie filter is found by its filter id (fs_meta), the bag of any topic by
+// its bytes through an exact-topic table of its own, laid out and probed like
+// the route image's and byte-verified against its own arena.
+constexpr uint32_t TM_NOT_LOCAL_ID = 0xFFFFFFFFu;   // ndisp of a delivery that is not the local node's
+
+struct alignas(32) SubSlot {
+    uint64_t hash;         // word_hash of the topic bytes (0 = empty slot)
+    uint32_t len;          // topic length
+    uint32_t n_plain;      // plain subscribers (entries of the segment)
+    uint64_t arena;        // topic bytes in the arena
+    uint32_t seg;          // first plain subscriber in the pool
+    uint32_t n_all;        // bag size, shared entries included
+};
+
+struct SubView {
+    const uint4*    fs_meta;        // n_filters: {segment, n_plain, n_all, 0}
+    uint32_t        n_filters;
+    uint32_t        local_target;   // target id of node() (tm_set_local_node)
+    const SubSlot*  sx_slots;       // power-of-two table, hash 0 = empty
+    uint64_t        sx_slot_mask;
+    const uint8_t*  sx_arena;
+    const uint32_t* pool;           // the plain pool
+};
+
 // ---- hashing (identical on host and device) ---------------------------------
 #if defined(__HIPCC__)
 #define TM_HD __host__ __device__ __forceinline__

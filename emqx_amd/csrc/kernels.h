@@ -143,6 +143,28 @@ hipError_t launch_aggre(const AggreView& av, uint32_t n, const uint32_t* rcount,
                         const uint32_t* src, const uint32_t* dest, uint64_t* key, uint32_t* large, uint32_t* acount, uint32_t* out_to, uint32_t* out_tg, uint64_t out_cap,
                         hipStream_t st);
 
+// emqx_broker:dispatch/2 fan-out (dispatch.hip) over the deliveries CSR that
+// launch_aggre left (acount, aoff = the route offsets, to, tg); slots =
+// min(route total, the deliveries' capacity), at most 2^32 - 2.
+//   launch_dispatch_count    per slot: ndisp (Count, or TM_NOT_LOCAL_ID), plain
+//                            count pcnt and pool segment pseg (slots entries each)
+//   launch_dispatch_lookup   the same for n Tos given by their bytes (slot i = To i)
+//   launch_scan0(pcnt, slots, P, P + slots, ...)   P[slots + 1]: first pair of each slot
+//   launch_dispatch_offsets  per topic sub_off[t] = P[aoff[t]], sub_count[t] (n + 1 / n)
+//   launch_dispatch_emit     pairs p < min(P[slots], cap): sub_id[p], and sub_to[p] =
+//                            to[slot] when to / sub_to are given; pairs_bound: an
+//                            upper bound of the pairs the caller knows (sizes the grid)
+hipError_t launch_dispatch_count(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
+                                 const uint32_t* acount, const uint64_t* aoff, const uint32_t* to, const uint32_t* tg,
+                                 uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st);
+hipError_t launch_dispatch_lookup(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
+                                  uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st);
+hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint64_t* aoff, uint32_t n,
+                                   uint32_t* sub_count, uint64_t* sub_off, hipStream_t st);
+hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
+                                const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
+                                uint64_t pairs_bound, hipStream_t st);
+
 // Sharded mode (shard.hip): merge per-topic match lists of S filter shards
 // for m topics.  counts [S][m]; source s's items start at src_base[s] of
 // ids / keys and are CSR-ordered by topic, each list in descending key order.

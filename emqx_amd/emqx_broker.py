@@ -1,0 +1,105 @@
+"""emqx_broker — the subscriber bag and publish/1's local dispatch
+(src/emqx_broker.erl), same names and semantics, backed by the MI355X engine:
+the emqx_subscriber duplicate_bag lives in the engine (tm_sub_add / tm_sub_del,
+subscribers/1) and publish/1 runs on the GPU end to end (trie walk, route
+expansion, aggre and the subscriber fan-out, dispatch.hip).
+
+    subscribe(Topic, Sub[, Group])     handle_cast #subscribe :332-345: insert_subscriber/3
+                                       :398-405, then emqx_router:add_route(Topic, dest(Group))
+    unsubscribe(Topic, Sub[, Group])   handle_cast #unsubscribe :347-358: delete_object :414,
+                                       then del_route when ets:member(?SUBSCRIBER, Topic) is false
+    subscribers(Topic)                 :245-247 -> [Sub | {share, Group, Sub}] in bag order
+    publish_many(Topics)               publish/1 :148-157 per topic: route(aggre(match_routes(T)))
+    dispatch_many(Tos)                 dispatch/2 :218-238 as a remote node's forward/3 calls it
+
+A subscriber is a u32 chosen by the caller (the NIF keeps id <-> {SubPid,
+SubId}); groups are byte strings.  The counterpart of emqx_router.py.
+"""
+from collections import namedtuple
+
+from .emqx_router import Router, _key
+from .engine import Engine, pack
+
+# one delivery of publish/1: target = (kind, key) as Router.match_deliveries_many
+# tags it; count = the Count of {dispatch, To, Count}, 0 = message.dropped, None =
+# not the local node's (a forward or a $share delivery, left to the caller)
+Delivery = namedtuple("Delivery", "to target count")
+Published = namedtuple("Published", "deliveries pairs")
+
+
+class Broker:
+    def __init__(self, engine: Engine, router: Router):
+        self.engine = engine
+        self.router = router
+        engine.set_local_node(_key(router.node))
+
+    def _dest(self, group):
+        # dest(undefined) -> node(); dest(Group) -> {Group, node()}   (:444-445)
+        return self.router.node if group is None else (group, self.router.node)
+
+    # handle_cast({From, #subscribe{}}) — :332-345
+    def subscribe(self, topic: bytes, sub: int, group=None):
+        self.engine.sub_add(topic, sub, None if group is None else _key(group))
+        self.router.add_route(topic, self._dest(group))
+        return "ok"
+
+    # handle_cast({From, #unsubscribe{}}) — :347-358
+    def unsubscribe(self, topic: bytes, sub: int, group=None):
+        left = self.engine.sub_del(topic, sub, None if group is None else _key(group))
+        if left == 0:                      # ets:member(?SUBSCRIBER, Topic) -> false
+            self.router.del_route(topic, self._dest(group))
+        return "ok"
+
+    # subscribers/1 — :245-247
+    def subscribers(self, topic: bytes):
+        names = {}
+        out = []
+        for sub, g in self.engine.subscribers(topic):
+            if g == Engine.NO_GROUP:
+                out.append(sub)
+            else:
+                if g not in names:
+                    names[g] = self.engine.sub_group_bytes(g)
+                out.append(("share", names[g], sub))
+        return out
+
+    # publish/1 — :148-157
+    def publish(self, topic: bytes):
+        return self.publish_many([topic])[0]
+
+    def publish_many(self, topics):
+        """one device batch for all topics -> [Published(deliveries, pairs)]:
+        deliveries in aggre's order, pairs = [(To, Sub)] in dispatch order"""
+        topics = list(topics)
+        buf, off = pack(topics)
+        counts, offs, to, tg, nd, scount, soff, sto, sid = self.engine.match_dispatch_batch(buf, off)
+        names, tnames, res = {}, {}, []
+
+        def name_of(s, topic):
+            if s == Engine.TOPIC_ROUTE:
+                return topic
+            if s not in names:
+                names[s] = self.engine.filter_bytes(s)
+            return names[s]
+
+        for t, topic in enumerate(topics):
+            dels = []
+            for k in range(int(offs[t]), int(offs[t]) + int(counts[t])):
+                g = int(tg[k])
+                if g not in tnames:
+                    tnames[g] = self.engine.target_bytes(g)
+                c = int(nd[k])
+                dels.append(Delivery(name_of(int(to[k]), topic), tnames[g], None if c == Engine.NOT_LOCAL else c))
+            a = int(soff[t])
+            pairs = [(name_of(int(sto[k]), topic), int(sid[k])) for k in range(a, a + int(scount[t]))]
+            res.append(Published(dels, pairs))
+        return res
+
+    # dispatch/2 — :218-238
+    def dispatch_many(self, tos):
+        """[(Count, [Sub])] per To (given by its bytes): Count counts shared
+        entries too, the list holds the plain subscribers in bag order"""
+        tos = list(tos)
+        buf, off = pack(tos)
+        nd, soff, sid = self.engine.dispatch_batch(buf, off)
+        return [(int(nd[i]), [int(x) for x in sid[int(soff[i]):int(soff[i + 1])]]) for i in range(len(tos))]

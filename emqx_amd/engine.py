@@ -434,6 +434,149 @@ class Engine:
                                                        p(d_offs), p(d_to), p(d_target), out_cap, p(d_total), st)
         return self._check(rc, "tm_match_deliveries_batch_device")
 
+    # -- emqx_broker: the subscriber bag and the local dispatch (dispatch.hip) ---
+    NO_GROUP = 0xFFFFFFFF     # group of a plain entry
+    NOT_LOCAL = 0xFFFFFFFF    # ndisp of a delivery that is not the local node's
+
+    def sub_add(self, topic: bytes, sub: int, group=None):
+        """insert_subscriber/3: group None = undefined (a plain entry)"""
+        return self._check(self.lib.tm_sub_add(self.h, topic, len(topic), sub, group, len(group) if group else 0),
+                           "tm_sub_add")
+
+    def sub_del(self, topic: bytes, sub: int, group=None) -> int:
+        """ets:delete_object of {Topic, shared(Group, Sub)}; returns the entries left in the topic's bag"""
+        left = ctypes.c_uint32()
+        self._check(self.lib.tm_sub_del(self.h, topic, len(topic), sub, group, len(group) if group else 0,
+                                        ctypes.byref(left)), "tm_sub_del")
+        return left.value
+
+    def _sub_many(self, fn, what, tbuf, toff, subs, gbuf, goff, shared):
+        n = len(toff) - 1
+        tbuf = np.ascontiguousarray(tbuf, dtype=np.uint8)
+        toff = np.ascontiguousarray(toff, dtype=np.uint64)
+        subs = np.ascontiguousarray(subs, dtype=np.uint32)
+        if shared is not None:
+            gbuf = np.ascontiguousarray(gbuf, dtype=np.uint8)
+            goff = np.ascontiguousarray(goff, dtype=np.uint64)
+            shared = np.ascontiguousarray(shared, dtype=np.uint8)
+        else:
+            gbuf = goff = None
+        return self._check(fn(self.h, _ptr(tbuf), _ptr(toff), _ptr(subs), _ptr(gbuf), _ptr(goff), _ptr(shared), n),
+                           what)
+
+    def sub_add_many(self, tbuf, toff, subs, gbuf=None, goff=None, shared=None):
+        """entry i = (topic i, subs[i]), shared with group i of (gbuf, goff) where shared[i]"""
+        return self._sub_many(self.lib.tm_sub_add_batch, "tm_sub_add_batch", tbuf, toff, subs, gbuf, goff, shared)
+
+    def sub_del_many(self, tbuf, toff, subs, gbuf=None, goff=None, shared=None):
+        return self._sub_many(self.lib.tm_sub_del_batch, "tm_sub_del_batch", tbuf, toff, subs, gbuf, goff, shared)
+
+    def subscribers(self, topic: bytes):
+        """subscribers/1: [(sub, group id or NO_GROUP)] in bag order"""
+        n = ctypes.c_uint32()
+        cap = 16
+        while True:
+            sub = np.zeros(cap, dtype=np.uint32)
+            grp = np.zeros(cap, dtype=np.uint32)
+            rc = self.lib.tm_subscribers(self.h, topic, len(topic), _ptr(sub), _ptr(grp), cap, ctypes.byref(n))
+            if rc == L.TM_ENOSPC:
+                cap = n.value
+                continue
+            self._check(rc, "tm_subscribers")
+            return [(int(s), int(g)) for s, g in zip(sub[: n.value], grp[: n.value])]
+
+    def sub_group_bytes(self, group_id: int) -> bytes:
+        n = ctypes.c_uint32()
+        p = self.lib.tm_sub_group_bytes(self.h, group_id, ctypes.byref(n))
+        if not p:
+            raise KeyError(group_id)
+        return ctypes.string_at(p, n.value)
+
+    @property
+    def sub_count(self):
+        return self.lib.tm_sub_count(self.h)
+
+    def set_local_node(self, node: bytes):
+        """the node() of route/2's Node =:= node() guard"""
+        return self._check(self.lib.tm_set_local_node(self.h, node, len(node)), "tm_set_local_node")
+
+    def debug_check_subs(self):
+        """host-side consistency check of the in-place subscriber image
+        (diagnostic, tm_debug_check_subs)"""
+        self.lib.tm_debug_check_subs.argtypes = [ctypes.c_void_p]
+        return self._check(self.lib.tm_debug_check_subs(self.h), "tm_debug_check_subs")
+
+    def match_dispatch_batch(self, buf, off, out_cap=None, sub_cap=None):
+        """Host batch -> (counts u32[n], offsets u64[n+1], to, target, ndisp
+        (one per delivery slot), sub_count u32[n], sub_off u64[n+1], sub_to,
+        sub_id): publish/1's deliveries with the local dispatch.  out_cap /
+        sub_cap None: retried at the needed sizes; given: one call
+        (TopicMatchError TM_ENOSPC when either is short)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        counts = np.zeros(max(n, 1), dtype=np.uint32)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        scount = np.zeros(max(n, 1), dtype=np.uint32)
+        soff = np.zeros(n + 1, dtype=np.uint64)
+        cap = 1 << 16 if out_cap is None else out_cap
+        scap = 1 << 16 if sub_cap is None else sub_cap
+        while True:
+            to, tg, nd = (np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(3))
+            sto, sid = (np.zeros(max(scap, 1), dtype=np.uint32) for _ in range(2))
+            needed, sneeded = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = self.lib.tm_match_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs), _ptr(to),
+                                                  _ptr(tg), _ptr(nd), cap, ctypes.byref(needed), _ptr(scount),
+                                                  _ptr(soff), _ptr(sto), _ptr(sid), scap, ctypes.byref(sneeded))
+            if rc == L.TM_ENOSPC and (out_cap is None or needed.value <= cap) and \
+                    (sub_cap is None or sneeded.value <= scap):
+                cap = max(cap, int(needed.value))
+                scap = max(scap, int(sneeded.value))
+                continue
+            if rc == L.TM_ENOSPC:
+                e = L.TopicMatchError(rc, "tm_match_dispatch_batch: needs %d deliveries, %d pairs"
+                                      % (needed.value, sneeded.value))
+                e.needed, e.sub_needed = int(needed.value), int(sneeded.value)
+                raise e
+            self._check(rc, "tm_match_dispatch_batch")
+            k, sk = int(needed.value), int(sneeded.value)
+            return counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk]
+
+    def match_dispatch_batch_device(self, d_bytes, d_off, n, topic_bytes, d_counts, d_offs, d_to, d_target, d_ndisp,
+                                    out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap,
+                                    d_sub_total, stream=None):
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_match_dispatch_batch_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts),
+                                                     p(d_offs), p(d_to), p(d_target), p(d_ndisp), out_cap, p(d_total),
+                                                     p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,
+                                                     p(d_sub_total), st)
+        return self._check(rc, "tm_match_dispatch_batch_device")
+
+    def dispatch_batch(self, buf, off, cap=None):
+        """dispatch/2 by To bytes -> (ndisp u32[n], sub_off u64[n+1], sub_id)"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        nd = np.zeros(max(n, 1), dtype=np.uint32)
+        soff = np.zeros(n + 1, dtype=np.uint64)
+        c = 1 << 16 if cap is None else cap
+        while True:
+            sid = np.zeros(max(c, 1), dtype=np.uint32)
+            needed = ctypes.c_uint64()
+            rc = self.lib.tm_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(nd), _ptr(soff), _ptr(sid), c,
+                                            ctypes.byref(needed))
+            if rc == L.TM_ENOSPC and cap is None:
+                c = int(needed.value)
+                continue
+            self._check(rc, "tm_dispatch_batch")
+            return nd[:n], soff, sid[: int(needed.value)]
+
     # walk variants (A/B knobs of tm_walk_queue): one global dequeue head, or
     # per-XCD heads over contiguous ranges of the batch
     WALKS = {"queue": 0, "queue_xcd": 1}

@@ -512,6 +512,99 @@ int tm_match_deliveries_batch_device(tm_engine* e, const uint8_t* d_topic_bytes,
                                      uint32_t* d_out_to, uint32_t* d_out_target, uint64_t out_cap,
                                      uint64_t* d_total, void* hip_stream);
 
+/* ---- local dispatch: the emqx_subscriber bag and publish/1's fan-out ---------
+ * (emqx_amd/csrc/dispatch.hip)  publish/1 runs route(aggre(match_routes(Topic)),
+ * Delivery) (src/emqx_broker.erl:148-157); for every delivery {To, node()}
+ * dispatch/2 (:218-238) reads subscribers(To) from the emqx_subscriber
+ * duplicate_bag (:245-247; table src/emqx_broker_sup.erl:55-67) and sends
+ * {dispatch, To, Msg} to each.  The engine keeps that bag and returns the
+ * (To, subscriber) pairs.
+ *
+ * A subscriber is a caller-chosen u32 (the NIF keeps id <-> {SubPid, SubId});
+ * 0xFFFFFFFF is reserved (TM_EINVAL).  A shared subscription's group is opaque
+ * bytes, interned to a group id; group == NULL is the atom undefined (a plain
+ * entry).  None of these calls touches the trie or the route bag: those stay
+ * the caller's add_route / del_route (tm_route_add / tm_route_del).  Changes
+ * reach the device with the next tm_commit, exactly as route changes do. */
+#define TM_NO_GROUP  0xFFFFFFFFu   /* out_group of a plain entry                      */
+#define TM_NOT_LOCAL 0xFFFFFFFFu   /* out_ndisp of a delivery that is not node()'s    */
+
+/* insert_subscriber/3 — src/emqx_broker.erl:398-415.  When the bag of `topic`
+ * already holds the PLAIN entry `sub` the call is a no-op whatever `group` is
+ * (the membership test :399-405 is on the bare Subscriber); otherwise
+ * shared(Group, sub) goes last in the bag.  So a repeated shared add
+ * duplicates the entry, and only a plain entry suppresses an add. */
+int tm_sub_add(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group, uint32_t glen);
+
+/* ets:delete_object(emqx_subscriber, {Topic, shared(Group, Sub)}) — do_unsubscribe/3
+ * :412-415, shared/2 :447-448 (unsubscribe :347-358): every equal object goes, duplicates included; an
+ * absent object is a no-op.  *remaining (may be NULL) = entries left in the
+ * topic's bag: the caller's ets:member test at :354 decides del_route. */
+int tm_sub_del(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group, uint32_t glen,
+               uint32_t* remaining);
+
+/* Bulk forms, laid out as tm_route_add_batch and applied in order: entry i =
+ * (topic [topic_off[i], topic_off[i+1]), subs[i], group).  Entry i is shared
+ * when shared && shared[i], its group then [group_off[i], group_off[i+1]) of
+ * groups; shared == NULL: every entry is plain (groups / group_off unused). */
+int tm_sub_add_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                     const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared, uint32_t n);
+int tm_sub_del_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                     const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared, uint32_t n);
+
+/* subscribers/1 — :245-247: the bag of `topic` in insertion order; out_group[i]
+ * = group id of a shared entry or TM_NO_GROUP (either array may be NULL with
+ * cap 0).  *out_n = entries (TM_ENOSPC when it exceeds cap). */
+int tm_subscribers(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t* out_sub, uint32_t* out_group,
+                   uint32_t cap, uint32_t* out_n);
+/* group id -> group bytes (engine-owned, valid until the next tm_sub_add on e) */
+const uint8_t* tm_sub_group_bytes(tm_engine* e, uint32_t group_id, uint32_t* len);
+/* entries of the bag over all topics (ets:info(emqx_subscriber, size)) */
+uint64_t tm_sub_count(tm_engine* e);
+
+/* The key of the TM_TARGET_NODE target that is node() (the Node =:= node()
+ * guard of route/2, :185-186).  Until it is called the dispatch calls below
+ * return TM_EINVAL. */
+int tm_set_local_node(tm_engine* e, const uint8_t* node, uint32_t len);
+
+/* publish/1 over a batch: the deliveries arrays exactly as
+ * tm_match_deliveries_batch returns them, and for delivery slot j
+ * out_ndisp[j]: the Count of {dispatch, To, Count} (:225-232: the bag size,
+ * shared entries included; 0 = the message.dropped case :221-224), or
+ * TM_NOT_LOCAL for a forward or a $share delivery, left to the caller
+ * (:185-189).  The pairs of topic t are sub_to / sub_id[sub_off[t] .. +
+ * sub_count[t]): sub_to = the To (filter id or TM_ROUTE_TOPIC), sub_id = a
+ * plain subscriber of To; deliveries in aggre's order (route/2 folds left,
+ * :191-192), bag order within a delivery.  Shared entries count in out_ndisp
+ * and produce no pair (picking a member is emqx_shared_sub's).  sub_off has
+ * n+1 entries.  Each capacity reports its own need: TM_ENOSPC when the route
+ * total exceeds out_cap (*out_needed) or the pairs exceed sub_cap
+ * (*sub_needed), counts and offsets still filled, as tm_match_batch.  Host
+ * buffers, synchronous; walk, routes, aggre and dispatch all run on the GPU
+ * (of the engine's first replica). */
+int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                            uint64_t* sub_needed);
+/* Same with device buffers on hip_stream, by the conventions of
+ * tm_match_deliveries_batch_device: *d_total = route total, deliveries at or
+ * past out_cap are dropped (and dispatch nothing); *d_sub_total = pairs of the
+ * deliveries kept, pairs past sub_cap are dropped. */
+int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
+                                   uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count, uint64_t* d_out_off,
+                                   uint32_t* d_out_to, uint32_t* d_out_target, uint32_t* d_out_ndisp, uint64_t out_cap,
+                                   uint64_t* d_total, uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to,
+                                   uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total, void* hip_stream);
+
+/* dispatch/2 as a remote node's forward/3 calls it (:209-216): To i is given
+ * by its bytes [to_off[i], to_off[i+1]).  ndisp[i] = the Count (0: no
+ * subscribers), the plain subscribers of To i are sub_id[sub_off[i] ..
+ * sub_off[i+1]) in bag order.  TM_ENOSPC / *needed as tm_match_batch.  Host
+ * buffers, synchronous, on the GPU. */
+int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
+                      uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed);
+
 /* ---- publish micro-batcher (emqx_amd/csrc/batcher.cpp) -----
  * emqx_broker:publish/1 (src/emqx_broker.erl:148-157) matches one topic per
  * call in the publisher's process.  The NIF instead submits the topic here
