@@ -431,6 +431,8 @@ __device__ __forceinline__ uint32_t tokenize_one(const ImageView& im, const B& b
 // its word id); 1000 keeps a 4-wave block at 32.5 KB of LDS, 5 blocks per CU
 // (5 waves per SIMD, as the VGPRs allow); a wave with more: the per-lane path
 constexpr uint32_t TOK_LMAX = 1000;
+// a level's descriptor packs start | length << 16: both are byte offsets into the wave's window
+static_assert(TOK_WIN_WORDS * 8 + 8 <= 65536, "a window offset or level length must fit 16 bits");
 constexpr uint32_t TOK_WAVE = 1u << 24;   // key_mode bit: the wave path (option "tok_wave"; 0: per lane)
 #ifndef TM_TOK_BATCH
 #define TM_TOK_BATCH 3   // dictionary probes in flight per lane (4 held to 96 VGPRs, or at 97 and 4 waves:

@@ -194,7 +194,25 @@ void tm_free(void* p);
  * have n+1 entries and topic_bytes = d_topic_off[n] - d_topic_off[0] (sizes
  * the engine's workspace without a device read).  Calls on one engine must
  * be issued on one stream.  This is the entry a pipelined batcher and the
- * bench use. */
+ * bench use.
+ *
+ * What every device entry that takes (d_topic_bytes, d_topic_off) requires of
+ * the byte buffer (this one, tm_match_small_device, the _keys / _keys_w forms,
+ * tm_match_routes_batch_device, tm_match_deliveries_batch_device,
+ * tm_match_dispatch_batch_device and tm_route_in.d_bytes): the kernels read
+ * topic bytes as aligned 8-byte words, so
+ *   - d_topic_bytes is 8-byte aligned (any hipMalloc'd base is);
+ *   - every aligned 8-byte word that holds a topic byte is readable: from
+ *     d_topic_bytes + (d_topic_off[0] & ~7) through the word holding byte
+ *     d_topic_off[n] - 1, i.e. up to 7 bytes past d_topic_off[n] (allocate 8
+ *     spare bytes).  Bytes outside [d_topic_off[0], d_topic_off[n]) are loaded
+ *     but never interpreted: they may hold anything;
+ *   - d_topic_off is non-decreasing and may start anywhere: d_topic_off[0]
+ *     need not be 0 nor a multiple of 8 (a batch may be a slice of a larger
+ *     buffer), and topic_bytes is exactly d_topic_off[n] - d_topic_off[0]
+ *     (the words of topics past 16 levels are stored by byte offset from
+ *     d_topic_off[0] in a workspace of that size: a smaller value overruns
+ *     it).  Any byte value is a topic byte; only '/' (0x2F) separates. */
 int tm_match_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
                           uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count,
                           uint64_t* d_out_off, uint32_t* d_out_filter_id, uint64_t out_cap,
