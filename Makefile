@@ -43,6 +43,9 @@ $(BUILD)/aggre.o: emqx_amd/csrc/aggre.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/
 $(BUILD)/dispatch.o: emqx_amd/csrc/dispatch.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(BUILD)/share.o: emqx_amd/csrc/share.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(BUILD)/exchange.o: emqx_amd/csrc/exchange.cpp emqx_amd/csrc/kernels.h include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O2 -fPIC -std=c++17 -Wall -c $< -o $@
 
@@ -58,7 +61,8 @@ $(BUILD)/acl.o: emqx_amd/csrc/acl.hip include/topicmatch.h | $(BUILD)
 $(BUILD)/rewrite.o: emqx_amd/csrc/rewrite.hip include/topicmatch.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIBOUT): $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
+LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
+$(LIBOUT): $(LIBOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -pthread $^ -L/opt/rocm/lib -lrccl -o $@
 
 emqx_amd/libtmwork.so: emqx_amd/csrc/workload.c
@@ -87,3 +91,16 @@ tools/ubench/batcher_bench: tools/ubench/batcher_bench.cpp emqx_amd/libtopicmatc
 # batcher driver for bench.py's batcher leg (measurement helper, ctypes)
 tools/ubench/libbatchdrive.so: tools/ubench/batchdrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
+
+# tm_share_* host calls under AddressSanitizer + UBSan on a host-only engine:
+# engine.cpp instrumented, the kernels linked as built and never run.  Leak
+# detection stays on for the engine's own allocations; the HIP and RCCL
+# runtimes' start-up allocations are suppressed by library name.
+SAN = -fsanitize=address,undefined -fno-omit-frame-pointer
+SAN_OBJS = $(filter-out $(BUILD)/engine.o,$(filter %.o,$(LIBOBJS)))
+san_share: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 $(SAN) $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 $(SAN) -c tools/san_share.cpp -o $(BUILD)/san_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_share
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_share
+.PHONY: san_share

@@ -246,6 +246,30 @@ SIGNATURES = [
     ("tm_dispatch_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.c_void_p]),
+    ("tm_share_add", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                                    ctypes.c_uint32, ctypes.c_uint32]),
+    ("tm_share_del", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                                    ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_share_add_batch", ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint32]),
+    ("tm_share_del_batch", ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_uint32]),
+    ("tm_share_member_down", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_share_members", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                        ctypes.POINTER(ctypes.c_uint32)]),
+    ("tm_share_count", ctypes.c_uint64, [ctypes.c_void_p]),
+    ("tm_match_publish_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                              ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_match_publish_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
     ("tm_batcher_open", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,

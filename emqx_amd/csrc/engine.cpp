@@ -124,6 +124,61 @@ struct Track {
     }
 };
 
+// A host mirror of an open-addressing device table (power-of-two slots, load
+// <= 1/2, linear probing, backward-shift deletion as rt_slot_del) with its
+// dirty log.  Slot: empty() / home(), a value-initialised Slot is empty;
+// Rec: the owner of a slot, which keeps its slot index in Rec::slot.
+template <class Slot, class Rec>
+struct MirrorTable {
+    std::vector<Slot> slots = std::vector<Slot>(16, Slot{});
+    std::vector<Rec*> rec = std::vector<Rec*>(16, nullptr);
+    size_t used = 0;
+    Track t;
+    void place(const Slot& v, Rec* r) {
+        const size_t mask = slots.size() - 1;
+        size_t s = v.home() & mask;
+        while (!slots[s].empty()) s = (s + 1) & mask;
+        slots[s] = v;
+        rec[s] = r;
+        r->slot = (uint32_t)s;
+        ++used;
+        t.cur.mark(s);
+    }
+    void put(const Slot& v, Rec* r) {
+        if ((used + 1) * 2 > slots.size()) {
+            std::vector<std::pair<Slot, Rec*>> old;
+            old.reserve(used);
+            for (size_t s = 0; s < slots.size(); ++s)
+                if (rec[s]) old.emplace_back(slots[s], rec[s]);
+            slots.assign(slots.size() * 2, Slot{});
+            rec.assign(slots.size(), nullptr);
+            used = 0;
+            for (auto& x : old) place(x.first, x.second);
+            t.cur.all = true;
+        }
+        place(v, r);
+    }
+    void del(Rec* r) {
+        const size_t mask = slots.size() - 1;
+        size_t i = r->slot;
+        for (size_t j = (i + 1) & mask; !slots[j].empty(); j = (j + 1) & mask) {
+            const size_t home = slots[j].home() & mask;
+            const bool stays = i <= j ? (home > i && home <= j) : (home > i || home <= j);
+            if (stays) continue;
+            slots[i] = slots[j];
+            rec[i] = rec[j];
+            rec[i]->slot = (uint32_t)i;
+            t.cur.mark(i);
+            i = j;
+        }
+        slots[i] = Slot{};
+        rec[i] = nullptr;
+        t.cur.mark(i);
+        r->slot = 0xFFFFFFFFu;
+        --used;
+    }
+};
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -246,6 +301,10 @@ struct Image {
     DevBuf d_fshape;   // option "shape_keys": filter id -> order key
     // subscriber image (dispatch.hip), same epoch as the trie and the routes
     DevBuf d_sslots, d_sarena, d_spool, d_fs_meta;
+    // share image (share.hip), same epoch; cursor: the replica's round-robin
+    // cursors (DevState::sh_cursor) as they were when this image was written
+    DevBuf d_hsets, d_htx, d_harena, d_hpool, d_hfx;
+    uint32_t* cursor = nullptr;
     DevBuf d_wheat;    // word id -> heat (option "presort" 2: the tail order's cost estimate)
     size_t arena_uploaded = 0, woff_uploaded = 0;
     uint64_t heat_uploaded = ~0ull;   // word_heat version in d_wheat
@@ -260,10 +319,11 @@ struct Image {
     RouteView rv{};
     AggreView av{};
     SubView sv{};
+    ShareView hv{};
     void release() {
         for (DevBuf* b : {&d_nodes, &d_edges, &d_hedges, &d_dict, &d_arena, &d_woff, &d_inner, &d_leaf, &d_rslots,
                           &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat,
-                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta})
+                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx})
             b->release();
         for (hipEvent_t ev : uses) (void)hipEventDestroy(ev);
         uses.clear();
@@ -356,6 +416,16 @@ struct DevState {
     // dispatch (dispatch.hip): per-slot plain counts, segments and prefix, and
     // the host-buffer call's deliveries / pairs before they go back
     DevBuf w_xpcnt, w_xpseg, w_xpre, w_xscan, w_xto, w_xscount, w_xsoff, w_xsub;
+    // shared-subscription pick (share.hip): per-slot Count / segment / set index
+    // / flag and the flag prefix, the (set index, slot) pairs and their sort,
+    // the runs' new cursors, and the host-buffer call's keys and picks
+    DevBuf w_hcnt, w_hseg, w_hset, w_hflag, w_hpre, w_hscan, w_hpairs, w_hnew, w_hcounts, w_hoff, w_hsscan, w_hkey,
+        w_hpick;
+    // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
+    // the image epochs, so a batch continues where the one before it stopped
+    // whichever image each was launched on
+    DevBuf sh_cursor;
+    uint32_t sh_cursor_n = 0;   // entries
     DevBuf w_mpre, w_mscan, w_bytes, w_off, w_counts, w_outoff, w_ids, w_total;
     // the route / aggre workspaces are shared by every stream:
     // rw_done is recorded after the last route or aggre kernel of a batch;
@@ -397,6 +467,8 @@ struct DevState {
         for (DevBuf* b : {&stage_dev, &w_rexact, &w_rscan, &w_rids, &w_rcounts, &w_roff, &w_dsrc, &w_dcount, &w_akey,
                           &w_alarge, &w_mpre, &w_mscan, &w_bytes, &w_off, &w_counts, &w_outoff, &w_ids, &w_total,
                           &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
+                          &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
+                          &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &sh_cursor,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -708,6 +780,57 @@ struct tm_engine {
     Track t_sslots, t_sarena, t_spool, t_fs_meta;
     bool local_set = false;        // tm_set_local_node: the target that is node()
     uint32_t local_target = 0;
+
+    // ---- shared subscriptions: the emqx_shared_subscription bag ----
+    // (src/emqx_shared_sub.erl:49-62: a mnesia bag of {group, topic, subpid}).
+    // A member is a caller-chosen u32; the group is the TM_TARGET_GROUP target
+    // aggre/1 leaves in {To, Group}.  One ShareSet per (group, topic) with
+    // members, in insertion order (ETS's order for the objects of one key).
+    struct ShareTopic;
+    struct ShareSet {
+        ShareTopic* topic = nullptr;
+        uint32_t tg = 0;                    // group target id
+        std::vector<uint32_t> members;      // list order; a member at most once (bag, not duplicate_bag)
+        uint32_t six = 0;                   // set index: the slot of its round-robin cursor
+        uint32_t off = 0, cap = 0;          // member segment in sh_pool
+        uint32_t slot = SLOT_NONE;          // sh_sets slot (every set with a member has one)
+    };
+    struct ShareTopic {
+        const std::string* key = nullptr;   // the sh_topics key (node-stable)
+        bool wild = false;
+        uint32_t fid = FILTER_NONE;         // wildcard topic: its trie filter, while both exist (the To key)
+        uint32_t xid = 0;                   // exact topic: its dense To key
+        uint32_t slot = SLOT_NONE;          // exact topic: sh_tx slot
+        uint64_t arena = 0, words = 0;      // exact topic: its bytes in sh_arena (u64 words)
+        std::unordered_map<uint32_t, std::unique_ptr<ShareSet>> sets;   // group target id -> set
+    };
+    std::unordered_map<std::string, ShareTopic> sh_topics;
+    // member -> the sets that hold it: cleanup_down/1 without a table scan,
+    // and the bag's "already present" test
+    std::unordered_map<uint32_t, std::vector<ShareSet*>> sh_member_sets;
+    std::unordered_map<uint32_t, ShareTopic*> sh_fid_topic;   // filter id -> linked wildcard topic
+    size_t sh_total = 0;
+    // The share image, kept in place like the subscriber image: the set table
+    // (sh_sets: (group target, xid) -> {Count, segment, set index}), the
+    // exact-topic table of every topic with a set (sh_tx / sh_arena -> xid),
+    // fx (filter id -> xid of a wildcard topic) and the member pool (sh_pool).
+    MirrorTable<ShareSetSlot, ShareSet> sh_sets;
+    MirrorTable<ShareTopicSlot, ShareTopic> sh_tx;
+    std::vector<uint64_t> sh_arena;
+    size_t sh_arena_garbage = 0;
+    std::vector<uint32_t> sh_pool;
+    size_t sh_pool_garbage = 0;
+    std::vector<uint32_t> sh_fx;   // filter id -> xid of the wildcard topic it is (SLOT_NONE: none), as fs_meta
+    Track t_sh_arena, t_sh_pool, t_sh_fx;
+    std::vector<uint32_t> sh_free_xid;   // an xid names a topic only within one image: reusable at once
+    uint32_t sh_next_xid = 0;
+    // Set indices name cursors that outlive the images, so an index is reused
+    // as a filter id is: once both image epochs are rewritten without its old
+    // set (no batch in flight can still advance the old set's cursor), and its
+    // cursor is reset by the commit that frees it.
+    std::vector<uint32_t> sh_free_six;
+    uint32_t sh_next_six = 0;
+    std::deque<std::pair<uint64_t, uint32_t>> sh_six_quarantine;   // (epoch from which images lack the set, index)
 
     // ---- batch pipeline knobs ----
     int nslots = 2;                     // option "slots"
@@ -1165,11 +1288,13 @@ struct tm_engine {
         ++live_filters;
         on_filter_new(p, len, id);
         on_filter_new_subs(p, len, id);
+        on_filter_new_shares(p, len, id);
         return id;
     }
     void free_filter(uint32_t id) {
         on_filter_free(id);
         on_filter_free_subs(id);
+        on_filter_free_shares(id);
         filters[id].node = NODE_NONE;   // off / len stay: the gather serves the id until it is reused
         quarantine.emplace_back(epoch.load() + 1, id);   // the next commit drops it from the images
         quarantined[id] = epoch.load() + 1;
@@ -1765,6 +1890,289 @@ struct tm_engine {
         return sv;
     }
 
+    // ------------------------------------------------------------------
+    // shared subscriptions (emqx_shared_sub.erl): the member bag and the image
+    // share.hip reads.  Independent of the trie, the routes and the
+    // emqx_subscriber bag.
+    void on_filter_new_shares(const uint8_t* p, uint32_t len, uint32_t fid) {
+        if (sh_topics.empty() || !tm_topic_wildcard(p, len)) return;
+        auto it = sh_topics.find(std::string(reinterpret_cast<const char*>(p), len));
+        if (it == sh_topics.end() || it->second.fid != FILTER_NONE) return;
+        share_fx_link(it->second, fid);
+    }
+    void share_fx_link(ShareTopic& tp, uint32_t fid) {
+        if (fid == FILTER_NONE) return;
+        if (fid >= sh_fx.size()) {
+            const size_t old = sh_fx.size(), n = std::max<size_t>(fid + 1, filters.size());
+            sh_fx.resize(n, SLOT_NONE);
+            t_sh_fx.mark_range(old, n);
+        }
+        tp.fid = fid;
+        sh_fid_topic[fid] = &tp;
+        sh_fx[fid] = tp.xid;
+        t_sh_fx.cur.mark(fid);
+    }
+    void share_fx_unlink(ShareTopic& tp) {
+        if (tp.fid == FILTER_NONE) return;
+        sh_fx[tp.fid] = SLOT_NONE;
+        t_sh_fx.cur.mark(tp.fid);
+        sh_fid_topic.erase(tp.fid);
+        tp.fid = FILTER_NONE;
+    }
+    void on_filter_free_shares(uint32_t fid) {
+        auto it = sh_fid_topic.find(fid);
+        if (it == sh_fid_topic.end()) return;
+        share_fx_unlink(*it->second);
+    }
+    void share_slot_put(ShareSet& s) {
+        const ShareTopic& tp = *s.topic;
+        sh_sets.put(ShareSetSlot{s.tg, tp.xid, (uint32_t)s.members.size(), s.off, s.six, 0u, 0u, 0u}, &s);
+    }
+    void share_sync(const ShareSet& s) {
+        if (s.slot == SLOT_NONE) return;
+        ShareSetSlot& x = sh_sets.slots[s.slot];
+        x.count = (uint32_t)s.members.size();
+        x.seg = s.off;
+        sh_sets.t.cur.mark(s.slot);
+    }
+    // the members of s into its segment (a new, doubled segment at the
+    // pool's end when they no longer fit)
+    void share_seg_rewrite(ShareSet& s) {
+        const size_t n = s.members.size();
+        if (n > s.cap) {
+            sh_pool_garbage += s.cap;
+            uint32_t cap = std::max<uint32_t>(s.cap * 2, 2);
+            while (cap < n) cap *= 2;
+            if (sh_pool.size() + cap >= 0xFFFFFFF0ull) throw RangeError("share member pool past 2^32 entries");
+            s.off = (uint32_t)sh_pool.size();
+            s.cap = cap;
+            sh_pool.resize(sh_pool.size() + cap, 0);
+        }
+        std::copy(s.members.begin(), s.members.end(), sh_pool.begin() + s.off);
+        t_sh_pool.mark_range(s.off, s.off + n);
+        share_sync(s);
+    }
+    uint32_t share_alloc_six() {
+        if (!sh_free_six.empty()) {
+            const uint32_t i = sh_free_six.back();
+            sh_free_six.pop_back();
+            return i;
+        }
+        if (sh_next_six >= 0xFFFFFFF0u) throw RangeError("share set indices exhausted");
+        return sh_next_six++;
+    }
+    // the indices no image and no batch in flight names any more (freed at
+    // epoch E: absent from the images of E + 1 and E + 2, and the commit that
+    // wrote E + 2 waited for the batches on the last image that had them)
+    std::vector<uint32_t> release_share_indices() {
+        std::vector<uint32_t> out;
+        const uint64_t now = epoch.load();
+        while (!sh_six_quarantine.empty() && now >= sh_six_quarantine.front().first + 1) {
+            out.push_back(sh_six_quarantine.front().second);
+            sh_six_quarantine.pop_front();
+        }
+        sh_free_six.insert(sh_free_six.end(), out.begin(), out.end());
+        return out;
+    }
+    // mnesia:dirty_write of record(Group, Topic, SubPid) (:77-79): a record
+    // already in the bag leaves it as it was
+    void share_add(const uint8_t* g, uint32_t glen, const uint8_t* t, uint32_t tlen, uint32_t member) {
+        const size_t ntg = target_names.size();
+        const uint32_t tg = intern_target(TM_TARGET_GROUP, g, glen);
+        if (target_names.size() != ntg) {
+            targets_dirty = true;
+            dev_dirty = true;
+        }
+        std::string key(reinterpret_cast<const char*>(t), tlen);
+        auto it = sh_topics.find(key);
+        if (it == sh_topics.end()) {
+            it = sh_topics.emplace(std::move(key), ShareTopic{}).first;
+            ShareTopic& tp = it->second;
+            tp.key = &it->first;
+            tp.wild = tm_topic_wildcard(t, tlen);
+            if (!sh_free_xid.empty()) {
+                tp.xid = sh_free_xid.back();
+                sh_free_xid.pop_back();
+            } else {
+                tp.xid = sh_next_xid++;
+            }
+            tp.words = std::max<uint64_t>(1, (tlen + 7) / 8);
+            tp.arena = sh_arena.size();
+            sh_arena.resize(sh_arena.size() + tp.words, 0);
+            if (tlen) std::memcpy(&sh_arena[tp.arena], t, tlen);
+            t_sh_arena.mark_range(tp.arena, tp.arena + tp.words);
+            sh_tx.put(ShareTopicSlot{word_hash(t, tlen), tlen, tp.xid, tp.arena * 8, 0}, &tp);
+            if (tp.wild) share_fx_link(tp, filter_of(t, tlen));
+        }
+        ShareTopic& tp = it->second;
+        std::unique_ptr<ShareSet>& sp = tp.sets[tg];
+        std::vector<ShareSet*>& of = sh_member_sets[member];
+        if (!sp) {
+            sp.reset(new ShareSet());
+            sp->topic = &tp;
+            sp->tg = tg;
+            sp->six = share_alloc_six();
+        } else if (std::find(of.begin(), of.end(), sp.get()) != of.end()) {
+            return;
+        }
+        ShareSet& s = *sp;
+        s.members.push_back(member);
+        of.push_back(&s);
+        if (s.members.size() > s.cap) {
+            share_seg_rewrite(s);
+        } else {
+            sh_pool[s.off + s.members.size() - 1] = member;
+            t_sh_pool.cur.mark(s.off + s.members.size() - 1);
+            share_sync(s);
+        }
+        if (s.slot == SLOT_NONE) share_slot_put(s);   // a new set: in the table once it has its member
+        ++sh_total;
+        dev_dirty = true;
+    }
+    ShareSet* share_find(const uint8_t* g, uint32_t glen, const uint8_t* t, uint32_t tlen) {
+        std::string gk(1, (char)TM_TARGET_GROUP);
+        gk.append(reinterpret_cast<const char*>(g), glen);
+        auto ti = target_index.find(gk);
+        if (ti == target_index.end()) return nullptr;
+        auto it = sh_topics.find(std::string(reinterpret_cast<const char*>(t), tlen));
+        if (it == sh_topics.end()) return nullptr;
+        auto si = it->second.sets.find(ti->second);
+        return si == it->second.sets.end() ? nullptr : si->second.get();
+    }
+    // member gone from s (its sh_member_sets entry is the caller's): the
+    // segment rewritten, or the emptied set (and a topic left without sets)
+    // dropped -- its index goes to quarantine, so the cursor is forgotten
+    void share_after_remove(ShareSet& s) {
+        --sh_total;
+        dev_dirty = true;
+        if (!s.members.empty()) return share_seg_rewrite(s);
+        ShareTopic& tp = *s.topic;
+        if (s.slot != SLOT_NONE) sh_sets.del(&s);
+        sh_pool_garbage += s.cap;
+        sh_six_quarantine.emplace_back(epoch.load() + 1, s.six);
+        const uint32_t tg = s.tg;
+        tp.sets.erase(tg);   // frees s
+        if (!tp.sets.empty()) return;
+        share_fx_unlink(tp);
+        sh_tx.del(&tp);
+        sh_free_xid.push_back(tp.xid);
+        sh_arena_garbage += tp.words;
+        const std::string key = *tp.key;
+        sh_topics.erase(key);
+    }
+    // mnesia:dirty_delete_object (:83-84): an absent record is a no-op;
+    // returns the members left in the (Group, Topic) set
+    uint32_t share_del(const uint8_t* g, uint32_t glen, const uint8_t* t, uint32_t tlen, uint32_t member) {
+        ShareSet* s = share_find(g, glen, t, tlen);
+        if (!s) return 0;
+        auto pos = std::find(s->members.begin(), s->members.end(), member);
+        if (pos == s->members.end()) return (uint32_t)s->members.size();
+        s->members.erase(pos);
+        auto mi = sh_member_sets.find(member);
+        std::vector<ShareSet*>& of = mi->second;
+        of.erase(std::find(of.begin(), of.end(), s));
+        if (of.empty()) sh_member_sets.erase(mi);
+        const uint32_t left = (uint32_t)s->members.size();
+        share_after_remove(*s);
+        maybe_compact_shares();
+        return left;
+    }
+    // cleanup_down/1 (:316-321): every record of the member, whatever the group or topic
+    uint32_t share_member_down(uint32_t member) {
+        auto mi = sh_member_sets.find(member);
+        if (mi == sh_member_sets.end()) return 0;
+        const std::vector<ShareSet*> of = std::move(mi->second);
+        sh_member_sets.erase(mi);
+        for (ShareSet* s : of) {
+            s->members.erase(std::find(s->members.begin(), s->members.end(), member));
+            share_after_remove(*s);
+        }
+        maybe_compact_shares();
+        return (uint32_t)of.size();
+    }
+    void maybe_compact_shares() {
+        const bool pool_gc = sh_pool_garbage > route_gc_min && sh_pool_garbage * 2 > sh_pool.size();
+        const bool arena_gc = sh_arena_garbage > route_gc_min / 4 && sh_arena_garbage * 2 > sh_arena.size();
+        if (!pool_gc && !arena_gc) return;
+        std::vector<uint32_t> np;
+        std::vector<uint64_t> na;
+        for (auto& kv : sh_topics) {
+            ShareTopic& tp = kv.second;
+            if (pool_gc)
+                for (auto& sk : tp.sets) {
+                    ShareSet& s = *sk.second;
+                    const uint32_t off = (uint32_t)np.size();
+                    np.insert(np.end(), sh_pool.begin() + s.off, sh_pool.begin() + s.off + s.cap);
+                    s.off = off;
+                    share_sync(s);
+                }
+            if (arena_gc) {
+                const uint64_t a = na.size();
+                na.insert(na.end(), sh_arena.begin() + tp.arena, sh_arena.begin() + tp.arena + tp.words);
+                tp.arena = a;
+                sh_tx.slots[tp.slot].arena = a * 8;
+                sh_tx.t.cur.mark(tp.slot);
+            }
+        }
+        if (pool_gc) {
+            sh_pool.swap(np);
+            sh_pool_garbage = 0;
+            t_sh_pool.cur.all = true;
+        }
+        if (arena_gc) {
+            sh_arena.swap(na);
+            sh_arena_garbage = 0;
+            t_sh_arena.cur.all = true;
+        }
+    }
+    ShareView make_share_view(const Image& g) const {
+        ShareView hv;
+        hv.sets = g.d_hsets.as<const ShareSetSlot>();
+        hv.set_mask = sh_sets.slots.size() - 1;
+        hv.tx_slots = g.d_htx.as<const ShareTopicSlot>();
+        hv.tx_mask = sh_tx.slots.size() - 1;
+        hv.tx_arena = g.d_harena.as<const uint8_t>();
+        hv.pool = g.d_hpool.as<const uint32_t>();
+        hv.fx = g.d_hfx.as<const uint32_t>();
+        hv.n_filters = (uint32_t)sh_fx.size();
+        hv.cursor = g.cursor;
+        hv.n_sets = sh_next_six;
+        return hv;
+    }
+    // commit, replica d: its cursor array covers every set index handed out
+    // (grown with its contents kept, after every batch that could still write
+    // the old array), and the cursors of the indices in `reset` go back to
+    // undefined with this commit's scatters
+    void share_cursor_prepare(DevState& d, Image& g, const std::vector<uint32_t>& reset) {
+        const uint32_t need = std::max<uint32_t>(sh_next_six, 1);
+        if (d.sh_cursor_n < need) {
+            d.drain_image(0);
+            d.drain_image(1);
+            d.rw_drain();
+            const uint32_t cap = (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(1024, (uint64_t)need * 2));
+            DevBuf nb;
+            nb.ensure((size_t)cap * 4, 1.0);
+            HIPCHK(hipMemsetAsync(nb.p, 0xFF, (size_t)cap * 4, d.ustream));
+            if (d.sh_cursor.p && d.sh_cursor_n)
+                HIPCHK(hipMemcpyAsync(nb.p, d.sh_cursor.p, (size_t)d.sh_cursor_n * 4, hipMemcpyDeviceToDevice, d.ustream));
+            HIPCHK(hipStreamSynchronize(d.ustream));
+            d.sh_cursor.release();
+            d.sh_cursor = nb;
+            d.sh_cursor_n = cap;
+        }
+        g.cursor = d.sh_cursor.as<uint32_t>();
+        if (reset.empty()) return;
+        const size_t n = reset.size();
+        const uint64_t off = (d.stage_host.size() + 15) & ~uint64_t(15);
+        d.stage_host.resize(off + n * 8);
+        uint32_t* ix = reinterpret_cast<uint32_t*>(d.stage_host.data() + off);
+        for (size_t k = 0; k < n; ++k) {
+            ix[k] = reset[k];
+            ix[n + k] = 0xFFFFFFFFu;
+        }
+        d.stage_ops.push_back(DevState::ScatterOp{d.sh_cursor.p, off, n, 1u});
+    }
+
     // ---- to_rank labels (order maintenance) ----
     static OrdKey ord_key(RouteRec* r) {
         uint8_t b[32] = {0};
@@ -2139,11 +2547,13 @@ struct tm_engine {
     static const RouteView& route_view(const DevState& d) { return d.img[d.bimg].rv; }
     static const AggreView& aggre_view(const DevState& d) { return d.img[d.bimg].av; }
     static const SubView& sub_view(const DevState& d) { return d.img[d.bimg].sv; }
+    static const ShareView& share_view(const DevState& d) { return d.img[d.bimg].hv; }
     void capture_views(Image& g) const {
         g.iv = make_view(g);
         g.rv = make_route_view(g);
         g.av = make_aggre_view(g);
         g.sv = make_sub_view(g);
+        g.hv = make_share_view(g);
     }
     // the views of image g, from the host tables it was just written from
     ImageView make_view(const Image& g) const {
@@ -2240,6 +2650,7 @@ struct tm_engine {
         if (dev_dirty || devs.empty() || !devs[0]->img[devs[0]->cur].written) maybe_relayout();
         if (targets_dirty && !devs.empty()) rank_targets();
         if (devs.empty()) {
+            (void)release_share_indices();
             ++epoch;
             dev_dirty = false;
             release_quarantine();
@@ -2258,6 +2669,9 @@ struct tm_engine {
             }
             return;
         }
+        // set indices whose quarantine is over: their cursors go back to
+        // undefined on every replica before a new set can take them
+        const std::vector<uint32_t> six_reset = release_share_indices();
         for (auto& dp : devs) {
             DevState& d = *dp;
             Guard gd(d.device);
@@ -2279,6 +2693,12 @@ struct tm_engine {
             upload_table(d, g, g.d_sarena, sx_arena, t_sarena.cur, t_sarena.prev);
             upload_table(d, g, g.d_spool, sx_pool, t_spool.cur, t_spool.prev);
             upload_table(d, g, g.d_fs_meta, fs_meta, t_fs_meta.cur, t_fs_meta.prev);
+            upload_table(d, g, g.d_hsets, sh_sets.slots, sh_sets.t.cur, sh_sets.t.prev);
+            upload_table(d, g, g.d_htx, sh_tx.slots, sh_tx.t.cur, sh_tx.t.prev);
+            upload_table(d, g, g.d_harena, sh_arena, t_sh_arena.cur, t_sh_arena.prev);
+            upload_table(d, g, g.d_hpool, sh_pool, t_sh_pool.cur, t_sh_pool.prev);
+            upload_table(d, g, g.d_hfx, sh_fx, t_sh_fx.cur, t_sh_fx.prev);
+            share_cursor_prepare(d, g, six_reset);
             if (shape_keys) upload_table(d, g, g.d_fshape, fshape, t_fshape.cur, t_fshape.prev);
             flush_stage(d);
             // append-only arrays: upload the new tail (or all after a realloc)
@@ -2340,6 +2760,11 @@ struct tm_engine {
         t_sarena.rotate(sx_arena.size());
         t_spool.rotate(sx_pool.size());
         t_fs_meta.rotate(fs_meta.size());
+        sh_sets.t.rotate(sh_sets.slots.size());
+        sh_tx.t.rotate(sh_tx.slots.size());
+        t_sh_arena.rotate(sh_arena.size());
+        t_sh_pool.rotate(sh_pool.size());
+        t_sh_fx.rotate(sh_fx.size());
         dev_dirty = false;
         ++epoch;
         release_quarantine();   // also for engines that only take forced ids (never reach new_filter's release)
@@ -2760,11 +3185,59 @@ struct tm_engine {
         HIPCHK(launch_dispatch_emit(sub_view(d), d.w_xpre.as<uint64_t>(), slots, d.w_xpseg.as<uint32_t>(), to, sub_to,
                                     sub_id, cap, pairs_bound, st));
     }
-    // publish/1's route(aggre(match_routes(T))) with the local dispatch, device buffers
+    // emqx_shared_sub:dispatch/3's pick over the deliveries CSR of a batch
+    // (share.hip): pick[slot] for slot < slots.  TM_SHARE_KEYED is one pass;
+    // round robin reads the number of slots to rank back (one 8 B copy) to
+    // size the sort, which covers the bits of the set indices handed out.
+    void share_pick(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, const uint32_t* acount,
+                    const uint64_t* aoff, const uint32_t* to, const uint32_t* tg, uint64_t slots, uint32_t strategy,
+                    const uint32_t* pub_key, uint32_t* pick, hipStream_t st) {
+        if (slots == 0) return;
+        if (slots >= 0xFFFFFFFEull) throw RangeError("publish: more than 2^32 - 2 delivery slots in one batch");
+        const ShareView& hv = share_view(d);
+        const uint32_t local = sub_view(d).local_target;
+        if (strategy == TM_SHARE_KEYED) {
+            HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, aoff, to, tg, slots, pub_key, pick, nullptr,
+                                       nullptr, nullptr, nullptr, st));
+            return;
+        }
+        for (DevBuf* b : {&d.w_hcnt, &d.w_hseg, &d.w_hset, &d.w_hflag}) b->ensure((size_t)slots * 4 + 4);
+        d.w_hpre.ensure((size_t)(slots + 1) * 8);
+        d.w_hscan.ensure(scan_tmp_elems((uint32_t)slots) * 8 + 8);
+        uint64_t* P = d.w_hpre.as<uint64_t>();
+        HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, aoff, to, tg, slots, nullptr, pick,
+                                   d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(), d.w_hset.as<uint32_t>(),
+                                   d.w_hflag.as<uint32_t>(), st));
+        HIPCHK(launch_scan0(d.w_hflag.as<uint32_t>(), (uint32_t)slots, P, P + slots, d.w_hscan.as<uint64_t>(), st));
+        uint64_t m64 = 0;
+        HIPCHK(hipMemcpyAsync(&m64, P + slots, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (m64 == 0) return;
+        const uint32_t m = (uint32_t)m64;
+        uint32_t bits = 0;
+        while (bits < 32 && ((uint64_t)1 << bits) < hv.n_sets) ++bits;
+        const uint32_t passes = (bits + 7) / 8, pc = presort_counts(m);
+        d.w_hpairs.ensure((size_t)m * 16);
+        d.w_hnew.ensure((size_t)m * 4);
+        d.w_hcounts.ensure((size_t)pc * 4);
+        d.w_hoff.ensure((size_t)(pc + 1) * 8);
+        d.w_hsscan.ensure(scan_tmp_elems(pc) * 8 + 8);
+        uint32_t* k0 = d.w_hpairs.as<uint32_t>();
+        uint32_t *v0 = k0 + m, *k1 = v0 + m, *v1 = k1 + m;
+        HIPCHK(launch_share_compact(d.w_hflag.as<uint32_t>(), P, d.w_hset.as<uint32_t>(), slots, k0, v0, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, m, passes, d.w_hcounts.as<uint32_t>(), d.w_hoff.as<uint64_t>(),
+                                 d.w_hsscan.as<uint64_t>(), st));
+        const bool odd = passes & 1u;
+        HIPCHK(launch_share_rr(hv, odd ? k1 : k0, odd ? v1 : v0, m, d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(),
+                               pick, d.w_hnew.as<uint32_t>(), st));
+    }
+    // publish/1's route(aggre(match_routes(T))) with the local dispatch, device buffers;
+    // strategy != 0 (tm_match_publish_batch_device): also the $share picks of the slots kept
     void run_dispatch(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, uint64_t nbytes,
                       uint32_t* counts, uint64_t* out_off, uint32_t* to, uint32_t* target, uint32_t* ndisp, uint64_t cap,
                       uint64_t* total, uint32_t* sub_count, uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id,
-                      uint64_t sub_cap, uint64_t* sub_total, hipStream_t st) {
+                      uint64_t sub_cap, uint64_t* sub_total, hipStream_t st, uint32_t strategy = 0,
+                      const uint32_t* pub_key = nullptr, uint32_t* pick = nullptr) {
         uint64_t rcap = 0, rtotal = 0;
         deliveries_routes(d, bytes, off, n, nbytes, out_off, total, st, rcap, &rtotal);
         aggre_out(d, n, out_off, rcap, counts, to, target, cap, st);
@@ -2772,7 +3245,8 @@ struct tm_engine {
         dispatch_count(d, bytes, off, n, counts, out_off, to, target, slots, ndisp, sub_count, sub_off, st);
         dispatch_emit(d, slots, to, sub_to, sub_id, sub_cap, sub_cap, st);
         HIPCHK(hipMemcpyAsync(sub_total, d.w_xpre.as<uint64_t>() + slots, 8, hipMemcpyDeviceToDevice, st));
-        d.note_use(st);   // the dispatch kernels read the pinned subscriber image after the walk's use
+        if (strategy) share_pick(d, bytes, off, n, counts, out_off, to, target, slots, strategy, pub_key, pick, st);
+        d.note_use(st);   // the dispatch and share kernels read the pinned images after the walk's use
         d.rw_release(st);
     }
 
@@ -4021,16 +4495,22 @@ int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const u
     }, [&] { e->finish_batch(n); });
 }
 
-int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
-                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
-                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
-                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
-                            uint64_t* sub_needed) {
+// tm_match_dispatch_batch (strategy 0: no pick pass, out_pick unused) and
+// tm_match_publish_batch share every step up to the picks
+extern "C++" {
+namespace {
+int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                           uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                           uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                           uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                           uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick) {
     if (!topic_off || !out_off || !sub_off || (n && (!out_count || !sub_count)) ||
-        (out_cap && (!out_to || !out_target || !out_ndisp)) || (sub_cap && (!sub_to || !sub_id)))
+        (out_cap && (!out_to || !out_target || !out_ndisp || (strategy && !out_pick))) || (sub_cap && (!sub_to || !sub_id)))
         return TM_EINVAL;
+    if (strategy && strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
+    if (strategy == TM_SHARE_KEYED && n && !pub_key) return TM_EINVAL;
     if (!e) return TM_EINVAL;
-    if (e->devs.empty()) return no_device(e, "dispatch");
+    if (e->devs.empty()) return no_device(e, strategy ? "publish" : "dispatch");
     if (int rc = local_node_unset(e)) return rc;
     DevState& d = *e->devs[0];
     return batch_call(e, {&d}, [&]() -> int {
@@ -4075,6 +4555,21 @@ int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint
         d.w_xsub.ensure(splane * 8);
         uint32_t* sp = d.w_xsub.as<uint32_t>();
         e->dispatch_emit(d, rtotal, to, sp, sp + splane, pairs, pairs, s);
+        // the picks only when everything fits: a call that returns TM_ENOSPC
+        // has advanced no cursor, so its retry picks what a first call would
+        const bool fits = rtotal <= out_cap && pairs <= sub_cap;
+        if (strategy && fits && rtotal) {
+            d.w_hpick.ensure(rtotal * 4);
+            const uint32_t* key = nullptr;
+            if (strategy == TM_SHARE_KEYED) {
+                d.w_hkey.ensure((size_t)n * 4);
+                HIPCHK(hipMemcpyAsync(d.w_hkey.p, pub_key, (size_t)n * 4, hipMemcpyHostToDevice, s));
+                key = d.w_hkey.as<uint32_t>();
+            }
+            e->share_pick(d, b, o, n, d.w_counts.as<uint32_t>(), d.w_outoff.as<uint64_t>(), to, to + plane, rtotal,
+                          strategy, key, d.w_hpick.as<uint32_t>(), s);
+        }
+        if (strategy) d.note_use(s);
         d.rw_release(s);
         HIPCHK(hipMemcpyAsync(out_count, d.w_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(out_off, d.w_outoff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -4085,6 +4580,7 @@ int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint
             HIPCHK(hipMemcpyAsync(out_to, to, c * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(out_target, to + plane, c * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(out_ndisp, to + 2 * plane, c * 4, hipMemcpyDeviceToHost, s));
+            if (strategy && fits) HIPCHK(hipMemcpyAsync(out_pick, d.w_hpick.p, c * 4, hipMemcpyDeviceToHost, s));
         }
         if (pc) {
             HIPCHK(hipMemcpyAsync(sub_to, sp, pc * 4, hipMemcpyDeviceToHost, s));
@@ -4093,8 +4589,19 @@ int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint
         HIPCHK(hipStreamSynchronize(s));
         if (out_needed) *out_needed = rtotal;
         if (sub_needed) *sub_needed = pairs;
-        return rtotal > out_cap || pairs > sub_cap ? TM_ENOSPC : TM_OK;
+        return fits ? TM_OK : TM_ENOSPC;
     }, [&] { e->finish_batch(n); });
+}
+}  // namespace
+}  // extern "C++"
+
+int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                            uint64_t* sub_needed) {
+    return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
+                         out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, 0, nullptr, nullptr);
 }
 
 int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
@@ -4145,6 +4652,131 @@ int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_
         if (needed) *needed = pairs;
         return pairs > cap ? TM_ENOSPC : TM_OK;
     }, [&] {});
+}
+
+// ---- shared subscriptions (emqx_shared_sub) ----------------------------------
+int tm_share_add(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                 uint32_t member) {
+    if ((!group && glen) || (!topic && tlen) || member == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        e->share_add(group, glen, topic, tlen, member);
+        return TM_OK;
+    });
+}
+
+int tm_share_del(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                 uint32_t member, uint32_t* remaining) {
+    if ((!group && glen) || (!topic && tlen) || member == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        const uint32_t left = e->share_del(group, glen, topic, tlen, member);
+        if (remaining) *remaining = left;
+        return TM_OK;
+    });
+}
+
+extern "C++" {
+namespace {
+template <class F>
+int share_batch(tm_engine* e, const uint8_t* groups, const uint64_t* group_off, const uint8_t* topics,
+                const uint64_t* topic_off, const uint32_t* members, uint32_t n, F&& one) {
+    if (n && (!group_off || !topic_off || !members)) return TM_EINVAL;
+    return chunked(e, n, [&](uint32_t i) {
+        if (topic_off[i + 1] < topic_off[i] || topic_off[i + 1] - topic_off[i] > 0xFFFFFFFFull ||
+            group_off[i + 1] < group_off[i] || group_off[i + 1] - group_off[i] > 0xFFFFFFFFull)
+            throw ArgError("bad offsets");
+        if (members[i] == 0xFFFFFFFFu) throw ArgError("member id 0xFFFFFFFF is reserved");
+        static const uint8_t none = 0;
+        one(groups ? groups + group_off[i] : &none, (uint32_t)(group_off[i + 1] - group_off[i]),
+            topics ? topics + topic_off[i] : &none, (uint32_t)(topic_off[i + 1] - topic_off[i]), members[i]);
+    });
+}
+}  // namespace
+}  // extern "C++"
+
+int tm_share_add_batch(tm_engine* e, const uint8_t* groups, const uint64_t* group_off, const uint8_t* topics,
+                       const uint64_t* topic_off, const uint32_t* members, uint32_t n) {
+    return share_batch(e, groups, group_off, topics, topic_off, members, n,
+                       [&](const uint8_t* g, uint32_t glen, const uint8_t* t, uint32_t tlen, uint32_t m) {
+                           e->share_add(g, glen, t, tlen, m);
+                       });
+}
+
+int tm_share_del_batch(tm_engine* e, const uint8_t* groups, const uint64_t* group_off, const uint8_t* topics,
+                       const uint64_t* topic_off, const uint32_t* members, uint32_t n) {
+    return share_batch(e, groups, group_off, topics, topic_off, members, n,
+                       [&](const uint8_t* g, uint32_t glen, const uint8_t* t, uint32_t tlen, uint32_t m) {
+                           (void)e->share_del(g, glen, t, tlen, m);
+                       });
+}
+
+int tm_share_member_down(tm_engine* e, uint32_t member, uint32_t* removed) {
+    if (member == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        const uint32_t k = e->share_member_down(member);
+        if (removed) *removed = k;
+        return TM_OK;
+    });
+}
+
+int tm_share_members(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                     uint32_t* out, uint32_t cap, uint32_t* out_n) {
+    if ((!group && glen) || (!topic && tlen) || !out_n || (cap && !out)) return TM_EINVAL;
+    return guarded(e, [&] {
+        const tm_engine::ShareSet* s = e->share_find(group, glen, topic, tlen);
+        const uint32_t k = s ? (uint32_t)s->members.size() : 0u;
+        *out_n = k;
+        for (uint32_t i = 0; i < k && i < cap; ++i) out[i] = s->members[i];
+        return k > cap ? TM_ENOSPC : TM_OK;
+    });
+}
+
+uint64_t tm_share_count(tm_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::recursive_mutex> lk(e->mu);
+    return e->sh_total;
+}
+
+int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                  uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                  uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                  uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                  uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
+                                  const uint32_t* d_pub_key, uint32_t* d_pick, void* hip_stream) {
+    if (!d_off || !d_out_off || !d_total || !d_sub_off || !d_sub_total || (n && (!d_count || !d_sub_count)) ||
+        (out_cap && (!d_to || !d_target || !d_ndisp || !d_pick)) || (sub_cap && (!d_sub_to || !d_sub_id)))
+        return TM_EINVAL;
+    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
+    if (strategy == TM_SHARE_KEYED && n && !d_pub_key) return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "publish");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->replica_for(d_off);
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (n == 0) {
+            HIPCHK(hipMemsetAsync(d_out_off, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_total, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_sub_off, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_sub_total, 0, 8, st));
+            return TM_OK;
+        }
+        e->run_dispatch(d, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
+                        d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, st, strategy,
+                        d_pub_key, d_pick);
+        return TM_OK;
+    }, [&] { e->finish_batch(n); });
+}
+
+int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                           uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                           uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                           uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                           uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick) {
+    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
+    return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
+                         out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, strategy, pub_key,
+                         out_pick);
 }
 
 int tm_match_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
@@ -4496,6 +5128,106 @@ extern "C" int tm_debug_check_subs(tm_engine* e) {
         for (size_t f = 0; f < e->fs_meta.size(); ++f)
             if ((e->fs_meta[f].y || e->fs_meta[f].z) && (!e->fs_rec[f] || e->fs_rec[f]->fid != f))
                 return fail("stale fs_meta");
+        return TM_OK;
+    });
+}
+
+// diagnostics (not part of include/topicmatch.h): the in-place share image
+// against the member table it mirrors -- every topic found by the kernel's
+// probe with its xid and bytes, every set found in the set table by exact
+// compare with its Count, segment and set index, the segment equal to the
+// member list, a wildcard topic linked to its trie filter (fx) and to no
+// other, set indices distinct and outside the free list and
+// the quarantine, the member index equal to the sets -- TM_OK or TM_EINVAL
+// with the first inconsistency in tm_last_error
+extern "C" int tm_debug_check_shares(tm_engine* e) {
+    return guarded(e, [&]() -> int {
+        auto fail = [&](const std::string& what) -> int { throw ArgError("share image: " + what); };
+        size_t total = 0, n_sets = 0, live_cap = 0, live_words = 0, linked = 0;
+        std::unordered_set<uint32_t> six_seen, xid_seen;
+        for (auto& kv : e->sh_topics) {
+            const tm_engine::ShareTopic& tp = kv.second;
+            const uint8_t* t = reinterpret_cast<const uint8_t*>(kv.first.data());
+            const uint32_t len = (uint32_t)kv.first.size();
+            if (tp.key != &kv.first || tp.sets.empty()) return fail("record of " + kv.first);
+            if (tp.wild != tm_topic_wildcard(t, len)) return fail("wildcard flag of " + kv.first);
+            if (tp.fid != (tp.wild ? e->filter_of(t, len) : FILTER_NONE)) return fail("filter link of " + kv.first);
+            if (tp.fid != FILTER_NONE) {
+                ++linked;
+                auto fi = e->sh_fid_topic.find(tp.fid);
+                if (fi == e->sh_fid_topic.end() || fi->second != &tp) return fail("filter index of " + kv.first);
+                if (tp.fid >= e->sh_fx.size() || e->sh_fx[tp.fid] != tp.xid) return fail("fx of " + kv.first);
+            }
+            {
+                live_words += tp.words;
+                if (!xid_seen.insert(tp.xid).second || tp.xid >= e->sh_next_xid) return fail("xid of " + kv.first);
+                // the probe the kernel runs (share.hip share_topic_lookup)
+                const uint64_t h = word_hash(t, len);
+                const size_t mask = e->sh_tx.slots.size() - 1;
+                size_t s = h & mask;
+                while (e->sh_tx.slots[s].hash && !(e->sh_tx.slots[s].hash == h && e->sh_tx.slots[s].len == len &&
+                                                    std::memcmp(&e->sh_arena[e->sh_tx.slots[s].arena / 8], t, len) == 0))
+                    s = (s + 1) & mask;
+                const ShareTopicSlot& x = e->sh_tx.slots[s];
+                if (!x.hash || s != tp.slot || e->sh_tx.rec[s] != &tp) return fail("probe of " + kv.first);
+                if (x.xid != tp.xid || x.arena != tp.arena * 8) return fail("slot of " + kv.first);
+                if (len % 8 && (e->sh_arena[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) return fail("arena padding");
+            }
+            for (auto& sk : tp.sets) {
+                const tm_engine::ShareSet& st = *sk.second;
+                if (st.topic != &tp || st.tg != sk.first || st.members.empty()) return fail("set of " + kv.first);
+                if (st.tg >= e->target_names.size() || (uint8_t)e->target_names[st.tg][0] != TM_TARGET_GROUP)
+                    return fail("group target of " + kv.first);
+                total += st.members.size();
+                live_cap += st.cap;
+                if (!six_seen.insert(st.six).second || st.six >= e->sh_next_six) return fail("set index of " + kv.first);
+                if (st.cap < st.members.size() || (uint64_t)st.off + st.cap > e->sh_pool.size() ||
+                    !std::equal(st.members.begin(), st.members.end(), e->sh_pool.begin() + st.off))
+                    return fail("segment of " + kv.first);
+                std::unordered_set<uint32_t> uniq(st.members.begin(), st.members.end());
+                if (uniq.size() != st.members.size()) return fail("duplicate member in " + kv.first);
+                for (uint32_t mbr : st.members) {
+                    auto mi = e->sh_member_sets.find(mbr);
+                    if (mi == e->sh_member_sets.end() ||
+                        std::count(mi->second.begin(), mi->second.end(), &st) != 1)
+                        return fail("member index of " + kv.first);
+                }
+                ++n_sets;
+                const size_t mask = e->sh_sets.slots.size() - 1;
+                size_t s = share_set_hash(st.tg, tp.xid) & mask;   // share.hip tm_share_lookup's probe
+                while (e->sh_sets.slots[s].count && !(e->sh_sets.slots[s].tg == st.tg && e->sh_sets.slots[s].xid == tp.xid))
+                    s = (s + 1) & mask;
+                const ShareSetSlot& x = e->sh_sets.slots[s];
+                if (!x.count || s != st.slot || e->sh_sets.rec[s] != &st) return fail("set probe of " + kv.first);
+                if (x.count != st.members.size() || x.seg != st.off || x.set != st.six) return fail("set slot of " + kv.first);
+            }
+        }
+        if (total != e->sh_total) return fail("member total");
+        size_t indexed = 0;
+        for (auto& mi : e->sh_member_sets) {
+            if (mi.second.empty()) return fail("empty member index entry");
+            indexed += mi.second.size();
+        }
+        if (indexed != total) return fail("member index size");
+        if (n_sets != e->sh_sets.used || e->sh_topics.size() != e->sh_tx.used) return fail("table counts");
+        if (linked != e->sh_fid_topic.size()) return fail("filter index size");
+        for (size_t f = 0; f < e->sh_fx.size(); ++f)
+            if (e->sh_fx[f] != tm_engine::SLOT_NONE && !e->sh_fid_topic.count((uint32_t)f)) return fail("stale fx");
+        size_t used = 0;
+        for (size_t s = 0; s < e->sh_sets.slots.size(); ++s)
+            if (e->sh_sets.slots[s].count) ++used;
+        if (used != e->sh_sets.used) return fail("set slots in use");
+        used = 0;
+        for (size_t s = 0; s < e->sh_tx.slots.size(); ++s)
+            if (e->sh_tx.slots[s].hash) ++used;
+        if (used != e->sh_tx.used) return fail("topic slots in use");
+        for (uint32_t i : e->sh_free_six)
+            if (!six_seen.insert(i).second) return fail("free set index in use");
+        for (auto& q : e->sh_six_quarantine)
+            if (!six_seen.insert(q.second).second) return fail("quarantined set index in use");
+        if (six_seen.size() != e->sh_next_six) return fail("set index accounting");
+        if (live_cap + e->sh_pool_garbage != e->sh_pool.size()) return fail("pool accounting");
+        if (live_words + e->sh_arena_garbage != e->sh_arena.size()) return fail("arena accounting");
         return TM_OK;
     });
 }

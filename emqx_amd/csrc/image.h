@@ -200,6 +200,53 @@ struct SubView {
     const uint32_t* pool;           // the plain pool
 };
 
+// ---- share image (emqx_shared_subscription bag, src/emqx_shared_sub.erl:49-62) ----
+// emqx_shared_sub:dispatch/3 picks one member of subscribers(Group, To)
+// (share.hip).  A member set is keyed by the pair (group target id, To key),
+// compared exactly.  The To key is a dense id (xid) of the set's topic: found
+// by a trie filter's id through fx (which follows the id's lifetime as
+// fs_meta does), and for To = the publish topic itself by its bytes through
+// an exact-topic table of this image (laid out, probed and byte-verified like
+// the subscriber image's; it holds every topic with a set, as that one
+// does).  Each set owns a segment of one member pool, in list (insertion)
+// order, and a set index: the slot of its round-robin cursor, which lives
+// outside the image epochs (one array per replica).
+constexpr uint32_t TM_NO_MEMBER_ID = 0xFFFFFFFFu;   // pick of a delivery without a member
+
+struct alignas(32) ShareTopicSlot {
+    uint64_t hash;         // word_hash of the topic bytes (0 = empty slot)
+    uint32_t len;          // topic length
+    uint32_t xid;          // the topic's To key
+    uint64_t arena;        // topic bytes in the arena
+    uint64_t pad;
+    bool empty() const { return hash == 0; }
+    uint64_t home() const { return hash; }
+};
+
+struct alignas(32) ShareSetSlot {
+    uint32_t tg;           // group target id
+    uint32_t xid;          // To key: the dense id of the set's topic
+    uint32_t count;        // members (0 = empty slot: a set in the table has at least one)
+    uint32_t seg;          // first member in the pool
+    uint32_t set;          // set index (cursor slot)
+    uint32_t pad0, pad1, pad2;
+    bool empty() const { return count == 0; }
+    inline uint64_t home() const;
+};
+
+struct ShareView {
+    const ShareSetSlot*   sets;      // power-of-two table, count 0 = empty
+    uint64_t              set_mask;
+    const ShareTopicSlot* tx_slots;  // power-of-two table, hash 0 = empty
+    uint64_t              tx_mask;
+    const uint8_t*        tx_arena;
+    const uint32_t*       pool;      // the member pool
+    const uint32_t*       fx;        // n_filters: filter id -> xid of that wildcard topic (0xFFFFFFFF: none)
+    uint32_t              n_filters;
+    uint32_t*             cursor;    // set index -> stored Rem, 0xFFFFFFFF = undefined (per replica)
+    uint32_t              n_sets;    // set indices handed out so far (cursor entries in use)
+};
+
 // ---- hashing (identical on host and device) ---------------------------------
 #if defined(__HIPCC__)
 #define TM_HD __host__ __device__ __forceinline__
@@ -261,6 +308,12 @@ TM_HD uint64_t fmix64(uint64_t k) {
     k ^= k >> 33;
     return k;
 }
+
+// placement of a share set's key (identity is the exact compare of both)
+TM_HD uint64_t share_set_hash(uint32_t tg, uint32_t xid) {
+    return fmix64(((uint64_t)tg << 32) | xid);
+}
+inline uint64_t ShareSetSlot::home() const { return share_set_hash(tg, xid); }
 
 TM_HD uint64_t edge_hash(uint32_t parent, uint32_t word) {
     return fmix64(((uint64_t)parent << 32) | word);

@@ -83,6 +83,13 @@ struct QueueBufs {
 uint32_t presort_counts(uint32_t n);
 hipError_t launch_presort(const uint32_t* twords, const uint32_t* meta, uint32_t n, const QueueBufs& qb,
                           hipStream_t st, bool gather = true);
+// the same stable LSD radix passes over plain arrays: n (key, value) u32 pairs
+// by the keys' low 8 * passes bits (passes 0..4).  Input in (k0, v0); the
+// result is in (k0, v0) after an even number of passes, in (k1, v1) after an
+// odd one.  counts: presort_counts(n) u32, off: presort_counts(n) + 1 u64,
+// tmp: scan_tmp_elems(presort_counts(n)).
+hipError_t launch_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
+                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st);
 // true when launch_queue's walk of a presorted batch writes stage row p for
 // queue position p (the copy-out then moves row p to topic perm[p]): without
 // chunk rows, or keyed / stats walks.  With chunk rows the walk reads each
@@ -164,6 +171,27 @@ hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint
 hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                 const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
                                 uint64_t pairs_bound, hipStream_t st);
+
+// emqx_shared_sub:dispatch/3 member pick (share.hip) over the same deliveries
+// CSR and slot geometry as launch_dispatch_count.
+//   launch_share_lookup   per slot pick[slot] (TM_NO_MEMBER_ID for a hole, a non-group
+//                         slot and an empty set).  pub_key != null (n keys, TM_SHARE_KEYED):
+//                         every pick is final, cnt / seg / set / flag unused.  pub_key ==
+//                         null (round robin): Count = 1 picked, cnt / seg / set (slots
+//                         entries each) written, flag[slot] = Count >= 2
+//   launch_scan0(flag, slots, P, P + slots, ...)   P[slots] = m, the pairs to rank
+//   launch_share_compact  keys / vals[P[slot]] = (set index, slot) of the flagged slots
+//   launch_sort_pairs     stable by set index (bits of ShareView::n_sets - 1)
+//   launch_share_rr       the sorted pairs: pick of each, then the runs' new cursors
+//                         (newcur: m u32 of workspace)
+hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const uint8_t* bytes, const uint64_t* off,
+                               uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
+                               const uint32_t* tg, uint64_t slots, const uint32_t* pub_key, uint32_t* pick,
+                               uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st);
+hipError_t launch_share_compact(const uint32_t* flag, const uint64_t* P, const uint32_t* set, uint64_t slots,
+                                uint32_t* keys, uint32_t* vals, hipStream_t st);
+hipError_t launch_share_rr(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
+                           const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur, hipStream_t st);
 
 // Sharded mode (shard.hip): merge per-topic match lists of S filter shards
 // for m topics.  counts [S][m]; source s's items start at src_base[s] of

@@ -262,4 +262,31 @@ hipError_t launch_presort(const uint32_t* twords, const uint32_t* meta, uint32_t
     return hipGetLastError();
 }
 
+// the same passes over plain arrays (share.hip sorts (set index, slot) pairs):
+// the keys' low 8 * passes bits, input in (k0, v0), ping-pong with (k1, v1)
+hipError_t launch_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
+                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st) {
+    if (n == 0 || passes == 0) return hipSuccess;
+    if (passes > 4) return hipErrorInvalidValue;
+    const uint32_t tiles = (n + PS_TILE - 1) / PS_TILE, nc = 256u * tiles;
+    uint32_t *ka = k0, *kb = k1, *va = v0, *vb = v1;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const uint32_t shift = 8 * pass;
+        hipLaunchKernelGGL(tm_presort_count, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, n, shift, counts);
+        hipError_t err = launch_scan(counts, nc, off, off + nc, tmp, st);
+        if (err != hipSuccess) return err;
+        if (TM_PS_LOCAL)
+            hipLaunchKernelGGL(tm_presort_scatter_ls, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb, vb);
+        else
+            hipLaunchKernelGGL(tm_presort_scatter, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb, vb);
+        uint32_t* t = ka;
+        ka = kb;
+        kb = t;
+        t = va;
+        va = vb;
+        vb = t;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace tmx

@@ -10,6 +10,8 @@ expansion, aggre and the subscriber fan-out, dispatch.hip).
                                        then del_route when ets:member(?SUBSCRIBER, Topic) is false
     subscribers(Topic)                 :245-247 -> [Sub | {share, Group, Sub}] in bag order
     publish_many(Topics)               publish/1 :148-157 per topic: route(aggre(match_routes(T)))
+    publish_shared_many(Topics, ...)   the same with route/2's $share clause :187-189: the member
+                                       emqx_shared_sub:dispatch/3 picks for every {To, Group} delivery
     dispatch_many(Tos)                 dispatch/2 :218-238 as a remote node's forward/3 calls it
 
 A subscriber is a u32 chosen by the caller (the NIF keeps id <-> {SubPid,
@@ -18,6 +20,7 @@ SubId}); groups are byte strings.  The counterpart of emqx_router.py.
 from collections import namedtuple
 
 from .emqx_router import Router, _key
+from .emqx_shared_sub import STRATEGIES, SharedSub
 from .engine import Engine, pack
 
 # one delivery of publish/1: target = (kind, key) as Router.match_deliveries_many
@@ -27,10 +30,22 @@ Delivery = namedtuple("Delivery", "to target count")
 Published = namedtuple("Published", "deliveries pairs")
 
 
+class SharedPublished(Published):
+    """a Published (the same two fields, equal to the plain one) with .picks:
+    [(To, Group, member | None)] of the $share deliveries in delivery order,
+    None = do_pick/5's `false`"""
+
+    def __new__(cls, deliveries, pairs, picks):
+        self = super().__new__(cls, deliveries, pairs)
+        self.picks = picks
+        return self
+
+
 class Broker:
     def __init__(self, engine: Engine, router: Router):
         self.engine = engine
         self.router = router
+        self.shared = SharedSub(engine)
         engine.set_local_node(_key(router.node))
 
     def _dest(self, group):
@@ -40,12 +55,14 @@ class Broker:
     # handle_cast({From, #subscribe{}}) — :332-345
     def subscribe(self, topic: bytes, sub: int, group=None):
         self.engine.sub_add(topic, sub, None if group is None else _key(group))
+        self.shared.subscribe(group, topic, sub)          # :394
         self.router.add_route(topic, self._dest(group))
         return "ok"
 
     # handle_cast({From, #unsubscribe{}}) — :347-358
     def unsubscribe(self, topic: bytes, sub: int, group=None):
         left = self.engine.sub_del(topic, sub, None if group is None else _key(group))
+        self.shared.unsubscribe(group, topic, sub)        # :353
         if left == 0:                      # ets:member(?SUBSCRIBER, Topic) -> false
             self.router.del_route(topic, self._dest(group))
         return "ok"
@@ -72,7 +89,20 @@ class Broker:
         deliveries in aggre's order, pairs = [(To, Sub)] in dispatch order"""
         topics = list(topics)
         buf, off = pack(topics)
-        counts, offs, to, tg, nd, scount, soff, sto, sid = self.engine.match_dispatch_batch(buf, off)
+        return self._published(topics, self.engine.match_dispatch_batch(buf, off), None)
+
+    def publish_shared_many(self, topics, strategy=None, keys=None):
+        """publish_many with the $share clause: Published.picks = [(To, Group,
+        member | None)] per $share delivery.  strategy: "round_robin", or
+        "hash" / "random" / "keyed" with keys = one u32 per topic
+        (erlang:phash2(ClientId), or a uniform draw); default: self.shared.strategy"""
+        topics = list(topics)
+        buf, off = pack(topics)
+        out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys)
+        return self._published(topics, out[:9], out[9])
+
+    def _published(self, topics, out, pick):
+        counts, offs, to, tg, nd, scount, soff, sto, sid = out
         names, tnames, res = {}, {}, []
 
         def name_of(s, topic):
@@ -84,15 +114,19 @@ class Broker:
 
         for t, topic in enumerate(topics):
             dels = []
+            picks = None if pick is None else []
             for k in range(int(offs[t]), int(offs[t]) + int(counts[t])):
                 g = int(tg[k])
                 if g not in tnames:
                     tnames[g] = self.engine.target_bytes(g)
                 c = int(nd[k])
                 dels.append(Delivery(name_of(int(to[k]), topic), tnames[g], None if c == Engine.NOT_LOCAL else c))
+                if pick is not None and tnames[g][0] == Engine.TARGET_GROUP:
+                    m = int(pick[k])
+                    picks.append((dels[-1].to, tnames[g][1], None if m == Engine.NO_MEMBER else m))
             a = int(soff[t])
             pairs = [(name_of(int(sto[k]), topic), int(sid[k])) for k in range(a, a + int(scount[t]))]
-            res.append(Published(dels, pairs))
+            res.append(Published(dels, pairs) if pick is None else SharedPublished(dels, pairs, picks))
         return res
 
     # dispatch/2 — :218-238

@@ -577,6 +577,124 @@ class Engine:
             self._check(rc, "tm_dispatch_batch")
             return nd[:n], soff, sid[: int(needed.value)]
 
+    # -- emqx_shared_sub: the $share member table and the pick (share.hip) ---------
+    NO_MEMBER = 0xFFFFFFFF            # pick: `false`, or not a $share delivery
+    SHARE_KEYED, SHARE_ROUND_ROBIN = 1, 2
+
+    def share_add(self, group: bytes, topic: bytes, member: int):
+        """subscribe/3: a record already in the bag leaves it as it was"""
+        return self._check(self.lib.tm_share_add(self.h, group, len(group), topic, len(topic), member),
+                           "tm_share_add")
+
+    def share_del(self, group: bytes, topic: bytes, member: int) -> int:
+        """unsubscribe/3; returns the members left in the (group, topic) set"""
+        left = ctypes.c_uint32()
+        self._check(self.lib.tm_share_del(self.h, group, len(group), topic, len(topic), member, ctypes.byref(left)),
+                    "tm_share_del")
+        return left.value
+
+    def _share_many(self, fn, what, gbuf, goff, tbuf, toff, members):
+        n = len(toff) - 1
+        gbuf = np.ascontiguousarray(gbuf, dtype=np.uint8)
+        goff = np.ascontiguousarray(goff, dtype=np.uint64)
+        tbuf = np.ascontiguousarray(tbuf, dtype=np.uint8)
+        toff = np.ascontiguousarray(toff, dtype=np.uint64)
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        return self._check(fn(self.h, _ptr(gbuf), _ptr(goff), _ptr(tbuf), _ptr(toff), _ptr(members), n), what)
+
+    def share_add_many(self, gbuf, goff, tbuf, toff, members):
+        """record i = (group i of (gbuf, goff), topic i of (tbuf, toff), members[i])"""
+        return self._share_many(self.lib.tm_share_add_batch, "tm_share_add_batch", gbuf, goff, tbuf, toff, members)
+
+    def share_del_many(self, gbuf, goff, tbuf, toff, members):
+        return self._share_many(self.lib.tm_share_del_batch, "tm_share_del_batch", gbuf, goff, tbuf, toff, members)
+
+    def share_member_down(self, member: int) -> int:
+        """cleanup_down/1; returns the records deleted"""
+        k = ctypes.c_uint32()
+        self._check(self.lib.tm_share_member_down(self.h, member, ctypes.byref(k)), "tm_share_member_down")
+        return k.value
+
+    def share_members(self, group: bytes, topic: bytes, cap=None):
+        """subscribers/2 in insertion order.  cap given: one call
+        (TopicMatchError TM_ENOSPC when the set is larger)"""
+        n = ctypes.c_uint32()
+        c = 16 if cap is None else cap
+        while True:
+            out = np.zeros(max(c, 1), dtype=np.uint32)
+            rc = self.lib.tm_share_members(self.h, group, len(group), topic, len(topic), _ptr(out), c, ctypes.byref(n))
+            if rc == L.TM_ENOSPC and cap is None:
+                c = n.value
+                continue
+            self._check(rc, "tm_share_members")
+            return [int(x) for x in out[: n.value]]
+
+    @property
+    def share_count(self):
+        return self.lib.tm_share_count(self.h)
+
+    def debug_check_shares(self):
+        """host-side consistency check of the in-place share image
+        (diagnostic, tm_debug_check_shares)"""
+        self.lib.tm_debug_check_shares.argtypes = [ctypes.c_void_p]
+        return self._check(self.lib.tm_debug_check_shares(self.h), "tm_debug_check_shares")
+
+    def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None):
+        """match_dispatch_batch's tuple plus pick u32 (one per delivery slot):
+        the member picked for a $share delivery, NO_MEMBER otherwise.
+        strategy SHARE_KEYED takes keys (u32[n]); SHARE_ROUND_ROBIN none.  A
+        short out_cap / sub_cap: as match_dispatch_batch (no cursor moves)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.uint32)
+            if len(keys) != n:
+                raise ValueError("keys: one u32 per topic")
+        counts = np.zeros(max(n, 1), dtype=np.uint32)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        scount = np.zeros(max(n, 1), dtype=np.uint32)
+        soff = np.zeros(n + 1, dtype=np.uint64)
+        cap = 1 << 16 if out_cap is None else out_cap
+        scap = 1 << 16 if sub_cap is None else sub_cap
+        while True:
+            to, tg, nd, pick = (np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(4))
+            sto, sid = (np.zeros(max(scap, 1), dtype=np.uint32) for _ in range(2))
+            needed, sneeded = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = self.lib.tm_match_publish_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs), _ptr(to),
+                                                 _ptr(tg), _ptr(nd), cap, ctypes.byref(needed), _ptr(scount),
+                                                 _ptr(soff), _ptr(sto), _ptr(sid), scap, ctypes.byref(sneeded),
+                                                 strategy, _ptr(keys), _ptr(pick))
+            if rc == L.TM_ENOSPC and (out_cap is None or needed.value <= cap) and \
+                    (sub_cap is None or sneeded.value <= scap):
+                cap = max(cap, int(needed.value))
+                scap = max(scap, int(sneeded.value))
+                continue
+            if rc == L.TM_ENOSPC:
+                e = L.TopicMatchError(rc, "tm_match_publish_batch: needs %d deliveries, %d pairs"
+                                      % (needed.value, sneeded.value))
+                e.needed, e.sub_needed = int(needed.value), int(sneeded.value)
+                raise e
+            self._check(rc, "tm_match_publish_batch")
+            k, sk = int(needed.value), int(sneeded.value)
+            return counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk], pick[:k]
+
+    def match_publish_batch_device(self, d_bytes, d_off, n, topic_bytes, d_counts, d_offs, d_to, d_target, d_ndisp,
+                                   out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap,
+                                   d_sub_total, strategy, d_keys, d_pick, stream=None):
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_match_publish_batch_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts),
+                                                    p(d_offs), p(d_to), p(d_target), p(d_ndisp), out_cap, p(d_total),
+                                                    p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,
+                                                    p(d_sub_total), strategy, p(d_keys), p(d_pick), st)
+        return self._check(rc, "tm_match_publish_batch_device")
+
     # walk variants (A/B knobs of tm_walk_queue): one global dequeue head, or
     # per-XCD heads over contiguous ranges of the batch
     WALKS = {"queue": 0, "queue_xcd": 1}

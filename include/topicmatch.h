@@ -623,6 +623,98 @@ int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, c
 int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
                       uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed);
 
+/* ---- shared-subscription dispatch: the $share member table and the pick -------
+ * (emqx_amd/csrc/share.hip)  The third clause of route/2
+ * (src/emqx_broker.erl:187-189) hands a {To, Group} delivery to
+ * emqx_shared_sub:dispatch/3, which picks ONE member of subscribers(Group, To)
+ * (src/emqx_shared_sub.erl:89-111, 228-252).  The engine keeps that table --
+ * emqx_shared_subscription, a mnesia bag of {group, topic, subpid} (:49,
+ * 57-62) -- and returns the picked member per $share delivery.
+ *
+ * A member is a caller-chosen u32 as a subscriber is; 0xFFFFFFFF is reserved
+ * (TM_EINVAL).  The group bytes are interned as a TM_TARGET_GROUP target, the
+ * one tm_dest_target gives a {Group, Node} dest: a node atom with the same
+ * bytes is another target, and a group may have members before it has a
+ * route.  The table is independent of the trie, the routes and the
+ * emqx_subscriber bag, and it is cluster-wide (aggre/1 drops the node of
+ * {Group, Node}).  Members of one (group, topic) come back in insertion order:
+ * ETS's order for the objects of one key, which the reference relies on
+ * without stating it (as the emqx_subscriber bag does).  Changes reach the
+ * device with the next tm_commit. */
+#define TM_NO_MEMBER         0xFFFFFFFFu   /* out_pick: `false`, or not a $share delivery  */
+#define TM_SHARE_KEYED       1u            /* pick = member (pub_key[topic] rem Count)      */
+#define TM_SHARE_ROUND_ROBIN 2u            /* pick = the set's cursor, advanced per publish */
+
+/* subscribe/3 — :77-79, a dirty_write into a bag: a record already present
+ * leaves the bag as it was (first position kept). */
+int tm_share_add(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                 uint32_t member);
+/* unsubscribe/3 — :83-84, dirty_delete_object: an absent record is a no-op.
+ * *remaining (may be NULL) = members left in the (group, topic) set. */
+int tm_share_del(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                 uint32_t member, uint32_t* remaining);
+/* Bulk forms, laid out as tm_sub_add_batch and applied in order: record i =
+ * (group [group_off[i], group_off[i+1]), topic [topic_off[i], topic_off[i+1]),
+ * members[i]). */
+int tm_share_add_batch(tm_engine* e, const uint8_t* groups, const uint64_t* group_off, const uint8_t* topics,
+                       const uint64_t* topic_off, const uint32_t* members, uint32_t n);
+int tm_share_del_batch(tm_engine* e, const uint8_t* groups, const uint64_t* group_off, const uint8_t* topics,
+                       const uint64_t* topic_off, const uint32_t* members, uint32_t n);
+/* cleanup_down/1 — :316-321: every record of the member, whatever the group or
+ * topic (through a member -> records index, no table scan).  *removed (may be
+ * NULL) = records deleted. */
+int tm_share_member_down(tm_engine* e, uint32_t member, uint32_t* removed);
+/* subscribers/2 — :251-252, in insertion order.  *out_n = members (TM_ENOSPC
+ * when it exceeds cap, the first cap still written). */
+int tm_share_members(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                     uint32_t* out, uint32_t cap, uint32_t* out_n);
+/* records of the table (ets:info(emqx_shared_subscription, size), :324) */
+uint64_t tm_share_count(tm_engine* e);
+
+/* publish/1 up to the sends: everything tm_match_dispatch_batch returns,
+ * element for element (a $share slot's out_ndisp stays TM_NOT_LOCAL), and
+ * out_pick parallel to out_ndisp: for a {To, Group} delivery the member
+ * do_pick/5 picks with FailedSubs = [] (:228-249), TM_NO_MEMBER for `false`
+ * (no member) and for every slot that is not a $share delivery.
+ *
+ * TM_SHARE_KEYED: pub_key has n entries, one u32 per publish; the pick is
+ * member (pub_key[t] rem Count), 0-based, of the list.  With pub_key[t] =
+ * erlang:phash2(ClientId) this is the `hash` strategy exactly; with a fresh
+ * uniform draw per publish it is `random` (bias at most Count / 2^32; one key
+ * serves every group of the publish, each group's pick still uniform).
+ * Stateless and reentrant.
+ *
+ * TM_SHARE_ROUND_ROBIN (pub_key unused, may be NULL): one cursor per (Group,
+ * To) set, held per replica outside the image epochs.  The publishes of a
+ * replica are taken as if one publisher process sent them: batches in stream
+ * order, topic index ascending within a batch, so a batch of n publishes
+ * gives what n one-topic batches give.  A set of one member is picked without
+ * touching its cursor (:231); otherwise Rem = 0 on the first use and (N + 1)
+ * rem Count after (:243-249), with the Count of the image the batch runs on
+ * (also when N >= Count after a shrink).  Two deviations: the reference keeps
+ * the cursor per publisher process (erlang:get), the engine per set -- equal
+ * for one publisher --; and a set that loses its last member forgets its
+ * cursor, which the reference never erases.
+ *
+ * Host buffers: TM_ENOSPC as tm_match_dispatch_batch; such a call writes no
+ * out_pick and advances no cursor, so its retry picks what a first call
+ * would have.  On the engine's first replica. */
+int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                           uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                           uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                           uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                           uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick);
+/* Same with device buffers (d_pub_key too) on hip_stream, by the conventions of
+ * tm_match_dispatch_batch_device: a delivery at or past out_cap is dropped,
+ * gets no pick and takes no cursor value.  Round robin waits once for the
+ * stream (an 8 B read-back sizes the sort). */
+int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
+                                  uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count, uint64_t* d_out_off,
+                                  uint32_t* d_out_to, uint32_t* d_out_target, uint32_t* d_out_ndisp, uint64_t out_cap,
+                                  uint64_t* d_total, uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to,
+                                  uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
+                                  const uint32_t* d_pub_key, uint32_t* d_out_pick, void* hip_stream);
+
 /* ---- publish micro-batcher (emqx_amd/csrc/batcher.cpp) -----
  * emqx_broker:publish/1 (src/emqx_broker.erl:148-157) matches one topic per
  * call in the publisher's process.  The NIF instead submits the topic here
