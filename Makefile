@@ -15,7 +15,8 @@ all: $(LIBOUT) emqx_amd/libtmwork.so oracle/liboracle.so tools/ubench/batcher_be
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/kernels.o: emqx_amd/csrc/kernels.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
+# every kernel file: one rule (device_bytes.h is the shared device header)
+$(BUILD)/%.o: emqx_amd/csrc/%.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h emqx_amd/csrc/device_bytes.h include/topicmatch.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/engine.o: emqx_amd/csrc/engine.cpp emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h include/topicmatch.h | $(BUILD)
@@ -28,38 +29,11 @@ variant:
 	$(MAKE) BUILD=build_$(TAG) LIBOUT=emqx_amd/variants/libtopicmatch_$(TAG).so TMDEFS="$(TMDEFS)" emqx_amd/variants/libtopicmatch_$(TAG).so
 .PHONY: variant
 
-$(BUILD)/shard.o: emqx_amd/csrc/shard.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/routes.o: emqx_amd/csrc/routes.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/presort.o: emqx_amd/csrc/presort.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/aggre.o: emqx_amd/csrc/aggre.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/dispatch.o: emqx_amd/csrc/dispatch.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/share.o: emqx_amd/csrc/share.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
 $(BUILD)/exchange.o: emqx_amd/csrc/exchange.cpp emqx_amd/csrc/kernels.h include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O2 -fPIC -std=c++17 -Wall -c $< -o $@
 
 $(BUILD)/batcher.o: emqx_amd/csrc/batcher.cpp include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O2 -fPIC -std=c++17 -Wall -pthread -c $< -o $@
-
-$(BUILD)/route.o: emqx_amd/csrc/route.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/acl.o: emqx_amd/csrc/acl.hip include/topicmatch.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(BUILD)/rewrite.o: emqx_amd/csrc/rewrite.hip include/topicmatch.h | $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
 $(LIBOUT): $(LIBOBJS)
@@ -92,7 +66,7 @@ tools/ubench/batcher_bench: tools/ubench/batcher_bench.cpp emqx_amd/libtopicmatc
 tools/ubench/libbatchdrive.so: tools/ubench/batchdrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
 
-# tm_share_* host calls under AddressSanitizer + UBSan on a host-only engine:
+# tm_route_* / tm_sub_* / tm_share_* host calls under AddressSanitizer + UBSan on a host-only engine:
 # engine.cpp instrumented, the kernels linked as built and never run.  Leak
 # detection stays on for the engine's own allocations; the HIP and RCCL
 # runtimes' start-up allocations are suppressed by library name.

@@ -35,66 +35,19 @@
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
+#include "device_bytes.h"
 
 namespace tmx {
 
 constexpr int DBLOCK = 256;
 constexpr uint32_t DCHUNK = 1024;   // pairs per wave step of the emit
 
-__device__ __forceinline__ uint64_t d_load_u64_aligned(const uint8_t* base, uint64_t p) {
-    return *reinterpret_cast<const uint64_t*>(base + (p & ~7ull));
-}
-// bytes [p, p+k) (k in 1..8) little-endian, zero padded
-__device__ __forceinline__ uint64_t d_load_chunk(const uint8_t* base, uint64_t p, uint32_t k) {
-    const uint32_t sh = (uint32_t)(p & 7) * 8;
-    uint64_t v = d_load_u64_aligned(base, p) >> sh;
-    if (sh != 0 && (p & 7) + k > 8) v |= d_load_u64_aligned(base, p + 8) << (64 - sh);
-    if (k < 8) v &= (~0ull) >> (64 - 8 * k);
-    return v;
-}
-
 // subscribers(Topic) by the topic's bytes [p, p+len): the subscriber image's
 // exact table, byte-verified; returns (segment, n_plain, n_all)
 __device__ __forceinline__ uint4 sub_exact_lookup(const SubView& sv, const uint8_t* bytes, uint64_t p, uint32_t len) {
-    if (!sv.sx_slots) return make_uint4(0, 0, 0, 0);
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = 0; i < len; i += 8) {
-        const uint32_t k = len - i < 8 ? len - i : 8;
-        h = word_hash_step(h, d_load_chunk(bytes, p + i, k));
-    }
-    h = word_hash_final(h, len);
-    for (uint64_t s = h & sv.sx_slot_mask;; s = (s + 1) & sv.sx_slot_mask) {
-        const SubSlot e = sv.sx_slots[s];
-        if (e.hash == 0) return make_uint4(0, 0, 0, 0);
-        if (e.hash == h && e.len == len) {
-            const uint64_t* a = reinterpret_cast<const uint64_t*>(sv.sx_arena + e.arena);
-            bool eq = true;
-            for (uint32_t i = 0; i < len && eq; i += 8) {
-                const uint32_t k = len - i < 8 ? len - i : 8;
-                eq = d_load_chunk(bytes, p + i, k) == a[i >> 3];
-            }
-            if (eq) return make_uint4(e.seg, e.n_plain, e.n_all, 0);
-        }
-    }
-}
-
-__device__ __forceinline__ uint64_t d_block_exclusive_scan(uint64_t x, uint64_t* lds, uint64_t& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) lds[wid] = inc;
-    __syncthreads();
-    uint64_t wpre = 0, tot = 0;
-    for (int i = 0; i < DBLOCK / 64; ++i) {
-        if (i < wid) wpre += lds[i];
-        tot += lds[i];
-    }
-    __syncthreads();
-    total = tot;
-    return wpre + inc - x;
+    SubSlot e{};   // a miss leaves it zero
+    if (sv.sx_slots) exact_find(sv.sx_slots, sv.sx_slot_mask, sv.sx_arena, GlobalBytes{bytes}, p, len, e);
+    return make_uint4(e.seg, e.n_plain, e.n_all, 0);
 }
 
 // pass 1 over blocks of 256 topics (their delivery spans are one contiguous
@@ -111,7 +64,7 @@ tm_dispatch_count(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t*
     const uint32_t t = t0 + threadIdx.x;
     const uint64_t span = threadIdx.x < tn ? aoff[t + 1] - aoff[t] : 0ull;
     uint64_t agg;
-    const uint64_t ex = d_block_exclusive_scan(span, lds_scan, agg);
+    const uint64_t ex = block_exclusive_scan<DBLOCK>(span, lds_scan, agg);
     lds_inc[threadIdx.x] = ex + span;
     __syncthreads();
     const uint64_t base = aoff[t0];

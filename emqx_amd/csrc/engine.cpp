@@ -125,9 +125,11 @@ struct Track {
 };
 
 // A host mirror of an open-addressing device table (power-of-two slots, load
-// <= 1/2, linear probing, backward-shift deletion as rt_slot_del) with its
-// dirty log.  Slot: empty() / home(), a value-initialised Slot is empty;
-// Rec: the owner of a slot, which keeps its slot index in Rec::slot.
+// <= 1/2, linear probing; backward-shift deletion: later members of the probe
+// run move up, so lookups never need tombstones) with its dirty log.  Slot:
+// empty() / home(), a value-initialised Slot is empty; Rec: the owner of a
+// slot, which keeps its slot index in Rec::slot.  A regrow carries the slot
+// values over.
 template <class Slot, class Rec>
 struct MirrorTable {
     std::vector<Slot> slots = std::vector<Slot>(16, Slot{});
@@ -178,6 +180,160 @@ struct MirrorTable {
         --used;
     }
 };
+
+// The topic bytes an exact-topic table is byte-verified against: u64 words,
+// each key zero padded to whole words (at least one).  A dropped key leaves
+// garbage until compact() rewrites the arena.
+struct TopicArena {
+    std::vector<uint64_t> words;
+    size_t garbage = 0;
+    Track t;
+    struct Span {
+        uint64_t arena, words;   // first word, word count
+    };
+    Span put(const uint8_t* key, uint32_t len) {
+        const Span s{words.size(), std::max<uint64_t>(1, (len + 7) / 8)};
+        words.resize(words.size() + s.words, 0);
+        if (len) std::memcpy(&words[s.arena], key, len);
+        t.mark_range(s.arena, s.arena + s.words);
+        return s;
+    }
+    void drop(uint64_t n_words) { garbage += n_words; }
+};
+
+// A pool of u32 segments, one per owner, which keeps its {off, cap}.  A
+// segment that no longer fits moves to a doubled one at the pool's end; the
+// old one is garbage until compact() rewrites the pool.
+struct SegPool {
+    std::vector<uint32_t> v;
+    size_t garbage = 0;
+    Track t;
+    // room for `need` entries in the owner's segment; true when it moved (the
+    // caller rewrites all of it)
+    bool fit(uint32_t& off, uint32_t& cap, size_t need, const char* overflow) {
+        if (need <= cap) return false;
+        garbage += cap;
+        uint32_t c = std::max<uint32_t>(cap * 2, 2);
+        while (c < need) c *= 2;
+        if (v.size() + c >= 0xFFFFFFF0ull) throw RangeError(overflow);
+        off = (uint32_t)v.size();
+        cap = c;
+        v.resize(v.size() + c, 0);
+        return true;
+    }
+    void set(size_t i, uint32_t x) {
+        v[i] = x;
+        t.cur.mark(i);
+    }
+    void drop(uint32_t cap) { garbage += cap; }
+};
+
+// The pool and the arena rewritten without garbage, each once its garbage
+// passes gc_min entries (a quarter of that for the arena) and half of it; the
+// whole of a rewritten one is uploaded again.  owners(seg, top) visits every
+// owner: seg(off, cap) moves a segment, top(arena, words) a key, each true
+// when it moved (the owner then syncs its slot).
+template <class Owners>
+void compact(SegPool& pool, TopicArena& arena, size_t gc_min, Owners&& owners) {
+    const bool pool_gc = pool.garbage > gc_min && pool.garbage * 2 > pool.v.size();
+    const bool arena_gc = arena.garbage > gc_min / 4 && arena.garbage * 2 > arena.words.size();
+    if (!pool_gc && !arena_gc) return;
+    std::vector<uint32_t> np;
+    std::vector<uint64_t> na;
+    if (pool_gc) np.reserve(pool.v.size() - pool.garbage);
+    if (arena_gc) na.reserve(arena.words.size() - arena.garbage);
+    owners(
+        [&](uint32_t& off, uint32_t cap) {
+            if (!pool_gc) return false;
+            const uint32_t to = (uint32_t)np.size();
+            np.insert(np.end(), pool.v.begin() + off, pool.v.begin() + off + cap);
+            off = to;
+            return true;
+        },
+        [&](uint64_t& at, uint64_t words) {
+            if (!arena_gc) return false;
+            const uint64_t to = na.size();
+            na.insert(na.end(), arena.words.begin() + at, arena.words.begin() + at + words);
+            at = to;
+            return true;
+        });
+    if (pool_gc) {
+        pool.v.swap(np);
+        pool.garbage = 0;
+        pool.t.cur.all = true;
+    }
+    if (arena_gc) {
+        arena.words.swap(na);
+        arena.garbage = 0;
+        arena.t.cur.all = true;
+    }
+}
+
+// filter id -> what the image keeps for the wildcard topic that is that trie
+// filter (Meta, `none` for an id without one), and the topic's record, which
+// keeps the id in Rec::fid while both exist
+template <class Meta, class Rec>
+struct FilterLink {
+    std::vector<Meta> meta;
+    std::vector<Rec*> rec;
+    Track t;
+    Meta none;
+    explicit FilterLink(Meta none_) : none(none_) {}
+    void link(Rec* r, uint32_t fid, size_t n_filters) {
+        if (fid >= meta.size()) {
+            const size_t old = meta.size(), n = std::max<size_t>(fid + 1, n_filters);
+            meta.resize(n, none);
+            rec.resize(n, nullptr);
+            t.mark_range(old, n);
+        }
+        r->fid = fid;
+        rec[fid] = r;
+    }
+    void unlink(Rec* r) {
+        set(r->fid, none);
+        rec[r->fid] = nullptr;
+        r->fid = FILTER_NONE;
+    }
+    void set(uint32_t fid, const Meta& m) {
+        meta[fid] = m;
+        t.cur.mark(fid);
+    }
+    Rec* owner(uint32_t fid) const { return fid < rec.size() ? rec[fid] : nullptr; }
+};
+
+// the debug checks' shared parts.  An exact-topic table against the bag it
+// mirrors: every used slot has its owner and the owners are the bag's
+// records; every key is found in its record's slot by the probe the kernels
+// run (device_bytes.h exact_find), with its last arena word zero padded
+template <class Slot, class Rec, class Bag, class Fail>
+void check_exact_table(const MirrorTable<Slot, Rec>& tab, const TopicArena& arena, const Bag& bag, Fail&& fail) {
+    size_t used = 0;
+    for (size_t s = 0; s < tab.slots.size(); ++s)
+        if (!tab.slots[s].empty()) {
+            ++used;
+            if (!tab.rec[s] || tab.rec[s]->slot != s) fail("slot owner");
+        }
+    if (used != tab.used || used != bag.size()) fail("slot count");
+    for (auto& kv : bag) {
+        const uint8_t* t = reinterpret_cast<const uint8_t*>(kv.first.data());
+        const uint32_t len = (uint32_t)kv.first.size();
+        const uint64_t h = word_hash(t, len);
+        const size_t mask = tab.slots.size() - 1;
+        size_t s = h & mask;
+        while (!tab.slots[s].empty() && !(tab.slots[s].hash == h && tab.slots[s].len == len &&
+                                          std::memcmp(&arena.words[tab.slots[s].arena / 8], t, len) == 0))
+            s = (s + 1) & mask;
+        const Slot& x = tab.slots[s];
+        if (x.empty() || s != kv.second.slot || tab.rec[s] != &kv.second) fail("probe of " + kv.first);
+        if (len % 8 && (arena.words[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) fail("arena padding");
+    }
+}
+// every pool entry and arena word is a live owner's or counted as garbage
+template <class Fail>
+void check_accounting(const SegPool& pool, const TopicArena& arena, size_t live_cap, size_t live_words, Fail&& fail) {
+    if (live_cap + pool.garbage != pool.v.size()) fail("pool accounting");
+    if (live_words + arena.garbage != arena.words.size()) fail("arena accounting");
+}
 
 struct DevBuf {
     void* p = nullptr;
@@ -534,7 +690,7 @@ struct tm_engine {
             ++heat_version;
         }
     }
-    Dirty dict_dirty;
+    Track t_dict;
 
     // ---- trie mirror / image ----
     std::vector<Node> nodes;
@@ -548,14 +704,12 @@ struct tm_engine {
     struct EdgeTable {
         std::vector<EdgeSlot> slots;
         size_t used = 0;
-        Dirty dirty;
+        Track t;
     };
     EdgeTable cold, hot;
     uint32_t hot_limit = 0;
     uint32_t hot_edge_depth = 0;      // option "hot_edges": parents of depth < D use `hot` (0 = off; A/B: no gain at C3)
-    Dirty node_dirty;
-    // the dirty maps of the previous commit (the other image missed them)
-    Dirty prev_node_dirty, prev_cold_dirty, prev_hot_dirty, prev_dict_dirty;
+    Track t_nodes;
     EdgeTable& tab(uint32_t parent) { return parent < hot_limit ? hot : cold; }
     const EdgeTable& tab(uint32_t parent) const { return parent < hot_limit ? hot : cold; }
     // ---- filter registry ----
@@ -704,28 +858,22 @@ struct tm_engine {
     size_t route_total = 0;
     // The route image, maintained in place by every add / del (no rebuild):
     // commit uploads the dirty pages into the back image epoch.
-    //   rt_slots  exact-topic table (open addressing, load <= 1/2, backward-
-    //             shift deletion): get_routes(Topic) of a publish topic
-    //   rt_arena  topic bytes of the slots (u64 words, zero padded)
-    //   rt_dest   dest segments, one per topic (capacity doubles; a moved
-    //             segment leaves garbage, compacted past half the pool)
-    //   fr_meta   filter id -> {segment, count, label}: the routes of a
+    //   rt_slots  exact-topic table (MirrorTable): get_routes(Topic) of a
+    //             publish topic
+    //   rt_arena  topic bytes of the slots (TopicArena)
+    //   rt_dest   dest segments, one per topic (SegPool)
+    //   fr.meta   filter id -> {segment, count, label}: the routes of a
     //             matched wildcard filter (the same segment as its slot)
     //   rank_src  label -> that topic as a route source (aggre's large lists)
-    std::vector<ExactSlot> rt_slots = std::vector<ExactSlot>(16, ExactSlot{0, 0, 0, 0, 0, 0});
-    std::vector<RouteRec*> rt_slot_rec = std::vector<RouteRec*>(16, nullptr);
-    size_t rt_used = 0;
-    std::vector<uint64_t> rt_arena;
-    size_t rt_arena_garbage = 0;
-    std::vector<uint32_t> rt_dest;
-    size_t rt_dest_garbage = 0;
+    MirrorTable<ExactSlot, RouteRec> rt_slots;
+    TopicArena rt_arena;
+    SegPool rt_dest;
     size_t route_gc_min = 1u << 20;   // option "route_gc": garbage entries before a compaction is considered
-    std::vector<uint4> fr_meta;
-    std::vector<RouteRec*> fr_rec;   // filter id -> linked topic
+    FilterLink<uint4, RouteRec> fr{make_uint4(0, 0, 0, 0)};
     OrdSet rt_order;
     uint32_t label_bits = 16;        // label universe 2^label_bits
     std::vector<uint32_t> rank_src = std::vector<uint32_t>(1u << 16, TM_ROUTE_TOPIC_ID);
-    Track t_slots, t_rarena, t_rdest, t_fr_meta, t_rank_src, t_dt, t_rank_tg;
+    Track t_rank_src, t_dt, t_rank_tg;
     // ---- emqx_broker:aggre/1 targets (aggre.hip) ----
     // a dest aggregates to a target: a node (atom) or a $share group; targets
     // are interned as kind byte + key bytes, so string order is the Erlang
@@ -766,18 +914,12 @@ struct tm_engine {
     size_t sub_total = 0;
     // The subscriber image, kept in place like the route image: an exact
     // table over every topic with subscribers (sx_slots / sx_arena), the pool
-    // of plain subscriber segments (sx_pool) and fs_meta: filter id ->
+    // of plain subscriber segments (sx_pool) and fs.meta: filter id ->
     // {segment, n_plain, n_all, 0}
-    std::vector<SubSlot> sx_slots = std::vector<SubSlot>(16, SubSlot{0, 0, 0, 0, 0, 0});
-    std::vector<SubRec*> sx_slot_rec = std::vector<SubRec*>(16, nullptr);
-    size_t sx_used = 0;
-    std::vector<uint64_t> sx_arena;
-    size_t sx_arena_garbage = 0;
-    std::vector<uint32_t> sx_pool;
-    size_t sx_pool_garbage = 0;
-    std::vector<uint4> fs_meta;
-    std::vector<SubRec*> fs_rec;   // filter id -> linked topic
-    Track t_sslots, t_sarena, t_spool, t_fs_meta;
+    MirrorTable<SubSlot, SubRec> sx_slots;
+    TopicArena sx_arena;
+    SegPool sx_pool;
+    FilterLink<uint4, SubRec> fs{make_uint4(0, 0, 0, 0)};
     bool local_set = false;        // tm_set_local_node: the target that is node()
     uint32_t local_target = 0;
 
@@ -808,7 +950,6 @@ struct tm_engine {
     // member -> the sets that hold it: cleanup_down/1 without a table scan,
     // and the bag's "already present" test
     std::unordered_map<uint32_t, std::vector<ShareSet*>> sh_member_sets;
-    std::unordered_map<uint32_t, ShareTopic*> sh_fid_topic;   // filter id -> linked wildcard topic
     size_t sh_total = 0;
     // The share image, kept in place like the subscriber image: the set table
     // (sh_sets: (group target, xid) -> {Count, segment, set index}), the
@@ -816,12 +957,9 @@ struct tm_engine {
     // fx (filter id -> xid of a wildcard topic) and the member pool (sh_pool).
     MirrorTable<ShareSetSlot, ShareSet> sh_sets;
     MirrorTable<ShareTopicSlot, ShareTopic> sh_tx;
-    std::vector<uint64_t> sh_arena;
-    size_t sh_arena_garbage = 0;
-    std::vector<uint32_t> sh_pool;
-    size_t sh_pool_garbage = 0;
-    std::vector<uint32_t> sh_fx;   // filter id -> xid of the wildcard topic it is (SLOT_NONE: none), as fs_meta
-    Track t_sh_arena, t_sh_pool, t_sh_fx;
+    TopicArena sh_arena;
+    SegPool sh_pool;
+    FilterLink<uint32_t, ShareTopic> sh_fx{SLOT_NONE};   // filter id -> xid of the wildcard topic it is
     std::vector<uint32_t> sh_free_xid;   // an xid names a topic only within one image: reusable at once
     uint32_t sh_next_xid = 0;
     // Set indices name cursors that outlive the images, so an index is reused
@@ -892,7 +1030,7 @@ struct tm_engine {
         std::memcpy(&d.head0, head, 8);
         std::memcpy(&d.head1, head + 8, 8);
         dict[s] = d;
-        dict_dirty.mark(s);
+        t_dict.cur.mark(s);
     }
     void dict_grow() {
         std::vector<DictSlot> old;
@@ -901,7 +1039,7 @@ struct tm_engine {
         for (const DictSlot& d : old)
             if (d.word != WORD_NONE)
                 dict_place(word_hash(&word_arena[word_off[d.word]], d.len), d.word, d.len);
-        dict_dirty.all = true;
+        t_dict.cur.all = true;
     }
     // word id of a level (interning it when `intern`)
     uint32_t word_id(const uint8_t* p, uint32_t len, bool intern) {
@@ -960,7 +1098,7 @@ struct tm_engine {
         size_t s = edge_home(x.parent, x.word, mask);
         while (t.slots[s].parent != EDGE_EMPTY) s = (s + 1) & mask;
         t.slots[s] = x;
-        t.dirty.mark(s);
+        t.t.cur.mark(s);
     }
     void edge_place(const EdgeSlot& x) { place_in(tab(x.parent), x); }
     static void edge_grow(EdgeTable& t) {
@@ -969,7 +1107,7 @@ struct tm_engine {
         t.slots.assign(old.size() * 2, kEmptySlot);
         for (const EdgeSlot& e : old)
             if (e.parent != EDGE_EMPTY) place_in(t, e);
-        t.dirty.all = true;
+        t.t.cur.all = true;
     }
     EdgeSlot slot_for(uint32_t parent, uint32_t word, uint32_t child) const {
         const Node& c = nodes[child];
@@ -1000,7 +1138,7 @@ struct tm_engine {
         const uint32_t v = child_sum(x);
         if (e.plus != v) {
             e.plus = v;
-            tab(p).dirty.mark(s);
+            tab(p).t.cur.mark(s);
         }
     }
     void edge_insert(uint32_t parent, uint32_t word, uint32_t child) {
@@ -1012,7 +1150,7 @@ struct tm_engine {
     // node x changed: mark its page and refresh the copy of its record in
     // its parent's edge slot (when it is a table child)
     void touched(uint32_t x) {
-        node_dirty.mark(x);
+        t_nodes.cur.mark(x);
         if (!SLOT_RECORD) return;
         const uint32_t p = aux[x].parent, w = aux[x].word;
         if (p == NODE_NONE || w == WORD_PLUS) return;
@@ -1020,14 +1158,14 @@ struct tm_engine {
         const size_t s = edge_find_slot(p, w);
         if (s == SIZE_MAX) return;
         tab(p).slots[s] = slot_for(p, w, x);
-        tab(p).dirty.mark(s);
+        tab(p).t.cur.mark(s);
     }
     void edge_erase(uint32_t parent, uint32_t word) {
         size_t i = edge_find_slot(parent, word);
         if (i == SIZE_MAX) return;
         EdgeTable& t = tab(parent);
         std::vector<EdgeSlot>& edges = t.slots;
-        Dirty& edge_dirty = t.dirty;
+        Dirty& edge_dirty = t.t.cur;
         size_t mask = edges.size() - 1;
         size_t j = i;
         for (;;) {
@@ -1062,7 +1200,7 @@ struct tm_engine {
         nodes[id] = empty_node();
         aux[id] = NodeAux{parent, word, 0, 0, (uint16_t)SUM_NONE, (uint16_t)SUM_NONE};
         if (word < WORD_MAX) heat_bump(word, +1);
-        node_dirty.mark(id);
+        t_nodes.cur.mark(id);
         ++live_nodes;
         ++created_since_layout;
         return id;
@@ -1165,7 +1303,7 @@ struct tm_engine {
         if (w < WORD_MAX) heat_bump(w, -1);
         nodes[c] = empty_node();
         aux[c] = NodeAux{NODE_NONE, 0, 0, 0, (uint16_t)SUM_NONE, (uint16_t)SUM_NONE};
-        node_dirty.mark(c);
+        t_nodes.cur.mark(c);
         free_nodes.push_back(c);
         --live_nodes;
         refresh_hf(v);   // a removed '#' child gives the field back to the summaries
@@ -1286,15 +1424,15 @@ struct tm_engine {
         fshape[id] = filter_shape(tmp_words.data(), (uint32_t)tmp_words.size());   // insert's split_words
         t_fshape.cur.mark(id);
         ++live_filters;
-        on_filter_new(p, len, id);
-        on_filter_new_subs(p, len, id);
-        on_filter_new_shares(p, len, id);
+        on_filter_new(route_bag, p, len, id);
+        on_filter_new(sub_bag, p, len, id);
+        on_filter_new(sh_topics, p, len, id);
         return id;
     }
     void free_filter(uint32_t id) {
-        on_filter_free(id);
-        on_filter_free_subs(id);
-        on_filter_free_shares(id);
+        on_filter_free(fr, id);
+        on_filter_free(fs, id);
+        on_filter_free(sh_fx, id);
         filters[id].node = NODE_NONE;   // off / len stay: the gather serves the id until it is reused
         quarantine.emplace_back(epoch.load() + 1, id);   // the next commit drops it from the images
         quarantined[id] = epoch.load() + 1;
@@ -1404,10 +1542,12 @@ struct tm_engine {
             it = route_bag.emplace(std::move(key), RouteRec{}).first;
             RouteRec& r = it->second;
             r.key = &it->first;
-            rt_arena_put(r);
-            rt_slot_put(&r);
+            const TopicArena::Span sp = rt_arena.put(t, tlen);
+            r.arena = sp.arena;
+            r.words = sp.words;
+            rt_slots.put(ExactSlot{word_hash(t, tlen), tlen, 0, r.arena * 8, 0, 0}, &r);
             order_insert(&r);
-            if (wild) fr_link(&r, filter_of(t, tlen));
+            if (wild) link_filter(r, filter_of(t, tlen));
         }
         RouteRec& r = it->second;
         r.dests.push_back(dest);
@@ -1445,11 +1585,11 @@ struct tm_engine {
             return;
         }
         // the last route of the topic: out of the image, then [Route] -> emqx_trie:delete(Topic)
-        fr_unlink(&r);
-        rt_slot_del(&r);
+        unlink_filter(r);
+        rt_slots.del(&r);
         order_erase(&r);
-        rt_dest_garbage += r.cap;
-        rt_arena_garbage += r.words;
+        rt_dest.drop(r.cap);
+        rt_arena.drop(r.words);
         route_bag.erase(it);
         if (trie && tm_topic_wildcard(t, tlen)) remove(t, tlen);
         maybe_compact_routes();
@@ -1470,170 +1610,77 @@ struct tm_engine {
     void rt_sync(const RouteRec& r) {
         const uint32_t count = (uint32_t)r.dests.size();
         if (r.slot != SLOT_NONE) {
-            ExactSlot& s = rt_slots[r.slot];
+            ExactSlot& s = rt_slots.slots[r.slot];
             s.count = count;
             s.dest_off = r.off;
             s.rank = r.label;
             s.arena = r.arena * 8;
-            t_slots.cur.mark(r.slot);
+            rt_slots.t.cur.mark(r.slot);
         }
-        if (r.fid != FILTER_NONE) {
-            fr_meta[r.fid] = make_uint4(r.off, count, r.label, 0u);
-            t_fr_meta.cur.mark(r.fid);
-        }
+        if (r.fid != FILTER_NONE) fr.set(r.fid, make_uint4(r.off, count, r.label, 0u));
         rank_src[r.label] = r.fid != FILTER_NONE ? r.fid : TM_ROUTE_TOPIC_ID;
         t_rank_src.cur.mark(r.label);
     }
-    // dests [from, end) of r into its segment (a new, doubled segment at the
-    // pool's end when they no longer fit; the old one becomes garbage)
+    // dests [from, end) of r into its segment (all of them into a new one
+    // when they no longer fit)
     void seg_write(RouteRec& r, size_t from) {
         const size_t n = r.dests.size();
-        if (n > r.cap) {
-            rt_dest_garbage += r.cap;
-            uint32_t cap = std::max<uint32_t>(r.cap * 2, 2);
-            while (cap < n) cap *= 2;
-            if (rt_dest.size() + cap >= 0xFFFFFFF0ull) throw RangeError("route dest pool past 2^32 entries");
-            r.off = (uint32_t)rt_dest.size();
-            r.cap = cap;
-            rt_dest.resize(rt_dest.size() + cap, 0);
-            from = 0;
-        }
+        if (rt_dest.fit(r.off, r.cap, n, "route dest pool past 2^32 entries")) from = 0;
         if (n > from) {
-            std::copy(r.dests.begin() + from, r.dests.end(), rt_dest.begin() + r.off + from);
-            t_rdest.mark_range(r.off + from, r.off + n);
+            std::copy(r.dests.begin() + from, r.dests.end(), rt_dest.v.begin() + r.off + from);
+            rt_dest.t.mark_range(r.off + from, r.off + n);
         }
         rt_sync(r);
     }
-    void rt_arena_put(RouteRec& r) {
-        const uint32_t len = (uint32_t)r.key->size();
-        r.words = std::max<uint64_t>(1, (len + 7) / 8);
-        r.arena = rt_arena.size();
-        rt_arena.resize(rt_arena.size() + r.words, 0);
-        if (len) std::memcpy(&rt_arena[r.arena], r.key->data(), len);
-        t_rarena.mark_range(r.arena, r.arena + r.words);
-    }
-    void rt_slot_put(RouteRec* r) {
-        if ((rt_used + 1) * 2 > rt_slots.size()) rt_regrow(rt_slots.size() * 2);
-        const uint8_t* t = reinterpret_cast<const uint8_t*>(r->key->data());
-        const uint64_t h = word_hash(t, (uint32_t)r->key->size());
-        const size_t mask = rt_slots.size() - 1;
-        size_t s = h & mask;
-        while (rt_slots[s].hash) s = (s + 1) & mask;
-        rt_slots[s] = ExactSlot{h, (uint32_t)r->key->size(), 0, r->arena * 8, 0, 0};
-        rt_slot_rec[s] = r;
-        r->slot = (uint32_t)s;
-        ++rt_used;
-        t_slots.cur.mark(s);
-    }
-    // backward-shift deletion: later members of the probe run move up, so
-    // lookups never need tombstones
-    void rt_slot_del(RouteRec* r) {
-        const size_t mask = rt_slots.size() - 1;
-        size_t i = r->slot;
-        for (size_t j = (i + 1) & mask; rt_slots[j].hash; j = (j + 1) & mask) {
-            const size_t home = rt_slots[j].hash & mask;
-            // move j into the hole at i unless its home lies cyclically in (i, j]
-            const bool stays = i <= j ? (home > i && home <= j) : (home > i || home <= j);
-            if (stays) continue;
-            rt_slots[i] = rt_slots[j];
-            rt_slot_rec[i] = rt_slot_rec[j];
-            rt_slot_rec[i]->slot = (uint32_t)i;
-            t_slots.cur.mark(i);
-            i = j;
-        }
-        rt_slots[i] = ExactSlot{0, 0, 0, 0, 0, 0};
-        rt_slot_rec[i] = nullptr;
-        t_slots.cur.mark(i);
-        r->slot = SLOT_NONE;
-        --rt_used;
-    }
-    void rt_regrow(size_t cap) {
-        std::vector<RouteRec*> recs;
-        recs.reserve(rt_used);
-        for (RouteRec* r : rt_slot_rec)
-            if (r) recs.push_back(r);
-        rt_slots.assign(cap, ExactSlot{0, 0, 0, 0, 0, 0});
-        rt_slot_rec.assign(cap, nullptr);
-        rt_used = 0;
-        for (RouteRec* r : recs) {
-            rt_slot_put(r);
-            rt_sync(*r);
-        }
-        t_slots.cur.all = true;
-    }
-    // the pool and the arena rewritten without garbage (all pages re-uploaded)
     void maybe_compact_routes() {
-        const bool dest_gc = rt_dest_garbage > route_gc_min && rt_dest_garbage * 2 > rt_dest.size();
-        const bool arena_gc = rt_arena_garbage > route_gc_min / 4 && rt_arena_garbage * 2 > rt_arena.size();
-        if (!dest_gc && !arena_gc) return;
-        std::vector<uint32_t> nd;
-        std::vector<uint64_t> na;
-        if (dest_gc) nd.reserve(rt_dest.size() - rt_dest_garbage);
-        if (arena_gc) na.reserve(rt_arena.size() - rt_arena_garbage);
-        for (auto& kv : route_bag) {
-            RouteRec& r = kv.second;
-            if (dest_gc) {
-                const uint32_t off = (uint32_t)nd.size();
-                nd.insert(nd.end(), rt_dest.begin() + r.off, rt_dest.begin() + r.off + r.cap);
-                r.off = off;
+        compact(rt_dest, rt_arena, route_gc_min, [&](auto seg, auto top) {
+            for (auto& kv : route_bag) {
+                RouteRec& r = kv.second;
+                seg(r.off, r.cap);
+                top(r.arena, r.words);
+                rt_sync(r);
             }
-            if (arena_gc) {
-                const uint64_t a = na.size();
-                na.insert(na.end(), rt_arena.begin() + r.arena, rt_arena.begin() + r.arena + r.words);
-                r.arena = a;
-            }
-            rt_sync(r);
-        }
-        if (dest_gc) {
-            rt_dest.swap(nd);
-            rt_dest_garbage = 0;
-            t_rdest.cur.all = true;
-        }
-        if (arena_gc) {
-            rt_arena.swap(na);
-            rt_arena_garbage = 0;
-            t_rarena.cur.all = true;
-        }
+        });
     }
-    // a wildcard topic's filter id <-> its routes
-    void fr_link(RouteRec* r, uint32_t fid) {
+    // a wildcard topic's filter id <-> its routes, subscribers or share sets
+    void link_filter(RouteRec& r, uint32_t fid) {
         if (fid == FILTER_NONE) return;
-        if (fid >= fr_meta.size()) {
-            const size_t old = fr_meta.size(), n = std::max<size_t>(fid + 1, filters.size());
-            fr_meta.resize(n, make_uint4(0, 0, 0, 0));
-            fr_rec.resize(n, nullptr);
-            t_fr_meta.mark_range(old, n);
-        }
-        r->fid = fid;
-        fr_rec[fid] = r;
-        rt_sync(*r);
+        fr.link(&r, fid, filters.size());
+        rt_sync(r);
     }
-    void fr_unlink(RouteRec* r) {
-        if (r->fid == FILTER_NONE) return;
-        fr_meta[r->fid] = make_uint4(0, 0, 0, 0);
-        fr_rec[r->fid] = nullptr;
-        t_fr_meta.cur.mark(r->fid);
-        r->fid = FILTER_NONE;
-        rt_sync(*r);
+    void unlink_filter(RouteRec& r) {
+        if (r.fid == FILTER_NONE) return;
+        fr.unlink(&r);
+        rt_sync(r);
+    }
+    void link_filter(SubRec& r, uint32_t fid) {
+        if (fid == FILTER_NONE) return;
+        fs.link(&r, fid, filters.size());
+        sx_sync(r);
+    }
+    void unlink_filter(SubRec& r) {
+        if (r.fid != FILTER_NONE) fs.unlink(&r);
+    }
+    void link_filter(ShareTopic& tp, uint32_t fid) {
+        if (fid == FILTER_NONE) return;
+        sh_fx.link(&tp, fid, filters.size());
+        sh_fx.set(fid, tp.xid);
+    }
+    void unlink_filter(ShareTopic& tp) {
+        if (tp.fid != FILTER_NONE) sh_fx.unlink(&tp);
     }
     // trie hooks (new_filter / free_filter): a filter created or deleted
-    // outside add_route / del_route (tm_insert / tm_delete of a topic that
-    // has routes) keeps the link right
-    void on_filter_new(const uint8_t* p, uint32_t len, uint32_t fid) {
-        if (route_bag.empty() || !tm_topic_wildcard(p, len)) return;
-        auto it = route_bag.find(std::string(reinterpret_cast<const char*>(p), len));
-        if (it != route_bag.end() && it->second.fid == FILTER_NONE) fr_link(&it->second, fid);
+    // outside the image's own add / del (tm_insert / tm_delete of a topic that
+    // has routes, subscribers or share sets) keeps the link right
+    template <class Bag>
+    void on_filter_new(Bag& bag, const uint8_t* p, uint32_t len, uint32_t fid) {
+        if (bag.empty() || !tm_topic_wildcard(p, len)) return;
+        auto it = bag.find(std::string(reinterpret_cast<const char*>(p), len));
+        if (it != bag.end() && it->second.fid == FILTER_NONE) link_filter(it->second, fid);
     }
-    void on_filter_free(uint32_t fid) {
-        if (fid < fr_rec.size() && fr_rec[fid]) fr_unlink(fr_rec[fid]);
-    }
-    void on_filter_new_subs(const uint8_t* p, uint32_t len, uint32_t fid) {
-        if (sub_bag.empty() || !tm_topic_wildcard(p, len)) return;
-        auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(p), len));
-        if (it != sub_bag.end() && it->second.fid == FILTER_NONE) fs_link(&it->second, fid);
-    }
-    void on_filter_free_subs(uint32_t fid) {
-        if (fid < fs_rec.size() && fs_rec[fid]) fs_unlink(fs_rec[fid]);
+    template <class Link>
+    void on_filter_free(Link& l, uint32_t fid) {
+        if (auto* r = l.owner(fid)) unlink_filter(*r);
     }
 
     // ------------------------------------------------------------------
@@ -1671,9 +1718,11 @@ struct tm_engine {
             it = sub_bag.emplace(std::move(key), SubRec{}).first;
             SubRec& r = it->second;
             r.key = &it->first;
-            sx_arena_put(r);
-            sx_slot_put(&r);
-            if (tm_topic_wildcard(t, tlen)) fs_link(&r, filter_of(t, tlen));
+            const TopicArena::Span sp = sx_arena.put(t, tlen);
+            r.arena = sp.arena;
+            r.words = sp.words;
+            sx_slots.put(SubSlot{word_hash(t, tlen), tlen, 0, r.arena * 8, 0, 0}, &r);
+            if (tm_topic_wildcard(t, tlen)) link_filter(r, filter_of(t, tlen));
         }
         SubRec& r = it->second;
         r.bag.emplace_back(sub, gid);
@@ -1716,10 +1765,10 @@ struct tm_engine {
             else sx_sync(r);
             return (uint32_t)r.bag.size();
         }
-        fs_unlink(&r);
-        sx_slot_del(&r);
-        sx_pool_garbage += r.cap;
-        sx_arena_garbage += r.words;
+        unlink_filter(r);
+        sx_slots.del(&r);
+        sx_pool.drop(r.cap);
+        sx_arena.drop(r.words);
         sub_bag.erase(it);
         maybe_compact_subs();
         return 0;
@@ -1733,158 +1782,47 @@ struct tm_engine {
     void sx_sync(const SubRec& r) {
         const uint32_t n_all = (uint32_t)r.bag.size();
         if (r.slot != SLOT_NONE) {
-            SubSlot& s = sx_slots[r.slot];
+            SubSlot& s = sx_slots.slots[r.slot];
             s.n_plain = r.n_plain;
             s.n_all = n_all;
             s.seg = r.off;
             s.arena = r.arena * 8;
-            t_sslots.cur.mark(r.slot);
+            sx_slots.t.cur.mark(r.slot);
         }
-        if (r.fid != FILTER_NONE) {
-            fs_meta[r.fid] = make_uint4(r.off, r.n_plain, n_all, 0u);
-            t_fs_meta.cur.mark(r.fid);
-        }
+        if (r.fid != FILTER_NONE) fs.set(r.fid, make_uint4(r.off, r.n_plain, n_all, 0u));
     }
-    // the plain subscribers of r into its segment, from the bag (a new,
-    // doubled segment at the pool's end when they no longer fit)
+    // the plain subscribers of r into its segment, from the bag
     void sseg_rewrite(SubRec& r) {
-        if (r.n_plain > r.cap) {
-            sx_pool_garbage += r.cap;
-            uint32_t cap = std::max<uint32_t>(r.cap * 2, 2);
-            while (cap < r.n_plain) cap *= 2;
-            if (sx_pool.size() + cap >= 0xFFFFFFF0ull) throw RangeError("subscriber pool past 2^32 entries");
-            r.off = (uint32_t)sx_pool.size();
-            r.cap = cap;
-            sx_pool.resize(sx_pool.size() + cap, 0);
-        }
+        sx_pool.fit(r.off, r.cap, r.n_plain, "subscriber pool past 2^32 entries");
         size_t k = r.off;
         for (const auto& x : r.bag)
-            if (x.second == NO_GROUP) sx_pool[k++] = x.first;
-        t_spool.mark_range(r.off, k);
+            if (x.second == NO_GROUP) sx_pool.v[k++] = x.first;
+        sx_pool.t.mark_range(r.off, k);
         sx_sync(r);
     }
     void sseg_append(SubRec& r, uint32_t sub) {   // sub is r's last plain entry
         if (r.n_plain > r.cap) return sseg_rewrite(r);
-        sx_pool[r.off + r.n_plain - 1] = sub;
-        t_spool.cur.mark(r.off + r.n_plain - 1);
+        sx_pool.set(r.off + r.n_plain - 1, sub);
         sx_sync(r);
     }
-    void sx_arena_put(SubRec& r) {
-        const uint32_t len = (uint32_t)r.key->size();
-        r.words = std::max<uint64_t>(1, (len + 7) / 8);
-        r.arena = sx_arena.size();
-        sx_arena.resize(sx_arena.size() + r.words, 0);
-        if (len) std::memcpy(&sx_arena[r.arena], r.key->data(), len);
-        t_sarena.mark_range(r.arena, r.arena + r.words);
-    }
-    void sx_slot_put(SubRec* r) {
-        if ((sx_used + 1) * 2 > sx_slots.size()) sx_regrow(sx_slots.size() * 2);
-        const uint8_t* t = reinterpret_cast<const uint8_t*>(r->key->data());
-        const uint64_t h = word_hash(t, (uint32_t)r->key->size());
-        const size_t mask = sx_slots.size() - 1;
-        size_t s = h & mask;
-        while (sx_slots[s].hash) s = (s + 1) & mask;
-        sx_slots[s] = SubSlot{h, (uint32_t)r->key->size(), 0, r->arena * 8, 0, 0};
-        sx_slot_rec[s] = r;
-        r->slot = (uint32_t)s;
-        ++sx_used;
-        t_sslots.cur.mark(s);
-    }
-    void sx_slot_del(SubRec* r) {   // backward-shift deletion, as rt_slot_del
-        const size_t mask = sx_slots.size() - 1;
-        size_t i = r->slot;
-        for (size_t j = (i + 1) & mask; sx_slots[j].hash; j = (j + 1) & mask) {
-            const size_t home = sx_slots[j].hash & mask;
-            const bool stays = i <= j ? (home > i && home <= j) : (home > i || home <= j);
-            if (stays) continue;
-            sx_slots[i] = sx_slots[j];
-            sx_slot_rec[i] = sx_slot_rec[j];
-            sx_slot_rec[i]->slot = (uint32_t)i;
-            t_sslots.cur.mark(i);
-            i = j;
-        }
-        sx_slots[i] = SubSlot{0, 0, 0, 0, 0, 0};
-        sx_slot_rec[i] = nullptr;
-        t_sslots.cur.mark(i);
-        r->slot = SLOT_NONE;
-        --sx_used;
-    }
-    void sx_regrow(size_t cap) {
-        std::vector<SubRec*> recs;
-        recs.reserve(sx_used);
-        for (SubRec* r : sx_slot_rec)
-            if (r) recs.push_back(r);
-        sx_slots.assign(cap, SubSlot{0, 0, 0, 0, 0, 0});
-        sx_slot_rec.assign(cap, nullptr);
-        sx_used = 0;
-        for (SubRec* r : recs) {
-            sx_slot_put(r);
-            sx_sync(*r);
-        }
-        t_sslots.cur.all = true;
-    }
-    // the pool and the arena rewritten without garbage (option "route_gc"
-    // sets the threshold of both images)
+    // option "route_gc" sets the threshold of all three images
     void maybe_compact_subs() {
-        const bool pool_gc = sx_pool_garbage > route_gc_min && sx_pool_garbage * 2 > sx_pool.size();
-        const bool arena_gc = sx_arena_garbage > route_gc_min / 4 && sx_arena_garbage * 2 > sx_arena.size();
-        if (!pool_gc && !arena_gc) return;
-        std::vector<uint32_t> np;
-        std::vector<uint64_t> na;
-        if (pool_gc) np.reserve(sx_pool.size() - sx_pool_garbage);
-        if (arena_gc) na.reserve(sx_arena.size() - sx_arena_garbage);
-        for (auto& kv : sub_bag) {
-            SubRec& r = kv.second;
-            if (pool_gc) {
-                const uint32_t off = (uint32_t)np.size();
-                np.insert(np.end(), sx_pool.begin() + r.off, sx_pool.begin() + r.off + r.cap);
-                r.off = off;
+        compact(sx_pool, sx_arena, route_gc_min, [&](auto seg, auto top) {
+            for (auto& kv : sub_bag) {
+                SubRec& r = kv.second;
+                seg(r.off, r.cap);
+                top(r.arena, r.words);
+                sx_sync(r);
             }
-            if (arena_gc) {
-                const uint64_t a = na.size();
-                na.insert(na.end(), sx_arena.begin() + r.arena, sx_arena.begin() + r.arena + r.words);
-                r.arena = a;
-            }
-            sx_sync(r);
-        }
-        if (pool_gc) {
-            sx_pool.swap(np);
-            sx_pool_garbage = 0;
-            t_spool.cur.all = true;
-        }
-        if (arena_gc) {
-            sx_arena.swap(na);
-            sx_arena_garbage = 0;
-            t_sarena.cur.all = true;
-        }
-    }
-    // a wildcard topic's filter id <-> its bag
-    void fs_link(SubRec* r, uint32_t fid) {
-        if (fid == FILTER_NONE) return;
-        if (fid >= fs_meta.size()) {
-            const size_t old = fs_meta.size(), n = std::max<size_t>(fid + 1, filters.size());
-            fs_meta.resize(n, make_uint4(0, 0, 0, 0));
-            fs_rec.resize(n, nullptr);
-            t_fs_meta.mark_range(old, n);
-        }
-        r->fid = fid;
-        fs_rec[fid] = r;
-        sx_sync(*r);
-    }
-    void fs_unlink(SubRec* r) {
-        if (r->fid == FILTER_NONE) return;
-        fs_meta[r->fid] = make_uint4(0, 0, 0, 0);
-        fs_rec[r->fid] = nullptr;
-        t_fs_meta.cur.mark(r->fid);
-        r->fid = FILTER_NONE;
+        });
     }
     SubView make_sub_view(const Image& g) const {
         SubView sv;
         sv.fs_meta = g.d_fs_meta.as<const uint4>();
-        sv.n_filters = (uint32_t)fs_meta.size();
+        sv.n_filters = (uint32_t)fs.meta.size();
         sv.local_target = local_target;
         sv.sx_slots = g.d_sslots.as<const SubSlot>();
-        sv.sx_slot_mask = sx_slots.size() - 1;
+        sv.sx_slot_mask = sx_slots.slots.size() - 1;
         sv.sx_arena = g.d_sarena.as<const uint8_t>();
         sv.pool = g.d_spool.as<const uint32_t>();
         return sv;
@@ -1894,36 +1832,6 @@ struct tm_engine {
     // shared subscriptions (emqx_shared_sub.erl): the member bag and the image
     // share.hip reads.  Independent of the trie, the routes and the
     // emqx_subscriber bag.
-    void on_filter_new_shares(const uint8_t* p, uint32_t len, uint32_t fid) {
-        if (sh_topics.empty() || !tm_topic_wildcard(p, len)) return;
-        auto it = sh_topics.find(std::string(reinterpret_cast<const char*>(p), len));
-        if (it == sh_topics.end() || it->second.fid != FILTER_NONE) return;
-        share_fx_link(it->second, fid);
-    }
-    void share_fx_link(ShareTopic& tp, uint32_t fid) {
-        if (fid == FILTER_NONE) return;
-        if (fid >= sh_fx.size()) {
-            const size_t old = sh_fx.size(), n = std::max<size_t>(fid + 1, filters.size());
-            sh_fx.resize(n, SLOT_NONE);
-            t_sh_fx.mark_range(old, n);
-        }
-        tp.fid = fid;
-        sh_fid_topic[fid] = &tp;
-        sh_fx[fid] = tp.xid;
-        t_sh_fx.cur.mark(fid);
-    }
-    void share_fx_unlink(ShareTopic& tp) {
-        if (tp.fid == FILTER_NONE) return;
-        sh_fx[tp.fid] = SLOT_NONE;
-        t_sh_fx.cur.mark(tp.fid);
-        sh_fid_topic.erase(tp.fid);
-        tp.fid = FILTER_NONE;
-    }
-    void on_filter_free_shares(uint32_t fid) {
-        auto it = sh_fid_topic.find(fid);
-        if (it == sh_fid_topic.end()) return;
-        share_fx_unlink(*it->second);
-    }
     void share_slot_put(ShareSet& s) {
         const ShareTopic& tp = *s.topic;
         sh_sets.put(ShareSetSlot{s.tg, tp.xid, (uint32_t)s.members.size(), s.off, s.six, 0u, 0u, 0u}, &s);
@@ -1935,21 +1843,12 @@ struct tm_engine {
         x.seg = s.off;
         sh_sets.t.cur.mark(s.slot);
     }
-    // the members of s into its segment (a new, doubled segment at the
-    // pool's end when they no longer fit)
+    // the members of s into its segment
     void share_seg_rewrite(ShareSet& s) {
         const size_t n = s.members.size();
-        if (n > s.cap) {
-            sh_pool_garbage += s.cap;
-            uint32_t cap = std::max<uint32_t>(s.cap * 2, 2);
-            while (cap < n) cap *= 2;
-            if (sh_pool.size() + cap >= 0xFFFFFFF0ull) throw RangeError("share member pool past 2^32 entries");
-            s.off = (uint32_t)sh_pool.size();
-            s.cap = cap;
-            sh_pool.resize(sh_pool.size() + cap, 0);
-        }
-        std::copy(s.members.begin(), s.members.end(), sh_pool.begin() + s.off);
-        t_sh_pool.mark_range(s.off, s.off + n);
+        sh_pool.fit(s.off, s.cap, n, "share member pool past 2^32 entries");
+        std::copy(s.members.begin(), s.members.end(), sh_pool.v.begin() + s.off);
+        sh_pool.t.mark_range(s.off, s.off + n);
         share_sync(s);
     }
     uint32_t share_alloc_six() {
@@ -1996,13 +1895,11 @@ struct tm_engine {
             } else {
                 tp.xid = sh_next_xid++;
             }
-            tp.words = std::max<uint64_t>(1, (tlen + 7) / 8);
-            tp.arena = sh_arena.size();
-            sh_arena.resize(sh_arena.size() + tp.words, 0);
-            if (tlen) std::memcpy(&sh_arena[tp.arena], t, tlen);
-            t_sh_arena.mark_range(tp.arena, tp.arena + tp.words);
+            const TopicArena::Span ap = sh_arena.put(t, tlen);
+            tp.arena = ap.arena;
+            tp.words = ap.words;
             sh_tx.put(ShareTopicSlot{word_hash(t, tlen), tlen, tp.xid, tp.arena * 8, 0}, &tp);
-            if (tp.wild) share_fx_link(tp, filter_of(t, tlen));
+            if (tp.wild) link_filter(tp, filter_of(t, tlen));
         }
         ShareTopic& tp = it->second;
         std::unique_ptr<ShareSet>& sp = tp.sets[tg];
@@ -2021,8 +1918,7 @@ struct tm_engine {
         if (s.members.size() > s.cap) {
             share_seg_rewrite(s);
         } else {
-            sh_pool[s.off + s.members.size() - 1] = member;
-            t_sh_pool.cur.mark(s.off + s.members.size() - 1);
+            sh_pool.set(s.off + s.members.size() - 1, member);
             share_sync(s);
         }
         if (s.slot == SLOT_NONE) share_slot_put(s);   // a new set: in the table once it has its member
@@ -2048,15 +1944,15 @@ struct tm_engine {
         if (!s.members.empty()) return share_seg_rewrite(s);
         ShareTopic& tp = *s.topic;
         if (s.slot != SLOT_NONE) sh_sets.del(&s);
-        sh_pool_garbage += s.cap;
+        sh_pool.drop(s.cap);
         sh_six_quarantine.emplace_back(epoch.load() + 1, s.six);
         const uint32_t tg = s.tg;
         tp.sets.erase(tg);   // frees s
         if (!tp.sets.empty()) return;
-        share_fx_unlink(tp);
+        unlink_filter(tp);
         sh_tx.del(&tp);
         sh_free_xid.push_back(tp.xid);
-        sh_arena_garbage += tp.words;
+        sh_arena.drop(tp.words);
         const std::string key = *tp.key;
         sh_topics.erase(key);
     }
@@ -2091,39 +1987,17 @@ struct tm_engine {
         return (uint32_t)of.size();
     }
     void maybe_compact_shares() {
-        const bool pool_gc = sh_pool_garbage > route_gc_min && sh_pool_garbage * 2 > sh_pool.size();
-        const bool arena_gc = sh_arena_garbage > route_gc_min / 4 && sh_arena_garbage * 2 > sh_arena.size();
-        if (!pool_gc && !arena_gc) return;
-        std::vector<uint32_t> np;
-        std::vector<uint64_t> na;
-        for (auto& kv : sh_topics) {
-            ShareTopic& tp = kv.second;
-            if (pool_gc)
-                for (auto& sk : tp.sets) {
-                    ShareSet& s = *sk.second;
-                    const uint32_t off = (uint32_t)np.size();
-                    np.insert(np.end(), sh_pool.begin() + s.off, sh_pool.begin() + s.off + s.cap);
-                    s.off = off;
-                    share_sync(s);
+        compact(sh_pool, sh_arena, route_gc_min, [&](auto seg, auto top) {
+            for (auto& kv : sh_topics) {
+                ShareTopic& tp = kv.second;
+                for (auto& sk : tp.sets)
+                    if (seg(sk.second->off, sk.second->cap)) share_sync(*sk.second);
+                if (top(tp.arena, tp.words)) {
+                    sh_tx.slots[tp.slot].arena = tp.arena * 8;
+                    sh_tx.t.cur.mark(tp.slot);
                 }
-            if (arena_gc) {
-                const uint64_t a = na.size();
-                na.insert(na.end(), sh_arena.begin() + tp.arena, sh_arena.begin() + tp.arena + tp.words);
-                tp.arena = a;
-                sh_tx.slots[tp.slot].arena = a * 8;
-                sh_tx.t.cur.mark(tp.slot);
             }
-        }
-        if (pool_gc) {
-            sh_pool.swap(np);
-            sh_pool_garbage = 0;
-            t_sh_pool.cur.all = true;
-        }
-        if (arena_gc) {
-            sh_arena.swap(na);
-            sh_arena_garbage = 0;
-            t_sh_arena.cur.all = true;
-        }
+        });
     }
     ShareView make_share_view(const Image& g) const {
         ShareView hv;
@@ -2134,7 +2008,7 @@ struct tm_engine {
         hv.tx_arena = g.d_harena.as<const uint8_t>();
         hv.pool = g.d_hpool.as<const uint32_t>();
         hv.fx = g.d_hfx.as<const uint32_t>();
-        hv.n_filters = (uint32_t)sh_fx.size();
+        hv.n_filters = (uint32_t)sh_fx.meta.size();
         hv.cursor = g.cursor;
         hv.n_sets = sh_next_six;
         return hv;
@@ -2289,9 +2163,9 @@ struct tm_engine {
     RouteView make_route_view(const Image& g) const {
         RouteView rv;
         rv.fr_meta = g.d_fr_meta.as<const uint4>();
-        rv.n_filters = (uint32_t)fr_meta.size();
+        rv.n_filters = (uint32_t)fr.meta.size();
         rv.ex_slots = g.d_rslots.as<const ExactSlot>();
-        rv.ex_slot_mask = rt_slots.size() - 1;
+        rv.ex_slot_mask = rt_slots.slots.size() - 1;
         rv.ex_arena = g.d_rarena.as<const uint8_t>();
         rv.dest = g.d_rdest.as<const uint32_t>();
         return rv;
@@ -2524,9 +2398,9 @@ struct tm_engine {
         free_nodes.clear();
         created_since_layout = 0;
         force_relayout = false;
-        node_dirty.all = true;
-        cold.dirty.all = true;
-        hot.dirty.all = true;
+        t_nodes.cur.all = true;
+        cold.t.cur.all = true;
+        hot.t.cur.all = true;
     }
 
     // ------------------------------------------------------------------
@@ -2580,6 +2454,37 @@ struct tm_engine {
         im.word_heat = g.d_wheat.as<const uint8_t>();
         im.n_words = g.heat_words;
         return im;
+    }
+
+    // Every host table the images mirror, named once: the table, its dirty
+    // logs and its buffer in an Image.  commit() uploads and rotates over this
+    // list, so a table cannot be in one loop and missing from the other (the
+    // other image epoch would then miss one commit's changes).  The one
+    // asymmetry: fshape is kept and rotated always, uploaded only under
+    // option "shape_keys".
+    template <class F>
+    void for_each_table(F&& f) {
+        f(nodes, t_nodes, &Image::d_nodes, true);
+        f(cold.slots, cold.t, &Image::d_edges, true);
+        f(hot.slots, hot.t, &Image::d_hedges, true);
+        f(dict, t_dict, &Image::d_dict, true);
+        f(rt_slots.slots, rt_slots.t, &Image::d_rslots, true);
+        f(rt_arena.words, rt_arena.t, &Image::d_rarena, true);
+        f(rt_dest.v, rt_dest.t, &Image::d_rdest, true);
+        f(fr.meta, fr.t, &Image::d_fr_meta, true);
+        f(rank_src, t_rank_src, &Image::d_rank_src, true);
+        f(dt, t_dt, &Image::d_dt, true);
+        f(rank_tg, t_rank_tg, &Image::d_rank_tg, true);
+        f(sx_slots.slots, sx_slots.t, &Image::d_sslots, true);
+        f(sx_arena.words, sx_arena.t, &Image::d_sarena, true);
+        f(sx_pool.v, sx_pool.t, &Image::d_spool, true);
+        f(fs.meta, fs.t, &Image::d_fs_meta, true);
+        f(sh_sets.slots, sh_sets.t, &Image::d_hsets, true);
+        f(sh_tx.slots, sh_tx.t, &Image::d_htx, true);
+        f(sh_arena.words, sh_arena.t, &Image::d_harena, true);
+        f(sh_pool.v, sh_pool.t, &Image::d_hpool, true);
+        f(sh_fx.meta, sh_fx.t, &Image::d_hfx, true);
+        f(fshape, t_fshape, &Image::d_fshape, shape_keys != 0);
     }
 
     // upload a host table to one replica: the whole table after a resize (or
@@ -2678,28 +2583,10 @@ struct tm_engine {
             const int back = double_buffer ? 1 - d.cur : d.cur;
             Image& g = d.img[back];
             d.drain_image(back);   // the batches launched on it before the last flip
-            upload_table(d, g, g.d_nodes, nodes, node_dirty, prev_node_dirty);
-            upload_table(d, g, g.d_edges, cold.slots, cold.dirty, prev_cold_dirty);
-            upload_table(d, g, g.d_hedges, hot.slots, hot.dirty, prev_hot_dirty);
-            upload_table(d, g, g.d_dict, dict, dict_dirty, prev_dict_dirty);
-            upload_table(d, g, g.d_rslots, rt_slots, t_slots.cur, t_slots.prev);
-            upload_table(d, g, g.d_rarena, rt_arena, t_rarena.cur, t_rarena.prev);
-            upload_table(d, g, g.d_rdest, rt_dest, t_rdest.cur, t_rdest.prev);
-            upload_table(d, g, g.d_fr_meta, fr_meta, t_fr_meta.cur, t_fr_meta.prev);
-            upload_table(d, g, g.d_rank_src, rank_src, t_rank_src.cur, t_rank_src.prev);
-            upload_table(d, g, g.d_dt, dt, t_dt.cur, t_dt.prev);
-            upload_table(d, g, g.d_rank_tg, rank_tg, t_rank_tg.cur, t_rank_tg.prev);
-            upload_table(d, g, g.d_sslots, sx_slots, t_sslots.cur, t_sslots.prev);
-            upload_table(d, g, g.d_sarena, sx_arena, t_sarena.cur, t_sarena.prev);
-            upload_table(d, g, g.d_spool, sx_pool, t_spool.cur, t_spool.prev);
-            upload_table(d, g, g.d_fs_meta, fs_meta, t_fs_meta.cur, t_fs_meta.prev);
-            upload_table(d, g, g.d_hsets, sh_sets.slots, sh_sets.t.cur, sh_sets.t.prev);
-            upload_table(d, g, g.d_htx, sh_tx.slots, sh_tx.t.cur, sh_tx.t.prev);
-            upload_table(d, g, g.d_harena, sh_arena, t_sh_arena.cur, t_sh_arena.prev);
-            upload_table(d, g, g.d_hpool, sh_pool, t_sh_pool.cur, t_sh_pool.prev);
-            upload_table(d, g, g.d_hfx, sh_fx, t_sh_fx.cur, t_sh_fx.prev);
+            for_each_table([&](const auto& host, Track& t, DevBuf Image::*buf, bool upload) {
+                if (upload) upload_table(d, g, g.*buf, host, t.cur, t.prev);
+            });
             share_cursor_prepare(d, g, six_reset);
-            if (shape_keys) upload_table(d, g, g.d_fshape, fshape, t_fshape.cur, t_fshape.prev);
             flush_stage(d);
             // append-only arrays: upload the new tail (or all after a realloc)
             {
@@ -2736,35 +2623,7 @@ struct tm_engine {
         }
         // this commit's dirty pages become the "previous" set the other image
         // still needs at the next commit
-        struct Rot {
-            Dirty *cur, *prev;
-            size_t elems;
-        };
-        for (const Rot& r : {Rot{&node_dirty, &prev_node_dirty, nodes.size()},
-                             Rot{&cold.dirty, &prev_cold_dirty, cold.slots.size()},
-                             Rot{&hot.dirty, &prev_hot_dirty, hot.slots.size()},
-                             Rot{&dict_dirty, &prev_dict_dirty, dict.size()}}) {
-            *r.prev = *r.cur;
-            r.cur->clear();
-            r.cur->limit = std::max<size_t>(4096, r.elems / 16);
-        }
-        t_slots.rotate(rt_slots.size());
-        t_rarena.rotate(rt_arena.size());
-        t_rdest.rotate(rt_dest.size());
-        t_fr_meta.rotate(fr_meta.size());
-        t_rank_src.rotate(rank_src.size());
-        t_dt.rotate(dt.size());
-        t_rank_tg.rotate(rank_tg.size());
-        t_fshape.rotate(fshape.size());
-        t_sslots.rotate(sx_slots.size());
-        t_sarena.rotate(sx_arena.size());
-        t_spool.rotate(sx_pool.size());
-        t_fs_meta.rotate(fs_meta.size());
-        sh_sets.t.rotate(sh_sets.slots.size());
-        sh_tx.t.rotate(sh_tx.slots.size());
-        t_sh_arena.rotate(sh_arena.size());
-        t_sh_pool.rotate(sh_pool.size());
-        t_sh_fx.rotate(sh_fx.size());
+        for_each_table([](const auto& host, Track& t, DevBuf Image::*, bool) { t.rotate(host.size()); });
         dev_dirty = false;
         ++epoch;
         release_quarantine();   // also for engines that only take forced ids (never reach new_filter's release)
@@ -5009,45 +4868,33 @@ extern "C" int tm_debug_words(tm_engine* e, const uint8_t* bytes, const uint64_t
 // diagnostics (not part of include/topicmatch.h): the in-place route image
 // against the route bags it mirrors -- every topic found in the exact table
 // by the kernel's probe, its segment equal to its bag, its filter entry, the
-// labels strictly increasing in topic order, rank_src -- TM_OK or TM_EINVAL
-// with the first inconsistency in tm_last_error
+// labels strictly increasing in topic order, rank_src, the pool and arena
+// accounting -- TM_OK or TM_EINVAL with the first inconsistency in
+// tm_last_error
 extern "C" int tm_debug_check_routes(tm_engine* e) {
     return guarded(e, [&]() -> int {
         auto fail = [&](const std::string& what) -> int { throw ArgError("route image: " + what); };
-        size_t used = 0;
-        for (size_t s = 0; s < e->rt_slots.size(); ++s)
-            if (e->rt_slots[s].hash) {
-                ++used;
-                if (!e->rt_slot_rec[s] || e->rt_slot_rec[s]->slot != s) return fail("slot owner");
-            }
-        if (used != e->rt_used || used != e->route_bag.size()) return fail("slot count");
-        size_t total = 0;
+        check_exact_table(e->rt_slots, e->rt_arena, e->route_bag, fail);
+        size_t total = 0, live_cap = 0, live_words = 0;
         for (auto& kv : e->route_bag) {
             const tm_engine::RouteRec& r = kv.second;
             const uint8_t* t = reinterpret_cast<const uint8_t*>(kv.first.data());
             const uint32_t len = (uint32_t)kv.first.size();
             total += r.dests.size();
+            live_cap += r.cap;
+            live_words += r.words;
             if (r.key != &kv.first || r.dests.empty()) return fail("record of " + kv.first);
-            // the probe the kernel runs (routes.hip exact_lookup)
-            const uint64_t h = word_hash(t, len);
-            const size_t mask = e->rt_slots.size() - 1;
-            size_t s = h & mask;
-            while (e->rt_slots[s].hash && !(e->rt_slots[s].hash == h && e->rt_slots[s].len == len &&
-                                             std::memcmp(&e->rt_arena[e->rt_slots[s].arena / 8], t, len) == 0))
-                s = (s + 1) & mask;
-            if (!e->rt_slots[s].hash || s != r.slot) return fail("probe of " + kv.first);
-            const ExactSlot& x = e->rt_slots[s];
+            const ExactSlot& x = e->rt_slots.slots[r.slot];
             if (x.count != r.dests.size() || x.dest_off != r.off || x.rank != r.label) return fail("slot of " + kv.first);
-            if (len % 8 && (e->rt_arena[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) return fail("arena padding");
-            if (r.cap < r.dests.size() || (uint64_t)r.off + r.cap > e->rt_dest.size() ||
-                !std::equal(r.dests.begin(), r.dests.end(), e->rt_dest.begin() + r.off))
+            if (r.cap < r.dests.size() || (uint64_t)r.off + r.cap > e->rt_dest.v.size() ||
+                !std::equal(r.dests.begin(), r.dests.end(), e->rt_dest.v.begin() + r.off))
                 return fail("segment of " + kv.first);
             const bool wild = tm_topic_wildcard(t, len);
             const uint32_t fid = wild ? e->filter_of(t, len) : FILTER_NONE;
             if (r.fid != fid) return fail("filter link of " + kv.first);
             if (fid != FILTER_NONE) {
-                const uint4 m = e->fr_meta[fid];
-                if (m.x != r.off || m.y != r.dests.size() || m.z != r.label || e->fr_rec[fid] != &r)
+                const uint4 m = e->fr.meta[fid];
+                if (m.x != r.off || m.y != r.dests.size() || m.z != r.label || e->fr.rec[fid] != &r)
                     return fail("fr_meta of " + kv.first);
             }
             if (r.label >= e->rank_src.size() || e->rank_src[r.label] != (fid != FILTER_NONE ? fid : TM_ROUTE_TOPIC_ID))
@@ -5055,8 +4902,9 @@ extern "C" int tm_debug_check_routes(tm_engine* e) {
             if ((r.index != nullptr) != (r.dests.size() >= tm_engine::BAG_INDEX_MIN)) return fail("bag index");
         }
         if (total != e->route_total) return fail("route total");
-        for (size_t f = 0; f < e->fr_meta.size(); ++f)
-            if (e->fr_meta[f].y && (!e->fr_rec[f] || e->fr_rec[f]->fid != f)) return fail("stale fr_meta");
+        check_accounting(e->rt_dest, e->rt_arena, live_cap, live_words, fail);
+        for (size_t f = 0; f < e->fr.meta.size(); ++f)
+            if (e->fr.meta[f].y && (!e->fr.rec[f] || e->fr.rec[f]->fid != f)) return fail("stale fr_meta");
         if (e->rt_order.size() != e->route_bag.size()) return fail("order size");
         const tm_engine::RouteRec* prev = nullptr;
         for (const tm_engine::OrdKey& k : e->rt_order) {
@@ -5077,13 +4925,7 @@ extern "C" int tm_debug_check_routes(tm_engine* e) {
 extern "C" int tm_debug_check_subs(tm_engine* e) {
     return guarded(e, [&]() -> int {
         auto fail = [&](const std::string& what) -> int { throw ArgError("subscriber image: " + what); };
-        size_t used = 0;
-        for (size_t s = 0; s < e->sx_slots.size(); ++s)
-            if (e->sx_slots[s].hash) {
-                ++used;
-                if (!e->sx_slot_rec[s] || e->sx_slot_rec[s]->slot != s) return fail("slot owner");
-            }
-        if (used != e->sx_used || used != e->sub_bag.size()) return fail("slot count");
+        check_exact_table(e->sx_slots, e->sx_arena, e->sub_bag, fail);
         size_t total = 0, live_cap = 0, live_words = 0;
         for (auto& kv : e->sub_bag) {
             const tm_engine::SubRec& r = kv.second;
@@ -5093,40 +4935,30 @@ extern "C" int tm_debug_check_subs(tm_engine* e) {
             live_cap += r.cap;
             live_words += r.words;
             if (r.key != &kv.first || r.bag.empty()) return fail("record of " + kv.first);
-            // the probe the kernel runs (dispatch.hip sub_exact_lookup)
-            const uint64_t h = word_hash(t, len);
-            const size_t mask = e->sx_slots.size() - 1;
-            size_t s = h & mask;
-            while (e->sx_slots[s].hash && !(e->sx_slots[s].hash == h && e->sx_slots[s].len == len &&
-                                             std::memcmp(&e->sx_arena[e->sx_slots[s].arena / 8], t, len) == 0))
-                s = (s + 1) & mask;
-            if (!e->sx_slots[s].hash || s != r.slot) return fail("probe of " + kv.first);
-            const SubSlot& x = e->sx_slots[s];
+            const SubSlot& x = e->sx_slots.slots[r.slot];
             std::vector<uint32_t> plain;
             for (const auto& b : r.bag)
                 if (b.second == tm_engine::NO_GROUP) plain.push_back(b.first);
             if (plain.size() != r.n_plain) return fail("plain count of " + kv.first);
             if (x.n_plain != r.n_plain || x.n_all != r.bag.size() || x.seg != r.off) return fail("slot of " + kv.first);
-            if (len % 8 && (e->sx_arena[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) return fail("arena padding");
-            if (r.cap < r.n_plain || (uint64_t)r.off + r.cap > e->sx_pool.size() ||
-                !std::equal(plain.begin(), plain.end(), e->sx_pool.begin() + r.off))
+            if (r.cap < r.n_plain || (uint64_t)r.off + r.cap > e->sx_pool.v.size() ||
+                !std::equal(plain.begin(), plain.end(), e->sx_pool.v.begin() + r.off))
                 return fail("segment of " + kv.first);
             const bool wild = tm_topic_wildcard(t, len);
             const uint32_t fid = wild ? e->filter_of(t, len) : FILTER_NONE;
             if (r.fid != fid) return fail("filter link of " + kv.first);
             if (fid != FILTER_NONE) {
-                const uint4 m = e->fs_meta[fid];
-                if (m.x != r.off || m.y != r.n_plain || m.z != r.bag.size() || e->fs_rec[fid] != &r)
+                const uint4 m = e->fs.meta[fid];
+                if (m.x != r.off || m.y != r.n_plain || m.z != r.bag.size() || e->fs.rec[fid] != &r)
                     return fail("fs_meta of " + kv.first);
             }
             if ((r.index != nullptr) != (r.bag.size() >= tm_engine::BAG_INDEX_MIN)) return fail("bag index");
             if (r.index && r.index->size() != r.n_plain) return fail("bag index size");
         }
         if (total != e->sub_total) return fail("subscriber total");
-        if (live_cap + e->sx_pool_garbage != e->sx_pool.size()) return fail("pool accounting");
-        if (live_words + e->sx_arena_garbage != e->sx_arena.size()) return fail("arena accounting");
-        for (size_t f = 0; f < e->fs_meta.size(); ++f)
-            if ((e->fs_meta[f].y || e->fs_meta[f].z) && (!e->fs_rec[f] || e->fs_rec[f]->fid != f))
+        check_accounting(e->sx_pool, e->sx_arena, live_cap, live_words, fail);
+        for (size_t f = 0; f < e->fs.meta.size(); ++f)
+            if ((e->fs.meta[f].y || e->fs.meta[f].z) && (!e->fs.rec[f] || e->fs.rec[f]->fid != f))
                 return fail("stale fs_meta");
         return TM_OK;
     });
@@ -5143,6 +4975,7 @@ extern "C" int tm_debug_check_subs(tm_engine* e) {
 extern "C" int tm_debug_check_shares(tm_engine* e) {
     return guarded(e, [&]() -> int {
         auto fail = [&](const std::string& what) -> int { throw ArgError("share image: " + what); };
+        check_exact_table(e->sh_tx, e->sh_arena, e->sh_topics, fail);
         size_t total = 0, n_sets = 0, live_cap = 0, live_words = 0, linked = 0;
         std::unordered_set<uint32_t> six_seen, xid_seen;
         for (auto& kv : e->sh_topics) {
@@ -5154,25 +4987,13 @@ extern "C" int tm_debug_check_shares(tm_engine* e) {
             if (tp.fid != (tp.wild ? e->filter_of(t, len) : FILTER_NONE)) return fail("filter link of " + kv.first);
             if (tp.fid != FILTER_NONE) {
                 ++linked;
-                auto fi = e->sh_fid_topic.find(tp.fid);
-                if (fi == e->sh_fid_topic.end() || fi->second != &tp) return fail("filter index of " + kv.first);
-                if (tp.fid >= e->sh_fx.size() || e->sh_fx[tp.fid] != tp.xid) return fail("fx of " + kv.first);
+                if (e->sh_fx.owner(tp.fid) != &tp) return fail("filter index of " + kv.first);
+                if (e->sh_fx.meta[tp.fid] != tp.xid) return fail("fx of " + kv.first);
             }
-            {
-                live_words += tp.words;
-                if (!xid_seen.insert(tp.xid).second || tp.xid >= e->sh_next_xid) return fail("xid of " + kv.first);
-                // the probe the kernel runs (share.hip share_topic_lookup)
-                const uint64_t h = word_hash(t, len);
-                const size_t mask = e->sh_tx.slots.size() - 1;
-                size_t s = h & mask;
-                while (e->sh_tx.slots[s].hash && !(e->sh_tx.slots[s].hash == h && e->sh_tx.slots[s].len == len &&
-                                                    std::memcmp(&e->sh_arena[e->sh_tx.slots[s].arena / 8], t, len) == 0))
-                    s = (s + 1) & mask;
-                const ShareTopicSlot& x = e->sh_tx.slots[s];
-                if (!x.hash || s != tp.slot || e->sh_tx.rec[s] != &tp) return fail("probe of " + kv.first);
-                if (x.xid != tp.xid || x.arena != tp.arena * 8) return fail("slot of " + kv.first);
-                if (len % 8 && (e->sh_arena[x.arena / 8 + len / 8] >> (8 * (len % 8))) != 0) return fail("arena padding");
-            }
+            live_words += tp.words;
+            if (!xid_seen.insert(tp.xid).second || tp.xid >= e->sh_next_xid) return fail("xid of " + kv.first);
+            const ShareTopicSlot& tx = e->sh_tx.slots[tp.slot];
+            if (tx.xid != tp.xid || tx.arena != tp.arena * 8) return fail("slot of " + kv.first);
             for (auto& sk : tp.sets) {
                 const tm_engine::ShareSet& st = *sk.second;
                 if (st.topic != &tp || st.tg != sk.first || st.members.empty()) return fail("set of " + kv.first);
@@ -5181,8 +5002,8 @@ extern "C" int tm_debug_check_shares(tm_engine* e) {
                 total += st.members.size();
                 live_cap += st.cap;
                 if (!six_seen.insert(st.six).second || st.six >= e->sh_next_six) return fail("set index of " + kv.first);
-                if (st.cap < st.members.size() || (uint64_t)st.off + st.cap > e->sh_pool.size() ||
-                    !std::equal(st.members.begin(), st.members.end(), e->sh_pool.begin() + st.off))
+                if (st.cap < st.members.size() || (uint64_t)st.off + st.cap > e->sh_pool.v.size() ||
+                    !std::equal(st.members.begin(), st.members.end(), e->sh_pool.v.begin() + st.off))
                     return fail("segment of " + kv.first);
                 std::unordered_set<uint32_t> uniq(st.members.begin(), st.members.end());
                 if (uniq.size() != st.members.size()) return fail("duplicate member in " + kv.first);
@@ -5210,24 +5031,22 @@ extern "C" int tm_debug_check_shares(tm_engine* e) {
         }
         if (indexed != total) return fail("member index size");
         if (n_sets != e->sh_sets.used || e->sh_topics.size() != e->sh_tx.used) return fail("table counts");
-        if (linked != e->sh_fid_topic.size()) return fail("filter index size");
-        for (size_t f = 0; f < e->sh_fx.size(); ++f)
-            if (e->sh_fx[f] != tm_engine::SLOT_NONE && !e->sh_fid_topic.count((uint32_t)f)) return fail("stale fx");
         size_t used = 0;
+        for (size_t f = 0; f < e->sh_fx.meta.size(); ++f) {
+            if (e->sh_fx.rec[f]) ++used;
+            if (e->sh_fx.meta[f] != tm_engine::SLOT_NONE && !e->sh_fx.rec[f]) return fail("stale fx");
+        }
+        if (linked != used) return fail("filter index size");
+        used = 0;
         for (size_t s = 0; s < e->sh_sets.slots.size(); ++s)
             if (e->sh_sets.slots[s].count) ++used;
         if (used != e->sh_sets.used) return fail("set slots in use");
-        used = 0;
-        for (size_t s = 0; s < e->sh_tx.slots.size(); ++s)
-            if (e->sh_tx.slots[s].hash) ++used;
-        if (used != e->sh_tx.used) return fail("topic slots in use");
         for (uint32_t i : e->sh_free_six)
             if (!six_seen.insert(i).second) return fail("free set index in use");
         for (auto& q : e->sh_six_quarantine)
             if (!six_seen.insert(q.second).second) return fail("quarantined set index in use");
         if (six_seen.size() != e->sh_next_six) return fail("set index accounting");
-        if (live_cap + e->sh_pool_garbage != e->sh_pool.size()) return fail("pool accounting");
-        if (live_words + e->sh_arena_garbage != e->sh_arena.size()) return fail("arena accounting");
+        check_accounting(e->sh_pool, e->sh_arena, live_cap, live_words, fail);
         return TM_OK;
     });
 }

@@ -142,6 +142,9 @@ struct ImageView {
 // itself) through an exact-topic hash table whose keys are verified byte for
 // byte against the topic arena (8-aligned, zero padded).  The host patches
 // all of it in place per add / del (engine.cpp, route image maintenance).
+// The three images below share their parts: the exact-topic table is a
+// MirrorTable on the host (engine.cpp) and is probed by exact_find on the
+// device (device_bytes.h); its slots begin {hash, len, <u32>, arena}.
 constexpr uint32_t TM_ROUTE_TOPIC_ID = 0xFFFFFFFFu;   // route source = the literal topic
 
 struct alignas(32) ExactSlot {
@@ -151,7 +154,10 @@ struct alignas(32) ExactSlot {
     uint64_t arena;        // topic bytes in the arena
     uint32_t dest_off;     // first route's dest in the dest pool
     uint32_t rank;         // to_rank of the topic (aggre)
+    bool empty() const { return hash == 0; }
+    uint64_t home() const { return hash; }
 };
+static_assert(sizeof(ExactSlot) == 32, "exact-topic slot is one 32 B half line");
 
 struct RouteView {
     const uint4*     fr_meta;       // n_filters: {dest offset, count, to_rank, 0} (count 0: no routes)
@@ -177,8 +183,8 @@ struct AggreView {
 // with subscribers owns a segment of one pool of plain subscriber ids (bag
 // order, shared entries left out: dispatch/2 only counts those).  The bag of
 // a trie filter is found by its filter id (fs_meta), the bag of any topic by
-// its bytes through an exact-topic table of its own, laid out and probed like
-// the route image's and byte-verified against its own arena.
+// its bytes through an exact-topic table of its own (MirrorTable / exact_find,
+// as the route image's), byte-verified against its own arena.
 constexpr uint32_t TM_NOT_LOCAL_ID = 0xFFFFFFFFu;   // ndisp of a delivery that is not the local node's
 
 struct alignas(32) SubSlot {
@@ -188,7 +194,10 @@ struct alignas(32) SubSlot {
     uint64_t arena;        // topic bytes in the arena
     uint32_t seg;          // first plain subscriber in the pool
     uint32_t n_all;        // bag size, shared entries included
+    bool empty() const { return hash == 0; }
+    uint64_t home() const { return hash; }
 };
+static_assert(sizeof(SubSlot) == 32, "exact-topic slot is one 32 B half line");
 
 struct SubView {
     const uint4*    fs_meta;        // n_filters: {segment, n_plain, n_all, 0}
@@ -206,9 +215,8 @@ struct SubView {
 // compared exactly.  The To key is a dense id (xid) of the set's topic: found
 // by a trie filter's id through fx (which follows the id's lifetime as
 // fs_meta does), and for To = the publish topic itself by its bytes through
-// an exact-topic table of this image (laid out, probed and byte-verified like
-// the subscriber image's; it holds every topic with a set, as that one
-// does).  Each set owns a segment of one member pool, in list (insertion)
+// an exact-topic table of this image (MirrorTable / exact_find again; it
+// holds every topic with a set, as the subscriber image's does).  Each set owns a segment of one member pool, in list (insertion)
 // order, and a set index: the slot of its round-robin cursor, which lives
 // outside the image epochs (one array per replica).
 constexpr uint32_t TM_NO_MEMBER_ID = 0xFFFFFFFFu;   // pick of a delivery without a member
@@ -222,6 +230,7 @@ struct alignas(32) ShareTopicSlot {
     bool empty() const { return hash == 0; }
     uint64_t home() const { return hash; }
 };
+static_assert(sizeof(ShareTopicSlot) == 32, "exact-topic slot is one 32 B half line");
 
 struct alignas(32) ShareSetSlot {
     uint32_t tg;           // group target id
@@ -233,6 +242,7 @@ struct alignas(32) ShareSetSlot {
     bool empty() const { return count == 0; }
     inline uint64_t home() const;
 };
+static_assert(sizeof(ShareSetSlot) == 32, "share set slot is one 32 B half line");
 
 struct ShareView {
     const ShareSetSlot*   sets;      // power-of-two table, count 0 = empty

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
+#include "device_bytes.h"
 
 namespace tmx {
 
@@ -72,37 +73,6 @@ __device__ __forceinline__ void wave_sync_lds() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// ---------------------------------------------------------------------------
-// byte access: aligned 8-byte words (an aligned word holding a valid byte
-// never crosses a page), little-endian extraction.  Topic bytes are read
-// either from global memory or from a wave's LDS window (tm_tokenize stages
-// the bytes of its 64 topics with coalesced loads first).
-struct GlobalBytes {
-    const uint8_t* p;
-    __device__ __forceinline__ uint64_t word(uint64_t q) const {
-        return *reinterpret_cast<const uint64_t*>(p + (q & ~7ull));
-    }
-    __device__ __forceinline__ uint32_t byte(uint64_t q) const { return p[q]; }
-};
-struct LdsBytes {
-    const uint64_t* w;   // LDS words of bytes [base, ...), base 8-aligned
-    uint64_t base;
-    __device__ __forceinline__ uint64_t word(uint64_t q) const { return w[(q - base) >> 3]; }
-    __device__ __forceinline__ uint32_t byte(uint64_t q) const {
-        return (uint32_t)(word(q) >> (8 * (q & 7))) & 0xFFu;
-    }
-};
-
-// assemble up to 8 bytes [p, p+k) (k in 1..8) little-endian, zero padded
-template <class B>
-__device__ __forceinline__ uint64_t load_chunk(const B& bytes, uint64_t p, uint32_t k) {
-    uint32_t sh = (uint32_t)(p & 7) * 8;
-    uint64_t v = bytes.word(p) >> sh;
-    if (sh != 0 && (p & 7) + k > 8) v |= bytes.word(p + 8) << (64 - sh);
-    if (k < 8) v &= (~0ull) >> (64 - 8 * k);
-    return v;
-}
-
 // dictionary lookup of topic bytes [p, p+len): word id, WORD_PLUS/HASH for the
 // atoms '+' / '#', or WORD_NONE (bytes no filter contains: match only '+'/'#').
 // Split in two so the tokenizer can issue a level's slot load (dict_begin),
@@ -119,12 +89,7 @@ __device__ __forceinline__ DictProbe dict_begin(const ImageView& im, const B& by
     DictProbe q;
     q.rel = (uint32_t)(p - b);
     q.len = len;
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = 0; i < len; i += 8) {
-        uint32_t k = len - i < 8 ? len - i : 8;
-        h = word_hash_step(h, load_chunk(bytes, p + i, k));
-    }
-    h = word_hash_final(h, len);
+    const uint64_t h = topic_hash(bytes, p, len);
     q.tag = dict_tag(h, len);
     q.s = (uint32_t)(h & im.dict_slot_mask);
     q.d0 = reinterpret_cast<const uint4*>(im.dict + q.s)[0];
@@ -168,27 +133,6 @@ __device__ __forceinline__ uint32_t dict_end(const ImageView& im, const B& bytes
         s = (s + 1) & im.dict_slot_mask;
         d0 = reinterpret_cast<const uint4*>(im.dict + s)[0];
     }
-}
-
-// ---------------------------------------------------------------------------
-// block scan helper (u64, BLOCK threads)
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t x, uint64_t* lds, uint64_t& total) {
-    int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        uint64_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) lds[wid] = inc;
-    __syncthreads();
-    uint64_t wpre = 0, tot = 0;
-    for (int i = 0; i < BLOCK / 64; ++i) {
-        if (i < wid) wpre += lds[i];
-        tot += lds[i];
-    }
-    __syncthreads();
-    total = tot;
-    return wpre + inc - x;
 }
 
 // exact per-byte '/' test of an 8-byte word: 0x80 in each byte that is '/'.
@@ -1722,7 +1666,7 @@ tm_copy_out(ImageView im, const uint64_t* __restrict__ off, uint32_t n, const ui
     const uint32_t tn = n - t0 < (uint32_t)BLOCK ? n - t0 : (uint32_t)BLOCK;
     const uint32_t c = threadIdx.x < tn ? counts[t0 + threadIdx.x] : 0u;
     uint64_t agg;
-    const uint64_t ex = block_exclusive_scan(c, lds_scan, agg);
+    const uint64_t ex = block_exclusive_scan<BLOCK>(c, lds_scan, agg);
     lds_inc[threadIdx.x] = (uint32_t)(ex + c);
     __syncthreads();
     const uint64_t base = out_off[t0];
@@ -1944,7 +1888,7 @@ tm_scan_reduce(const uint32_t* __restrict__ in, uint32_t n, uint64_t* __restrict
         if (k < n) s += in[k];
     }
     uint64_t tot;
-    block_exclusive_scan(s, lds, tot);
+    block_exclusive_scan<BLOCK>(s, lds, tot);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
 }
 
@@ -1956,7 +1900,7 @@ tm_scan_tiles(uint64_t* __restrict__ tile_sums, uint32_t n_tiles) {
         uint32_t k = b + threadIdx.x;
         uint64_t x = k < n_tiles ? tile_sums[k] : 0;
         uint64_t tot;
-        uint64_t ex = block_exclusive_scan(x, lds, tot);
+        uint64_t ex = block_exclusive_scan<BLOCK>(x, lds, tot);
         if (k < n_tiles) tile_sums[k] = carry + ex;
         carry += tot;
     }
@@ -1976,7 +1920,7 @@ tm_scan_final(const uint32_t* __restrict__ in, uint32_t n, const uint64_t* __res
         s += v[i];
     }
     uint64_t tot;
-    uint64_t ex = block_exclusive_scan(s, lds, tot) + tile_pre[blockIdx.x];
+    uint64_t ex = block_exclusive_scan<BLOCK>(s, lds, tot) + tile_pre[blockIdx.x];
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) {
         uint64_t k = base + i;
@@ -2065,7 +2009,7 @@ tm_scan_single(const uint32_t* __restrict__ in, uint32_t n, uint64_t* __restrict
             s += v[i];
         }
         uint64_t tot;
-        uint64_t ex = block_exclusive_scan(s, lds, tot) + carry;
+        uint64_t ex = block_exclusive_scan<BLOCK>(s, lds, tot) + carry;
 #pragma unroll
         for (int i = 0; i < SCAN_ITEMS; ++i) {
             const uint64_t k = base + i;

@@ -19,22 +19,13 @@
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
+#include "device_bytes.h"
 
 namespace tmx {
 
 namespace {
 
 constexpr int RB = 256;   // threads per block of the routing kernels
-
-// little-endian bytes [p, p+k) (k in 1..8) of an 8-byte-readable buffer
-__device__ __forceinline__ uint64_t chunk_at(const uint8_t* b, uint64_t p, uint32_t k) {
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(b + (p & ~7ull));
-    const uint32_t sh = (uint32_t)(p & 7) * 8;
-    uint64_t v = w[0] >> sh;
-    if (sh && (p & 7) + k > 8) v |= w[1] << (64 - sh);
-    if (k < 8) v &= (~0ull) >> (64 - 8 * k);
-    return v;
-}
 
 // the owner shard of topic [b, e): word hash of its first `depth` levels
 __device__ __forceinline__ uint32_t topic_owner(const uint8_t* bytes, uint64_t b, uint64_t e, uint32_t depth,
@@ -48,9 +39,7 @@ __device__ __forceinline__ uint32_t topic_owner(const uint8_t* bytes, uint64_t b
         }
     }
     const uint32_t len = (uint32_t)(cut - b);
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = 0; i < len; i += 8) h = word_hash_step(h, chunk_at(bytes, b + i, len - i < 8 ? len - i : 8));
-    return route_shard(word_hash_final(h, len), S);
+    return route_shard(topic_hash(GlobalBytes{bytes}, b, len), S);
 }
 
 __global__ void __launch_bounds__(RB)
@@ -155,7 +144,7 @@ tm_route_bytes(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ o
     const uint64_t b = off[t], len = off[t + 1] - b, d = soff[p];
     for (uint64_t i = 0; i < len; i += 8) {
         const uint32_t k = len - i < 8 ? (uint32_t)(len - i) : 8u;
-        const uint64_t v = chunk_at(bytes, b + i, k);
+        const uint64_t v = load_chunk(GlobalBytes{bytes}, b + i, k);
         for (uint32_t j = 0; j < k; ++j) sbuf[d + i + j] = (uint8_t)(v >> (8 * j));
     }
 }

@@ -22,65 +22,18 @@
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
+#include "device_bytes.h"
 
 namespace tmx {
 
 constexpr int RBLOCK = 256;
 
-__device__ __forceinline__ uint64_t r_load_u64_aligned(const uint8_t* base, uint64_t p) {
-    return *reinterpret_cast<const uint64_t*>(base + (p & ~7ull));
-}
-// bytes [p, p+k) (k in 1..8) little-endian, zero padded
-__device__ __forceinline__ uint64_t r_load_chunk(const uint8_t* base, uint64_t p, uint32_t k) {
-    const uint32_t sh = (uint32_t)(p & 7) * 8;
-    uint64_t v = r_load_u64_aligned(base, p) >> sh;
-    if (sh != 0 && (p & 7) + k > 8) v |= r_load_u64_aligned(base, p + 8) << (64 - sh);
-    if (k < 8) v &= (~0ull) >> (64 - 8 * k);
-    return v;
-}
-
 // get_routes(Topic) (emqx_router.erl:89-90): the exact-topic table slot of
 // topic bytes [p, p+len), byte-verified; returns (dest offset, count, to_rank)
 __device__ __forceinline__ uint4 exact_lookup(const RouteView& rv, const uint8_t* bytes, uint64_t p, uint32_t len) {
-    if (!rv.ex_slots) return make_uint4(0, 0, 0, 0);
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = 0; i < len; i += 8) {
-        const uint32_t k = len - i < 8 ? len - i : 8;
-        h = word_hash_step(h, r_load_chunk(bytes, p + i, k));
-    }
-    h = word_hash_final(h, len);
-    for (uint64_t s = h & rv.ex_slot_mask;; s = (s + 1) & rv.ex_slot_mask) {
-        const ExactSlot e = rv.ex_slots[s];
-        if (e.hash == 0) return make_uint4(0, 0, 0, 0);
-        if (e.hash == h && e.len == len) {
-            const uint64_t* a = reinterpret_cast<const uint64_t*>(rv.ex_arena + e.arena);
-            bool eq = true;
-            for (uint32_t i = 0; i < len && eq; i += 8) {
-                const uint32_t k = len - i < 8 ? len - i : 8;
-                eq = r_load_chunk(bytes, p + i, k) == a[i >> 3];
-            }
-            if (eq) return make_uint4(e.dest_off, e.count, e.rank, 0);
-        }
-    }
-}
-
-__device__ __forceinline__ uint64_t r_block_exclusive_scan(uint64_t x, uint64_t* lds, uint64_t& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) lds[wid] = inc;
-    __syncthreads();
-    uint64_t wpre = 0, tot = 0;
-    for (int i = 0; i < RBLOCK / 64; ++i) {
-        if (i < wid) wpre += lds[i];
-        tot += lds[i];
-    }
-    __syncthreads();
-    total = tot;
-    return wpre + inc - x;
+    ExactSlot e{};   // a miss leaves it zero
+    if (rv.ex_slots) exact_find(rv.ex_slots, rv.ex_slot_mask, rv.ex_arena, GlobalBytes{bytes}, p, len, e);
+    return make_uint4(e.dest_off, e.count, e.rank, 0);
 }
 
 // local topic of id j of the block: lds_inc holds the inclusive id prefix of
@@ -108,7 +61,7 @@ tm_route_count(RouteView rv, const uint8_t* __restrict__ bytes, const uint64_t* 
     const uint32_t t = t0 + threadIdx.x;
     const uint32_t c = threadIdx.x < tn ? counts[t] : 0u;
     uint64_t agg;
-    const uint64_t ex = r_block_exclusive_scan(c, lds_scan, agg);
+    const uint64_t ex = block_exclusive_scan<RBLOCK>(c, lds_scan, agg);
     lds_inc[threadIdx.x] = (uint32_t)(ex + c);
     lds_mr[threadIdx.x] = 0;
     uint4 xe = make_uint4(0, 0, 0, 0);
@@ -143,12 +96,12 @@ tm_route_emit(RouteView rv, AggreView av, uint32_t n, const uint32_t* __restrict
     const uint32_t t = t0 + threadIdx.x;
     const uint32_t c = threadIdx.x < tn ? counts[t] : 0u;
     uint64_t agg;
-    const uint64_t ex = r_block_exclusive_scan(c, lds_scan, agg);
+    const uint64_t ex = block_exclusive_scan<RBLOCK>(c, lds_scan, agg);
     lds_inc[threadIdx.x] = (uint32_t)(ex + c);
     const uint4 xe = threadIdx.x < tn ? exact[t] : make_uint4(0, 0, 0, 0);
     const uint32_t mr = threadIdx.x < tn ? rcount[t] - xe.y : 0u;
     uint64_t magg;
-    lds_m[threadIdx.x] = r_block_exclusive_scan(mr, lds_scan, magg);
+    lds_m[threadIdx.x] = block_exclusive_scan<RBLOCK>(mr, lds_scan, magg);
     if (threadIdx.x < tn) {   // get_routes(Topic): the literal topic's routes first
         const uint64_t o = out_off[t];
         const uint64_t xr = (uint64_t)xe.z << 32;
@@ -177,7 +130,7 @@ tm_route_emit(RouteView rv, AggreView av, uint32_t n, const uint32_t* __restrict
             }
         }
         uint64_t chunk;
-        const uint64_t r = carry + r_block_exclusive_scan(rc, lds_scan, chunk);
+        const uint64_t r = carry + block_exclusive_scan<RBLOCK>(rc, lds_scan, chunk);
         if (rc) {
             const uint32_t tl = t0 + lo;
             const uint64_t pos = out_off[tl] + exact[tl].y + (r - lds_m[lo]);

@@ -36,69 +36,21 @@
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
+#include "device_bytes.h"
 
 namespace tmx {
 
 constexpr int HBLOCK = 256;
 
-__device__ __forceinline__ uint64_t h_load_u64_aligned(const uint8_t* base, uint64_t p) {
-    return *reinterpret_cast<const uint64_t*>(base + (p & ~7ull));
-}
-// bytes [p, p+k) (k in 1..8) little-endian, zero padded
-__device__ __forceinline__ uint64_t h_load_chunk(const uint8_t* base, uint64_t p, uint32_t k) {
-    const uint32_t sh = (uint32_t)(p & 7) * 8;
-    uint64_t v = h_load_u64_aligned(base, p) >> sh;
-    if (sh != 0 && (p & 7) + k > 8) v |= h_load_u64_aligned(base, p + 8) << (64 - sh);
-    if (k < 8) v &= (~0ull) >> (64 - 8 * k);
-    return v;
-}
-
 // the To key of an exact topic by its bytes [p, p+len): the share image's
-// exact table, byte-verified (as dispatch.hip sub_exact_lookup); false when
+// exact table, byte-verified (device_bytes.h exact_find); false when
 // no set is on that topic
 __device__ __forceinline__ bool share_topic_lookup(const ShareView& hv, const uint8_t* bytes, uint64_t p, uint32_t len,
                                                    uint32_t& xid) {
-    uint64_t h = 0x243F6A8885A308D3ULL;
-    for (uint32_t i = 0; i < len; i += 8) {
-        const uint32_t k = len - i < 8 ? len - i : 8;
-        h = word_hash_step(h, h_load_chunk(bytes, p + i, k));
-    }
-    h = word_hash_final(h, len);
-    for (uint64_t s = h & hv.tx_mask;; s = (s + 1) & hv.tx_mask) {
-        const ShareTopicSlot e = hv.tx_slots[s];
-        if (e.hash == 0) return false;
-        if (e.hash == h && e.len == len) {
-            const uint64_t* a = reinterpret_cast<const uint64_t*>(hv.tx_arena + e.arena);
-            bool eq = true;
-            for (uint32_t i = 0; i < len && eq; i += 8) {
-                const uint32_t k = len - i < 8 ? len - i : 8;
-                eq = h_load_chunk(bytes, p + i, k) == a[i >> 3];
-            }
-            if (eq) {
-                xid = e.xid;
-                return true;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ uint64_t h_block_exclusive_scan(uint64_t x, uint64_t* lds, uint64_t& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-    }
-    if (lane == 63) lds[wid] = inc;
-    __syncthreads();
-    uint64_t wpre = 0, tot = 0;
-    for (int i = 0; i < HBLOCK / 64; ++i) {
-        if (i < wid) wpre += lds[i];
-        tot += lds[i];
-    }
-    __syncthreads();
-    total = tot;
-    return wpre + inc - x;
+    ShareTopicSlot e;
+    if (!exact_find(hv.tx_slots, hv.tx_mask, hv.tx_arena, GlobalBytes{bytes}, p, len, e)) return false;
+    xid = e.xid;
+    return true;
 }
 
 // lookup over blocks of 256 topics (the slot walk of dispatch.hip
@@ -119,7 +71,7 @@ tm_share_lookup(ShareView hv, uint32_t local_target, const uint8_t* __restrict__
     const uint32_t t = t0 + threadIdx.x;
     const uint64_t span = threadIdx.x < tn ? aoff[t + 1] - aoff[t] : 0ull;
     uint64_t agg;
-    const uint64_t ex = h_block_exclusive_scan(span, lds_scan, agg);
+    const uint64_t ex = block_exclusive_scan<HBLOCK>(span, lds_scan, agg);
     lds_inc[threadIdx.x] = ex + span;
     __syncthreads();
     const uint64_t base = aoff[t0];

@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import byte_corpus as C  # noqa: E402
-from dispatch_ref import SubscriberBag  # noqa: E402
+from dispatch_ref import SubscriberBag, route_dispatch  # noqa: E402
 from shared_ref import NO_MEMBER, SharedSub as RefShared, route_shared  # noqa: E402
 from emqx_amd import Engine  # noqa: E402
 from emqx_amd import _lib as L  # noqa: E402
@@ -504,4 +504,62 @@ def test_shared_filter_id_reuse_on_the_device(gpu_device):
     assert got.picks == [(b"b/#", b"g", None)]
     w.route(b"a/+", ("g", "n1"))
     _both(w, [b"a/x", b"b/x"], random.Random(4))
+    w.close()
+
+
+# ---- every mirrored table through both image epochs ---------------------------------------------
+
+def test_one_small_delta_per_commit_reaches_both_image_epochs(gpu_device):
+    """double_buffer 1: eight consecutive commits, each after exactly one small
+    delta -- a route, a plain subscriber, a share member, a trie filter deleted
+    and re-inserted behind the tables (a new filter id: nodes, edges, fr_meta,
+    fs_meta and fx all move), twice over.  Each commit writes the image epoch
+    that missed the previous commit, from that commit's dirty log and this
+    one's (a few elements of tables of dozens: the scatter path), so a host
+    table left out of the commit's upload or rotation shows as a stale
+    delivery, Count, pair or pick.  After every commit a 64-topic publish
+    equals the oracle's."""
+    rng = random.Random(9)
+    w = World(gpu_device)
+    w.e.set_option("double_buffer", 1)
+    wild = [b"a/+", b"a/#", b"+/b", b"#", b"c/+/d", b"c/#", b"+/+", b"d/+", b"a/b/#", b"+/c/+", b"e/#", b"e/+"]
+    exact = [b"t/%d" % i for i in range(20)] + [b"a/b", b"c/x/d", b"e/f", b"d"]
+    for i, f in enumerate(wild + exact):
+        w.route(f, "n1")
+        w.e.sub_add(f, 100 + i)
+        w.bag.insert_subscriber(None, f, 100 + i)
+        if i % 2 == 0:
+            g = (b"g1", b"g2")[i // 2 % 2]
+            w.route(f, (g.decode(), "n1"))
+            w.members(g, f, [300 + 3 * i, 301 + 3 * i, 302 + 3 * i][:1 + i % 3])
+    topics = (exact + [b"a/c", b"x/b", b"c/y/d", b"c/z", b"q/r", b"d/e", b"a/b/c", b"z/c/z", b"e/g", b"e", b"q"] +
+              _topics(rng, 64))[:64]
+    assert len(topics) == 64
+
+    def check(tag):
+        w.e.commit()
+        for tp, pub in zip(topics, w.b.publish_many(topics)):
+            counts, pairs = route_dispatch(w.o, w.bag, b"n1", tp)
+            assert [(d.to, d.target) for d in pub.deliveries] == w.o.match_deliveries(tp), (tag, tp)
+            assert [d.count for d in pub.deliveries] == counts, (tag, tp)
+            assert pub.pairs == pairs, (tag, tp)
+        stats = _both(w, topics, rng, tag)
+        assert stats.get(2, 0) > 0 and stats.get(1, 0) > 0, stats
+
+    check("built")
+    check("second epoch")
+    for k in range(2):
+        w.route(wild[k], "n2")                                   # one route
+        check(("route", k))
+        w.e.sub_add(exact[k], 900 + k)                           # one plain subscriber
+        w.bag.insert_subscriber(None, exact[k], 900 + k)
+        check(("subscriber", k))
+        w.member((b"g1", b"g2")[k], wild[2 * k], 500 + k)        # one share member
+        check(("member", k))
+        w.e.delete(wild[4 + k])                                  # one trie filter, behind the tables
+        w.e.insert(wild[4 + k])
+        check(("filter", k))
+    w.e.debug_check_routes()
+    w.e.debug_check_subs()
+    w.e.debug_check_shares()
     w.close()

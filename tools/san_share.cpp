@@ -1,9 +1,13 @@
-// san_share — drives the tm_share_* host calls on a host-only engine (device
-// -1) for a sanitizer build of engine.cpp: adds, deletes, member-down, filters
-// created and deleted behind the table, set-index / xid recycling, table
-// regrowth and pool / arena compaction, with tm_debug_check_shares after each
-// phase.  Build and run: make san_share (host code under
-// -fsanitize=address,undefined; the kernels are linked as built, never run).
+// san_share — drives the tm_route_*, tm_sub_* and tm_share_* host calls on a
+// host-only engine (device -1) for a sanitizer build of engine.cpp.  The three
+// images share their table code (MirrorTable, TopicArena, SegPool, compact,
+// FilterLink), so each goes through the same phases with option "route_gc"
+// small: adds, filters created and deleted behind the tables, deletes
+// (member-down for the shares), table regrowth, pool / arena compaction,
+// emptied and refilled (every slot, set index and xid recycled) -- with
+// tm_debug_check_routes / _subs / _shares after each phase.  Build and run:
+// make san_share (host code under -fsanitize=address,undefined; the kernels
+// are linked as built, never run).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +16,8 @@
 
 #include "../include/topicmatch.h"
 
+extern "C" int tm_debug_check_routes(tm_engine* e);
+extern "C" int tm_debug_check_subs(tm_engine* e);
 extern "C" int tm_debug_check_shares(tm_engine* e);
 
 static tm_engine* E;
@@ -24,9 +30,12 @@ static void ok(int rc, const char* what) {
 static void phase(const char* name) {
     uint64_t ep = 0;
     ok(tm_commit(E, &ep), "tm_commit");
+    ok(tm_debug_check_routes(E), name);
+    ok(tm_debug_check_subs(E), name);
     ok(tm_debug_check_shares(E), name);
-    std::printf("%-28s ok: %llu records, epoch %llu\n", name, (unsigned long long)tm_share_count(E),
-                (unsigned long long)ep);
+    std::printf("%-28s ok: %llu routes, %llu subscribers, %llu share records, epoch %llu\n", name,
+                (unsigned long long)tm_route_count(E), (unsigned long long)tm_sub_count(E),
+                (unsigned long long)tm_share_count(E), (unsigned long long)ep);
 }
 static const uint8_t* u8(const std::string& s) { return reinterpret_cast<const uint8_t*>(s.data()); }
 
@@ -45,40 +54,104 @@ int main() {
     for (int i = 0; i < 12; ++i) topics.push_back("w/" + std::to_string(i) + "/+");
     topics.push_back("#");
     topics.push_back(std::string("a\0b", 3));
+    // ---- shares ----
     for (int round = 0; round < 6; ++round) {
         for (int i = 0; i < 3000; ++i) {   // adds (duplicates included)
             const std::string &g = groups[rnd(4)], &t = topics[rnd((uint32_t)topics.size())];
             ok(tm_share_add(E, u8(g), (uint32_t)g.size(), u8(t), (uint32_t)t.size(), rnd(200)), "tm_share_add");
         }
-        phase("adds");
+        phase("share adds");
         for (int i = 0; i < 12; i += 2) {   // filters behind the table's back
             const std::string& f = topics[40 + i];
             ok(round % 2 ? tm_delete(E, u8(f), (uint32_t)f.size()) : tm_insert(E, u8(f), (uint32_t)f.size()), "filter");
         }
-        phase("filters");
+        phase("share filters");
         for (int i = 0; i < 2500; ++i) {   // deletes (absent records included)
             const std::string &g = groups[rnd(4)], &t = topics[rnd((uint32_t)topics.size())];
             uint32_t left = 0;
             ok(tm_share_del(E, u8(g), (uint32_t)g.size(), u8(t), (uint32_t)t.size(), rnd(200), &left), "tm_share_del");
         }
-        phase("deletes");
+        phase("share deletes");
         for (uint32_t m = round; m < 200; m += 3) {
             uint32_t gone = 0;
             ok(tm_share_member_down(E, m, &gone), "tm_share_member_down");
         }
-        phase("member_down");
+        phase("share member_down");
         uint32_t out[8], n = 0;
         const int rc = tm_share_members(E, u8(groups[0]), 2, u8(topics.back()), 3, out, 8, &n);
         if (rc != TM_OK && rc != TM_ENOSPC) ok(rc, "tm_share_members");
     }
     for (uint32_t m = 0; m < 200; ++m) ok(tm_share_member_down(E, m, nullptr), "tm_share_member_down");
-    phase("emptied");
+    phase("share emptied");
     if (tm_share_count(E) != 0) return 1;
     for (int i = 0; i < 500; ++i) {   // every index and xid recycled
         const std::string& t = topics[rnd((uint32_t)topics.size())];
         ok(tm_share_add(E, u8(groups[1]), 2, u8(t), (uint32_t)t.size(), rnd(50)), "tm_share_add");
     }
-    phase("refilled");
+    phase("share refilled");
+
+    // ---- routes and subscribers ----
+    // more topics than the tables' first 16 slots hold several times over
+    // (regrowth); wildcard topics w/i/+ get their filters from tm_route_add
+    // (routes) or from tm_insert / tm_delete behind the tables (subscribers)
+    for (int i = 40; i < 400; ++i) topics.push_back("t/" + std::to_string(i));
+    const uint32_t nt = (uint32_t)topics.size();
+    std::vector<std::string> dests;
+    for (int i = 0; i < 48; ++i) dests.push_back("node" + std::to_string(i));
+    auto route_del_all = [&]() {
+        for (const std::string& t : topics)
+            for (const std::string& d : dests) ok(tm_route_del(E, u8(t), (uint32_t)t.size(), u8(d), (uint32_t)d.size()), "tm_route_del");
+    };
+    auto sub_del_all = [&]() {
+        for (const std::string& t : topics)
+            for (uint32_t sub = 0; sub < 64; ++sub) {
+                ok(tm_sub_del(E, u8(t), (uint32_t)t.size(), sub, nullptr, 0, nullptr), "tm_sub_del");
+                for (int g = 0; g < 2; ++g)
+                    ok(tm_sub_del(E, u8(t), (uint32_t)t.size(), sub, u8(groups[g]), 2, nullptr), "tm_sub_del");
+            }
+    };
+    for (int round = 0; round < 4; ++round) {
+        for (int i = 0; i < 4000; ++i) {   // adds: bags past the index threshold, segments doubling
+            const std::string &t = topics[rnd(round ? nt : 60)], &d = dests[rnd((uint32_t)dests.size())];
+            ok(tm_route_add(E, u8(t), (uint32_t)t.size(), u8(d), (uint32_t)d.size()), "tm_route_add");
+            const std::string& st = topics[rnd(round ? nt : 60)];
+            const uint32_t g = rnd(4);
+            ok(tm_sub_add(E, u8(st), (uint32_t)st.size(), rnd(64), g < 2 ? u8(groups[g]) : nullptr, g < 2 ? 2 : 0),
+               "tm_sub_add");
+        }
+        phase("route/sub adds");
+        for (int i = 0; i < 12; i += 2) {   // filters behind the tables' back
+            const std::string& f = topics[40 + i];
+            ok(round % 2 ? tm_delete(E, u8(f), (uint32_t)f.size()) : tm_insert(E, u8(f), (uint32_t)f.size()), "filter");
+        }
+        phase("route/sub filters");
+        for (int i = 0; i < 6000; ++i) {   // deletes (absent entries included): segments and keys become garbage
+            const std::string &t = topics[rnd(nt)], &d = dests[rnd((uint32_t)dests.size())];
+            ok(tm_route_del(E, u8(t), (uint32_t)t.size(), u8(d), (uint32_t)d.size()), "tm_route_del");
+            const std::string& st = topics[rnd(nt)];
+            const uint32_t g = rnd(4);
+            uint32_t left = 0;
+            ok(tm_sub_del(E, u8(st), (uint32_t)st.size(), rnd(64), g < 2 ? u8(groups[g]) : nullptr, g < 2 ? 2 : 0, &left),
+               "tm_sub_del");
+        }
+        phase("route/sub deletes");
+        if (round == 1) {   // whole topics dropped: compaction of pool and arena
+            route_del_all();
+            sub_del_all();
+            phase("route/sub emptied");
+            if (tm_route_count(E) != 0 || tm_sub_count(E) != 0) return 1;
+        }
+    }
+    route_del_all();
+    sub_del_all();
+    phase("route/sub emptied");
+    if (tm_route_count(E) != 0 || tm_sub_count(E) != 0) return 1;
+    for (int i = 0; i < 1500; ++i) {   // every slot and segment taken again
+        const std::string &t = topics[rnd(nt)], &d = dests[rnd((uint32_t)dests.size())];
+        ok(tm_route_add(E, u8(t), (uint32_t)t.size(), u8(d), (uint32_t)d.size()), "tm_route_add");
+        ok(tm_sub_add(E, u8(t), (uint32_t)t.size(), rnd(64), nullptr, 0), "tm_sub_add");
+    }
+    phase("route/sub refilled");
     tm_close(E);
     std::puts("san_share: done");
     return 0;
