@@ -17,9 +17,9 @@ The device entries of f and g take the same envelopes as b (off[0] = 0 and 5).
 A wrong word id, hash or owner loses the topic's exact filter (every topic's
 own text is a filter, a route topic and a subscribed topic), so the
 comparison fails for that topic; every failure names the first differing
-topic with repr of its bytes.  Not covered: a forced 24-bit dictionary-tag
-collision (the negative branch of the byte-verify needs a brute-force search
-with a port of the hash)."""
+topic with repr of its bytes.  Forced collisions of the dictionary tag and of
+the 64-bit topic hash (the negative branch of every byte-verify) are in
+tests/test_gpu_collisions.py."""
 import contextlib
 import os
 import random

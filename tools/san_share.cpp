@@ -5,12 +5,16 @@
 // small: adds, filters created and deleted behind the tables, deletes
 // (member-down for the shares), table regrowth, pool / arena compaction,
 // emptied and refilled (every slot, set index and xid recycled) -- with
-// tm_debug_check_routes / _subs / _shares after each phase.  Build and run:
+// tm_debug_check_routes / _subs / _shares after each phase.  Each image first
+// takes two triples of topics with one 64-bit word_hash each into its empty
+// 16-slot exact-topic table (one triple's home is the last slot, so its run
+// wraps): add, delete the middle, delete the head, re-add.  Build and run:
 // make san_share (host code under -fsanitize=address,undefined; the kernels
 // are linked as built, never run).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -39,6 +43,70 @@ static void phase(const char* name) {
 }
 static const uint8_t* u8(const std::string& s) { return reinterpret_cast<const uint8_t*>(s.data()); }
 
+// Three topics of word_hash 0x803c68f6d88eacec, then three of 0xd9ab85f36d7764ef
+// (low four bits set: home = slot 15 of 16), from tests/collision_corpus.py
+// (classes E-triple and E-wrap): only the byte compare tells them apart.
+static const std::string kCollide[6] = {
+    std::string("\x9e\x28\xde\x86\xc6\x1d\xdc\xed\xac\x2b\x79\xbf\x06\x40\xb1\x53", 16),
+    std::string("\xe4\x35\x59\xc4\xca\x1d\xc8\x2a\x13\x84\xee\x46\x57\x0e\x74\xf0", 16),
+    std::string("\x63\xa0\xf2\x09\x80\x39\x71\xe6\x5c\xfe\x2a\xc0\x62\x53\x8c\x8c", 16),
+    std::string("\xf5\x48\x1f\x3a\xe4\xf1\xdd\x2a\x9e\x81\xa6\x4d\x6b\x54\x32\x83", 16),
+    std::string("\xad\x66\x4e\x4d\x74\x13\xad\xae\xab\xef\x76\x2c\xf8\xa1\x87\xe5", 16),
+    std::string("\x34\xf1\xbc\x2d\xbf\x88\x13\xf0\xe6\xaf\xd9\x17\x37\x7d\xf4\x47", 16),
+};
+enum Table { SHARES, ROUTES, SUBS };
+// key i owns what names it: member 2000 + i, subscriber 1000 + i, i + 1 routes
+static void collide_set(Table tab, int i, bool on) {
+    const std::string& t = kCollide[i];
+    const uint32_t tl = (uint32_t)t.size();
+    if (tab == SHARES) {
+        ok(on ? tm_share_add(E, u8("cg"), 2, u8(t), tl, 2000 + i) : tm_share_del(E, u8("cg"), 2, u8(t), tl, 2000 + i, nullptr),
+           "collide share");
+    } else if (tab == SUBS) {
+        ok(on ? tm_sub_add(E, u8(t), tl, 1000 + i, nullptr, 0) : tm_sub_del(E, u8(t), tl, 1000 + i, nullptr, 0, nullptr),
+           "collide sub");
+    } else {
+        for (int d = 0; d <= i; ++d) {
+            const std::string dest = "c" + std::to_string(d);
+            ok(on ? tm_route_add(E, u8(t), tl, u8(dest), (uint32_t)dest.size())
+                  : tm_route_del(E, u8(t), tl, u8(dest), (uint32_t)dest.size()),
+               "collide route");
+        }
+    }
+}
+static void collide_expect(Table tab, const bool* have, const char* name) {
+    for (int i = 0; i < 6; ++i) {
+        const std::string& t = kCollide[i];
+        uint32_t out[8] = {0}, grp[8], n = 99;
+        if (tab == SHARES) ok(tm_share_members(E, u8("cg"), 2, u8(t), (uint32_t)t.size(), out, 8, &n), name);
+        if (tab == SUBS) ok(tm_subscribers(E, u8(t), (uint32_t)t.size(), out, grp, 8, &n), name);
+        if (tab == ROUTES) ok(tm_get_routes(E, u8(t), (uint32_t)t.size(), out, 8, &n), name);
+        const uint32_t want_n = !have[i] ? 0u : tab == ROUTES ? (uint32_t)i + 1 : 1u;
+        const bool id_ok = !have[i] || tab == ROUTES || out[0] == (tab == SHARES ? 2000u : 1000u) + i;
+        if (n != want_n || !id_ok) {
+            std::fprintf(stderr, "%s: key %d holds %u entries (first %u), want %u\n", name, i, n, out[0], want_n);
+            std::exit(1);
+        }
+    }
+}
+// add, delete the middle of each triple, delete its head, re-add, then leave the table as it was
+static void collide(Table tab) {
+    bool have[6] = {false, false, false, false, false, false};
+    auto step = [&](std::initializer_list<int> keys, bool on, const char* name) {
+        for (int i : keys) {
+            collide_set(tab, i, on);
+            have[i] = on;
+        }
+        phase(name);
+        collide_expect(tab, have, name);
+    };
+    step({0, 1, 2, 3, 4, 5}, true, "collisions: added");
+    step({1, 4}, false, "collisions: middle deleted");
+    step({0, 3}, false, "collisions: head deleted");
+    step({0, 1, 3, 4}, true, "collisions: re-added");
+    step({2, 5, 0, 3, 1, 4}, false, "collisions: emptied");
+}
+
 int main() {
     tm_config cfg{};
     cfg.device = -1;
@@ -55,6 +123,7 @@ int main() {
     topics.push_back("#");
     topics.push_back(std::string("a\0b", 3));
     // ---- shares ----
+    collide(SHARES);
     for (int round = 0; round < 6; ++round) {
         for (int i = 0; i < 3000; ++i) {   // adds (duplicates included)
             const std::string &g = groups[rnd(4)], &t = topics[rnd((uint32_t)topics.size())];
@@ -98,6 +167,8 @@ int main() {
     const uint32_t nt = (uint32_t)topics.size();
     std::vector<std::string> dests;
     for (int i = 0; i < 48; ++i) dests.push_back("node" + std::to_string(i));
+    collide(ROUTES);
+    collide(SUBS);
     auto route_del_all = [&]() {
         for (const std::string& t : topics)
             for (const std::string& d : dests) ok(tm_route_del(E, u8(t), (uint32_t)t.size(), u8(d), (uint32_t)d.size()), "tm_route_del");
