@@ -10,7 +10,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-result 
 BUILD   ?= build
 LIBOUT  ?= emqx_amd/libtopicmatch.so
 
-all: $(LIBOUT) emqx_amd/libtmwork.so oracle/liboracle.so tools/ubench/batcher_bench tools/ubench/libbatchdrive.so
+all: $(LIBOUT) emqx_amd/libtmwork.so oracle/liboracle.so tools/ubench/batcher_bench tools/ubench/libbatchdrive.so tools/ubench/libpubdrive.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -35,7 +35,7 @@ $(BUILD)/exchange.o: emqx_amd/csrc/exchange.cpp emqx_amd/csrc/kernels.h include/
 $(BUILD)/batcher.o: emqx_amd/csrc/batcher.cpp include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O2 -fPIC -std=c++17 -Wall -pthread -c $< -o $@
 
-LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
+LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/pack.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
 $(LIBOUT): $(LIBOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -pthread $^ -L/opt/rocm/lib -lrccl -o $@
 
@@ -66,6 +66,10 @@ tools/ubench/batcher_bench: tools/ubench/batcher_bench.cpp emqx_amd/libtopicmatc
 tools/ubench/libbatchdrive.so: tools/ubench/batchdrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
 
+# deliveries / publish batcher driver of tools/bench_batcher.py --publish (measurement helper, ctypes)
+tools/ubench/libpubdrive.so: tools/ubench/pubdrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
+
 # tm_route_* / tm_sub_* / tm_share_* host calls under AddressSanitizer + UBSan on a host-only engine:
 # engine.cpp instrumented, the kernels linked as built and never run.  Leak
 # detection stays on for the engine's own allocations; the HIP and RCCL
@@ -78,3 +82,17 @@ san_share: $(LIBOUT)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_share
 	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_share
 .PHONY: san_share
+
+# tm_batcher_* host code (batcher.cpp, publish mode included) and engine.cpp
+# under AddressSanitizer + UBSan on a host-only engine: threaded publish
+# submits, both mismatched submit kinds, partial takes and a close with
+# requests in flight (tools/san_batcher.cpp); the kernels linked as built and
+# never run.
+SAN_BATCHER_OBJS = $(filter-out $(BUILD)/engine.o $(BUILD)/batcher.o,$(filter %.o,$(LIBOBJS)))
+san_batcher: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -pthread -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c emqx_amd/csrc/batcher.cpp -o $(BUILD)/san_batcher_lib.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -pthread -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c tools/san_batcher.cpp -o $(BUILD)/san_batcher_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_batcher_main.o $(BUILD)/san_engine.o $(BUILD)/san_batcher_lib.o $(SAN_BATCHER_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_batcher
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_batcher
+.PHONY: san_batcher

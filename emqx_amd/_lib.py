@@ -88,8 +88,22 @@ TM_BATCHER_ROUTES = 1
 TM_BATCHER_DELIVERIES = 2
 TM_BATCHER_EAGER = 4
 TM_BATCHER_CSR = 8
+TM_BATCHER_PUBLISH = 16
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
+
+
+class TmDelivery(ctypes.Structure):
+    _fields_ = [("to", ctypes.c_uint32), ("target", ctypes.c_uint32), ("ndisp", ctypes.c_uint32),
+                ("pick", ctypes.c_uint32)]
+
+
+class TmPair(ctypes.Structure):
+    _fields_ = [("to", ctypes.c_uint32), ("sub", ctypes.c_uint32)]
+
+
+PUBLISH_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(TmDelivery),
+                                   ctypes.c_uint32, ctypes.POINTER(TmPair), ctypes.c_uint32)
 
 # (name, restype, argtypes) — every symbol include/topicmatch.h declares
 SIGNATURES = [
@@ -270,10 +284,18 @@ SIGNATURES = [
                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_void_p]),
+    ("tm_publish_pack_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p]),
     ("tm_batcher_open", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,
                                          c_u64p]),
+    ("tm_batcher_submit_publish", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                                 PUBLISH_DONE_FN, ctypes.c_void_p, c_u64p]),
     ("tm_batcher_flush", ctypes.c_int, [ctypes.c_void_p]),
     ("tm_batcher_get_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats)]),
     ("tm_batcher_get_stats2", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats), ctypes.c_uint32,

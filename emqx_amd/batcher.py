@@ -3,20 +3,25 @@
 Many publisher threads submit single topics; the native worker thread seals
 device batches (by size or deadline) and calls back once per topic with its
 ordered match list (emqx_trie:match/1 filter ids), its match_routes/1
-routes, or (deliveries=True) aggre(match_routes/1): To ids + target ids.  This is the NIF's path: the callback there builds
+routes, or (deliveries=True) aggre(match_routes/1): To ids + target ids, or
+(publish=True, submit_publish) publish/1 up to the sends: the deliveries with
+their dispatch Count and $share pick, and the (To, subscriber) pairs.  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
 import itertools
+
+import numpy as np
 
 from . import _lib as L
 
 
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
-                 lanes_per_replica=0, callback_threads=0):
+                 lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0):
         self.engine = engine
         self.lib = engine.lib
-        flags = (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0)
+        flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
+            (L.TM_BATCHER_PUBLISH if publish else 0) | (L.TM_BATCHER_EAGER if eager else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
         rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))
@@ -27,6 +32,7 @@ class Batcher:
         self._cbs = {}
         self._keys = itertools.count(1)
         self._done = L.DONE_FN(self._on_done)     # one trampoline, kept alive with the batcher
+        self._pdone = L.PUBLISH_DONE_FN(self._on_publish_done)
 
     def _on_done(self, ctx, ticket, status, ids, dests, n):
         cb = self._cbs.pop(ctx)
@@ -46,6 +52,34 @@ class Batcher:
         if rc != L.TM_OK:
             del self._cbs[key]
             raise L.TopicMatchError(rc, "tm_batcher_submit")
+        return t.value
+
+    def _on_publish_done(self, ctx, ticket, status, deliv, n_deliv, pairs, n_pairs):
+        cb = self._cbs.pop(ctx)
+        if status != L.TM_OK:
+            cb(status, None, None)
+            return
+        # the records are valid only during the callback: copied out here
+        def rows(ptr, n, width):
+            if not n:
+                return []
+            raw = ctypes.string_at(ctypes.addressof(ptr.contents), n * width * 4)
+            return list(map(tuple, np.frombuffer(raw, dtype=np.uint32).reshape(n, width).tolist()))
+        cb(status, rows(deliv, n_deliv, 4), rows(pairs, n_pairs, 2))
+
+    def submit_publish(self, topic: bytes, key: int, callback):
+        """publish=True batchers: callback(status, deliveries, pairs) runs on
+        the worker thread; deliveries = [(to, target, ndisp, pick)], pairs =
+        [(to, sub)], both None on error.  key picks the $share members
+        (SHARE_KEYED: member key rem Count)"""
+        t = ctypes.c_uint64()
+        k = next(self._keys)
+        self._cbs[k] = callback
+        rc = self.lib.tm_batcher_submit_publish(self.h, topic, len(topic), key & 0xFFFFFFFF, self._pdone, k,
+                                                ctypes.byref(t))
+        if rc != L.TM_OK:
+            del self._cbs[k]
+            raise L.TopicMatchError(rc, "tm_batcher_submit_publish")
         return t.value
 
     def flush(self):

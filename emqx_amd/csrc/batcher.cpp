@@ -25,6 +25,16 @@
 // flight at once (one per lane: packing, upload, walk, read-back and
 // callbacks of neighbouring batches overlap, and every GPU of a multi-device
 // engine works), and no per-topic work runs on the single sealing thread.
+//
+// TM_BATCHER_PUBLISH carries publish/1 up to the sends (src/emqx_broker.erl:
+// 148-157, 175-192; src/emqx_shared_sub.erl:89-111, 228-249): every submit
+// brings a pick key that travels with its topic through the chunks, the lane
+// runs tm_match_publish_batch_device(TM_SHARE_KEYED) and tm_publish_pack_device
+// and reads one packed block back -- header, both offset arrays, 16 B delivery
+// records, 8 B pairs -- which the callbacks read in place.  Keyed picks are
+// stateless, so a batch whose lists outgrew the lane's buffers is simply run
+// again; round robin is not offered because that rerun would advance the set
+// cursors twice.
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
@@ -52,7 +62,10 @@ constexpr int NSTRIPE = 16;
 constexpr uint64_t TM_BATCHER_RESERVE_TOPICS = 262144;
 
 struct Req {
-    tm_batch_done_fn fn;
+    union {
+        tm_batch_done_fn fn;
+        tm_publish_done_fn pfn;   // TM_BATCHER_PUBLISH
+    };
     void* ctx;
     uint64_t ticket;
 };
@@ -63,6 +76,7 @@ struct Chunk {
     std::vector<uint8_t> bytes;
     std::vector<uint32_t> lens;
     std::vector<Req> reqs;
+    std::vector<uint32_t> keys;   // TM_BATCHER_PUBLISH: the pick key of each topic (else empty)
     size_t head = 0, bhead = 0;   // topics / bytes already taken
     size_t size() const { return lens.size() - head; }
     size_t nbytes() const { return bytes.size() - bhead; }
@@ -70,6 +84,7 @@ struct Chunk {
         bytes.clear();
         lens.clear();
         reqs.clear();
+        keys.clear();
         head = bhead = 0;
     }
     void compact() {   // drop the taken prefix once it is the larger part
@@ -77,6 +92,7 @@ struct Chunk {
         bytes.erase(bytes.begin(), bytes.begin() + bhead);
         lens.erase(lens.begin(), lens.begin() + head);
         reqs.erase(reqs.begin(), reqs.begin() + head);
+        if (!keys.empty()) keys.erase(keys.begin(), keys.begin() + head);
         head = bhead = 0;
     }
 };
@@ -157,6 +173,16 @@ struct Lane {
     const uint32_t* r_src = nullptr;
     const uint32_t* r_dst = nullptr;
     double ids_per_topic = 64.0;      // sizing estimate of the device result buffers
+    // TM_BATCHER_PUBLISH: the publish call's planes, pairs and per-topic pair
+    // counts (its other outputs use the buffers above; the packed block is
+    // d_out / h_out), the batch's results as the callbacks read them, and the
+    // sizing estimates of both capacities
+    Dev d_planes, d_sub, d_scount;
+    const uint64_t* r_doff = nullptr;
+    const uint64_t* r_soff = nullptr;
+    const tm_delivery* r_deliv = nullptr;
+    const tm_pair* r_pairs = nullptr;
+    double deliv_per_topic = 16.0, pairs_per_topic = 16.0;
     clk::time_point sealed;           // when the batch was handed over
     uint64_t launch_ns = 0, sync_ns = 0;   // this batch: host time enqueueing the device work, waiting on it
 };
@@ -173,6 +199,7 @@ struct tm_batcher {
     tm_engine* eng = nullptr;
     tm_batcher_config cfg{};
     bool host_only = false;
+    bool publish = false;   // TM_BATCHER_PUBLISH
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -216,6 +243,7 @@ struct tm_batcher {
             const size_t k = 2 * (size_t)cfg.max_topics / NSTRIPE + 64;
             c.lens.reserve(k);
             c.reqs.reserve(k);
+            if (cfg.flags & TM_BATCHER_PUBLISH) c.keys.reserve(k);
             c.bytes.reserve(k * 64);
             return c;
         }
@@ -294,6 +322,7 @@ struct tm_batcher {
                 c.bytes.assign(b0, b0 + kb);
                 c.lens.assign(x.cur.lens.begin() + h, x.cur.lens.begin() + h + k);
                 c.reqs.assign(x.cur.reqs.begin() + h, x.cur.reqs.begin() + h + k);
+                if (!x.cur.keys.empty()) c.keys.assign(x.cur.keys.begin() + h, x.cur.keys.begin() + h + k);
                 x.cur.head += k;
                 x.cur.bhead += kb;
                 x.cur.compact();
@@ -465,6 +494,114 @@ struct tm_batcher {
         return TM_OK;
     }
 
+    // TM_BATCHER_PUBLISH: [offsets (n+1) u64][keys n u32, padded to 8 B][bytes]
+    // in one pinned block, up in one copy
+    static uint64_t keyb_of(uint32_t n) { return ((uint64_t)n * 4 + 7) & ~7ull; }
+    bool pack_publish(Lane& L) {
+        uint64_t nb = 0;
+        for (const Chunk& c : L.chunks) nb += c.nbytes();
+        const uint64_t offb = ((uint64_t)L.n + 1) * 8, keyb = keyb_of(L.n);
+        if (!L.h_io.ensure(offb + keyb + nb + 16)) return false;
+        uint64_t* ho = (uint64_t*)L.h_io.p;
+        uint32_t* hk = (uint32_t*)((uint8_t*)L.h_io.p + offb);
+        uint8_t* hb = (uint8_t*)L.h_io.p + offb + keyb;
+        uint64_t o = 0, k = 0;
+        ho[0] = 0;
+        for (const Chunk& c : L.chunks) {
+            if (c.nbytes()) std::memcpy(hb + o, c.bytes.data() + c.bhead, c.nbytes());
+            if (c.size()) std::memcpy(hk + k, c.keys.data() + c.head, c.size() * 4);
+            for (size_t j = c.head; j < c.lens.size(); ++j) {
+                o += c.lens[j];
+                ho[++k] = o;
+            }
+        }
+        return true;
+    }
+    // the packed block of a publish batch (device and pinned copies alike):
+    // [hdr 4 u64][doff (n+1) u64][sub_off (n+1) u64][deliveries cap x 16 B][pairs scap x 8 B];
+    // the head is a multiple of 16 B, so the records are aligned for their stores
+    static uint64_t pk_head(uint32_t n) { return 32 + 2 * ((uint64_t)n + 1) * 8; }
+    int run_publish(Lane& L, uint64_t& results) {
+        auto chk = [](hipError_t e) { return e == hipSuccess; };
+        const uint32_t n = L.n;
+        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), head = pk_head(n);
+        const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
+        if (!L.d_io.ensure(offb + keyb + nbytes + 16) || !L.d_counts.ensure((uint64_t)n * 4 + 4) ||
+            !L.d_scount.ensure((uint64_t)n * 4 + 4) || !L.d_outoff.ensure(offb) || !L.d_total.ensure(64))
+            return TM_ENOMEM;
+        hipStream_t s = L.stream;
+        clk::time_point t0 = clk::now();
+        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + keyb + nbytes + 8, hipMemcpyHostToDevice, s)))
+            return TM_EDEVICE;
+        const uint64_t* d_off = (const uint64_t*)L.d_io.p;
+        const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
+        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + keyb;
+        uint64_t* d_total = (uint64_t*)L.d_total.p;   // [0] route total, [1] pair total
+        uint64_t cap = (uint64_t)(L.deliv_per_topic * n * 1.25) + 1024;
+        uint64_t scap = (uint64_t)(L.pairs_per_topic * n * 1.25) + 1024;
+        const bool eager = n <= EAGER_TOPICS;
+        // a second pass when the batch did not fit; a third only when the first
+        // also dropped deliveries, whose pairs its header could not count
+        for (int pass = 0; pass < 3; ++pass) {
+            if (pass) t0 = clk::now();
+            const uint64_t outb = head + cap * 16 + scap * 8;
+            if (!L.d_planes.ensure(cap * 16) || !L.d_sub.ensure(scap * 8) || !L.d_out.ensure(outb) ||
+                !L.h_out.ensure(eager ? outb : head))
+                return TM_ENOMEM;
+            uint32_t* pl = (uint32_t*)L.d_planes.p;   // to, target, ndisp, pick
+            uint32_t* sp = (uint32_t*)L.d_sub.p;      // sub_to, sub_id
+            uint8_t* d = (uint8_t*)L.d_out.p;
+            uint64_t* d_soff = (uint64_t*)(d + 32 + offb);
+            int rc = tm_match_publish_batch_device(eng, d_bytes, d_off, n, nbytes, (uint32_t*)L.d_counts.p,
+                                                   (uint64_t*)L.d_outoff.p, pl, pl + cap, pl + 2 * cap, cap, d_total,
+                                                   (uint32_t*)L.d_scount.p, d_soff, sp, sp + scap, scap, d_total + 1,
+                                                   TM_SHARE_KEYED, d_key, pl + 3 * cap, s);
+            if (rc != TM_OK) return rc;
+            rc = tm_publish_pack_device(eng, n, (const uint32_t*)L.d_counts.p, (const uint64_t*)L.d_outoff.p, pl,
+                                        pl + cap, pl + 2 * cap, pl + 3 * cap, cap, d_total, d_soff, sp, sp + scap,
+                                        scap, d_total + 1, (uint64_t*)d, (uint64_t*)(d + 32), (tm_delivery*)(d + head),
+                                        cap, (tm_pair*)(d + head + cap * 16), scap, s);
+            if (rc != TM_OK) return rc;
+            // header and offsets; a small batch also reads its records back
+            // speculatively (up to the capacities) in the same round trip
+            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? outb : head, hipMemcpyDeviceToHost, s)))
+                return TM_EDEVICE;
+            L.launch_ns += ns_since(t0);
+            t0 = clk::now();
+            if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
+            L.sync_ns += ns_since(t0);
+            const uint8_t* h = (const uint8_t*)L.h_out.p;
+            const uint64_t* hdr = (const uint64_t*)h;
+            const uint64_t rtotal = hdr[0], ptotal = hdr[1], D = hdr[2], P = hdr[3];
+            if (rtotal <= cap) {   // else the pair total covers the deliveries kept only
+                L.deliv_per_topic = 0.9 * L.deliv_per_topic + 0.1 * ((double)rtotal / n);
+                L.pairs_per_topic = 0.9 * L.pairs_per_topic + 0.1 * ((double)ptotal / n);
+            }
+            if (rtotal <= cap && ptotal <= scap && D <= cap && P <= scap) {
+                if (!eager) {   // exactly D deliveries and P pairs
+                    if (!L.h_out.ensure(outb)) return TM_ENOMEM;   // may move: the head is read again below
+                    t0 = clk::now();
+                    if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, head + D * 16, hipMemcpyDeviceToHost, s)) ||
+                        (P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + head + cap * 16, d + head + cap * 16, P * 8,
+                                                  hipMemcpyDeviceToHost, s))) ||
+                        !chk(hipStreamSynchronize(s)))
+                        return TM_EDEVICE;
+                    L.sync_ns += ns_since(t0);
+                    h = (const uint8_t*)L.h_out.p;
+                }
+                L.r_doff = (const uint64_t*)(h + 32);
+                L.r_soff = (const uint64_t*)(h + 32 + offb);
+                L.r_deliv = (const tm_delivery*)(h + head);
+                L.r_pairs = (const tm_pair*)(h + head + cap * 16);
+                results = D;
+                return TM_OK;
+            }
+            if (rtotal > cap) cap = rtotal + rtotal / 4 + 1024;   // overflow: rerun with room (rare)
+            if (ptotal > scap) scap = ptotal + ptotal / 4 + 1024;
+        }
+        return TM_EDEVICE;
+    }
+
     // callbacks of topics [lo, hi) of lane L's batch (gather order)
     void callbacks(const Lane& L, int rc, bool routes, uint32_t lo, uint32_t hi) {
         const uint32_t* cnt = L.r_counts;
@@ -481,7 +618,13 @@ struct tm_batcher {
             for (size_t j = c.head + (lo > i ? lo - i : 0u); j < c.reqs.size() && i + (j - c.head) < hi; ++j) {
                 const uint32_t k = i + (uint32_t)(j - c.head);
                 const Req& r = c.reqs[j];
-                if (rc == TM_OK)
+                if (publish) {
+                    if (rc == TM_OK)
+                        r.pfn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]),
+                              L.r_pairs + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]));
+                    else
+                        r.pfn(r.ctx, r.ticket, rc, nullptr, 0, nullptr, 0);
+                } else if (rc == TM_OK)
                     r.fn(r.ctx, r.ticket, TM_OK, src + off[k], routes ? dst + off[k] : nullptr, cnt[k]);
                 else
                     r.fn(r.ctx, r.ticket, rc, nullptr, nullptr, 0);
@@ -553,7 +696,12 @@ struct tm_batcher {
             // callbacks have gathered them (tm_lease_begin)
             uint64_t lease = 0;
             const bool leased = rc == TM_OK && n && tm_lease_begin(eng, &lease) == TM_OK;
-            if (rc == TM_OK && n) {
+            if (rc == TM_OK && n && publish) {
+                const bool packed = pack_publish(L);
+                t_packed = clk::now();
+                rc = packed ? run_publish(L, results) : TM_ENOMEM;
+                t_dev = clk::now();
+            } else if (rc == TM_OK && n) {
                 const bool packed = pack(L, routes);
                 t_packed = clk::now();
                 rc = packed ? run_device(L, routes, deliv, total) : TM_ENOMEM;
@@ -680,6 +828,40 @@ struct tm_batcher {
     }
 };
 
+namespace {
+// one topic into the calling thread's stripe (pub_key: TM_BATCHER_PUBLISH only)
+inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_t* topic, uint32_t len, Req r,
+                                                     bool publish, uint32_t pub_key, uint64_t* ticket_out) {
+    if (t_stripe < 0) t_stripe = (int)(g_stripe_rr.fetch_add(1, std::memory_order_relaxed) % NSTRIPE);
+    Stripe& s = b->stripes[t_stripe];
+    uint64_t t, was;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        t = ++s.seq * NSTRIPE + (uint64_t)t_stripe;   // unique per batcher, no shared counter
+        s.cur.bytes.insert(s.cur.bytes.end(), topic, topic + len);
+        s.cur.lens.push_back(len);
+        r.ticket = t;
+        s.cur.reqs.push_back(r);
+        if (publish) s.cur.keys.push_back(pub_key);
+        // the counters change only under the stripe lock: plain load + store
+        // (no read-modify-write per publish); the 0 -> 1 step is seq_cst for
+        // the sealer's idle hand-shake below
+        s.pending_bytes.store(s.pending_bytes.load(std::memory_order_relaxed) + len, std::memory_order_relaxed);
+        was = s.pending.load(std::memory_order_relaxed);
+        s.pending.store(was + 1, was == 0 ? std::memory_order_seq_cst : std::memory_order_release);
+        if (was == 0) s.first_ns.store(b->now_ns(), std::memory_order_release);
+    }
+    // wake the sealer only when it sleeps with nothing pending (it times the
+    // deadline itself), or when this stripe alone could fill a batch
+    if ((was == 0 && b->sealer_idle.exchange(false, std::memory_order_seq_cst)) ||
+        was + 1 == b->cfg.max_topics / NSTRIPE ||
+        ((b->cfg.flags & TM_BATCHER_EAGER) && was + 1 == TM_BATCHER_EAGER_TOPICS / NSTRIPE))
+        b->kick();
+    if (ticket_out) *ticket_out = t;
+    return TM_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out) {
@@ -692,6 +874,11 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
     if (b->cfg.max_bytes == 0) b->cfg.max_bytes = 64ull << 20;
     if (b->cfg.deadline_us == 0) b->cfg.deadline_us = 200;
     if (b->cfg.eager_us == 0) b->cfg.eager_us = 40;   // profiles/r05_f/latency.jsonl
+    b->publish = (b->cfg.flags & TM_BATCHER_PUBLISH) != 0;
+    if (b->publish && (b->cfg.flags & (TM_BATCHER_ROUTES | TM_BATCHER_DELIVERIES | TM_BATCHER_CSR))) {
+        delete b;
+        return TM_EINVAL;
+    }
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
@@ -743,6 +930,17 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
         (void)tm_reserve(e, (uint32_t)eng, eng * 64);
         for (auto& L : b->lanes) {
             if (L->device < 0 || hipSetDevice(L->device) != hipSuccess) continue;
+            if (b->publish) {   // the first batch's capacities (Lane::deliv_per_topic, pairs_per_topic)
+                const uint64_t pcap = (uint64_t)(L->deliv_per_topic * pre * 1.25) + 1024;
+                const uint64_t scap = (uint64_t)(L->pairs_per_topic * pre * 1.25) + 1024;
+                const uint64_t io = offb + tm_batcher::keyb_of((uint32_t)pre) + nbytes + 16;
+                const uint64_t outb = tm_batcher::pk_head((uint32_t)pre) + pcap * 16 + scap * 8;
+                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_counts.ensure(pre * 4 + 4) &&
+                       L->d_scount.ensure(pre * 4 + 4) && L->d_outoff.ensure(offb) && L->d_total.ensure(64) &&
+                       L->d_planes.ensure(pcap * 16) && L->d_sub.ensure(scap * 8) && L->d_out.ensure(outb) &&
+                       L->h_out.ensure(outb));
+                continue;
+            }
             (void)(L->h_io.ensure(offb + nbytes + 16) && L->d_io.ensure(offb + nbytes + 16) &&
                    L->h_out.ensure(8 + offb + cntb + cap * 4) && L->d_out.ensure(8 + offb + cntb + cap * 4) &&
                    L->h_bytes.ensure(nbytes + 16) && L->h_off.ensure(offb) && L->d_bytes.ensure(nbytes + 16) &&
@@ -771,32 +969,22 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
 
 int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn fn, void* ctx,
                       uint64_t* ticket_out) {
-    if (!b || !fn || (!topic && len)) return TM_EINVAL;
-    if (t_stripe < 0) t_stripe = (int)(g_stripe_rr.fetch_add(1, std::memory_order_relaxed) % NSTRIPE);
-    Stripe& s = b->stripes[t_stripe];
-    uint64_t t, was;
-    {
-        std::lock_guard<std::mutex> lk(s.mu);
-        t = ++s.seq * NSTRIPE + (uint64_t)t_stripe;   // unique per batcher, no shared counter
-        s.cur.bytes.insert(s.cur.bytes.end(), topic, topic + len);
-        s.cur.lens.push_back(len);
-        s.cur.reqs.push_back(Req{fn, ctx, t});
-        // the counters change only under the stripe lock: plain load + store
-        // (no read-modify-write per publish); the 0 -> 1 step is seq_cst for
-        // the sealer's idle hand-shake below
-        s.pending_bytes.store(s.pending_bytes.load(std::memory_order_relaxed) + len, std::memory_order_relaxed);
-        was = s.pending.load(std::memory_order_relaxed);
-        s.pending.store(was + 1, was == 0 ? std::memory_order_seq_cst : std::memory_order_release);
-        if (was == 0) s.first_ns.store(b->now_ns(), std::memory_order_release);
-    }
-    // wake the sealer only when it sleeps with nothing pending (it times the
-    // deadline itself), or when this stripe alone could fill a batch
-    if ((was == 0 && b->sealer_idle.exchange(false, std::memory_order_seq_cst)) ||
-        was + 1 == b->cfg.max_topics / NSTRIPE ||
-        ((b->cfg.flags & TM_BATCHER_EAGER) && was + 1 == TM_BATCHER_EAGER_TOPICS / NSTRIPE))
-        b->kick();
-    if (ticket_out) *ticket_out = t;
-    return TM_OK;
+    if (!b || !fn || (!topic && len) || b->publish) return TM_EINVAL;
+    Req r;
+    r.fn = fn;
+    r.ctx = ctx;
+    r.ticket = 0;
+    return submit_one(b, topic, len, r, false, 0, ticket_out);
+}
+
+int tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
+                              tm_publish_done_fn fn, void* ctx, uint64_t* ticket_out) {
+    if (!b || !fn || (!topic && len) || !b->publish) return TM_EINVAL;
+    Req r;
+    r.pfn = fn;
+    r.ctx = ctx;
+    r.ticket = 0;
+    return submit_one(b, topic, len, r, true, pub_key, ticket_out);
 }
 
 int tm_batcher_flush(tm_batcher* b) {

@@ -577,6 +577,7 @@ struct DevState {
     // the runs' new cursors, and the host-buffer call's keys and picks
     DevBuf w_hcnt, w_hseg, w_hset, w_hflag, w_hpre, w_hscan, w_hpairs, w_hnew, w_hcounts, w_hoff, w_hsscan, w_hkey,
         w_hpick;
+    DevBuf w_pscan;   // publish pack (pack.hip): the scan of the topics' delivery counts
     // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
     // the image epochs, so a batch continues where the one before it stopped
     // whichever image each was launched on
@@ -624,7 +625,7 @@ struct DevState {
                           &w_alarge, &w_mpre, &w_mscan, &w_bytes, &w_off, &w_counts, &w_outoff, &w_ids, &w_total,
                           &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
                           &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
-                          &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &sh_cursor,
+                          &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -4625,6 +4626,48 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const ui
                         d_pub_key, d_pick);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
+}
+
+static_assert(sizeof(tm_delivery) == 16 && sizeof(tm_pair) == 8, "pack.hip stores 16 B and 8 B records");
+
+int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                           const uint32_t* d_to, const uint32_t* d_target, const uint32_t* d_ndisp,
+                           const uint32_t* d_pick, uint64_t out_cap, const uint64_t* d_total,
+                           const uint64_t* d_sub_off, const uint32_t* d_sub_to, const uint32_t* d_sub_id,
+                           uint64_t sub_cap, const uint64_t* d_sub_total, uint64_t* d_hdr, uint64_t* d_doff,
+                           tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
+                           void* hip_stream) {
+    (void)d_sub_off;   // the pairs keep their positions: topic t's are [d_sub_off[t], d_sub_off[t+1]) as they were
+    if (!d_hdr || !d_doff || !d_off || !d_total || !d_sub_total || (n && !d_count) ||
+        (out_cap && deliv_cap && (!d_to || !d_target || !d_ndisp || !d_deliv)) ||
+        (sub_cap && pair_cap && (!d_sub_to || !d_sub_id || !d_pairs)))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "publish pack");
+    DevState& d = *e->replica_for(d_off);
+    // no image is read, so nothing is pinned: the replica's batch lock for its
+    // scan workspace, ordered on the device after the batches that used the
+    // shared workspaces before (no host wait)
+    std::unique_lock<std::mutex> held(d.bmu);
+    std::string err;
+    const int rc = catching(err, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (d.rw_used) HIPCHK(hipStreamWaitEvent(st, d.rw_done, 0));
+        d.w_pscan.ensure(scan_tmp_elems(n) * 8 + 8);
+        HIPCHK(launch_publish_pack(n, d_count, d_off, d_to, d_target, d_ndisp, d_pick, out_cap, d_total, d_sub_to,
+                                   d_sub_id, sub_cap, d_sub_total, d_hdr, d_doff, d_deliv, deliv_cap, d_pairs,
+                                   pair_cap, d.w_pscan.as<uint64_t>(), st));
+        d.rw_release(st);
+        return TM_OK;
+    });
+    held.unlock();
+    if (rc != TM_OK)
+        return guarded(e, [&] {
+            e->last_error = err;
+            return rc;
+        });
+    return rc;
 }
 
 int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,

@@ -193,6 +193,19 @@ hipError_t launch_share_compact(const uint32_t* flag, const uint64_t* P, const u
 hipError_t launch_share_rr(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
                            const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur, hipStream_t st);
 
+// A publish batch's results as dense records (pack.hip) over what
+// tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:
+// scan_tmp_elems(n)), deliv[doff[t] + k] = {to, tg, ndisp, pick} of slot
+// off[t] + k (16 B records, at most deliv_cap; pick == null: TM_NO_MEMBER_ID),
+// pairs[p] = {sub_to[p], sub_id[p]} (8 B records, at most pair_cap), hdr[4] =
+// {*total, *sub_total, doff[n], *sub_total}.  Slots at or past out_cap and
+// pairs at or past sub_cap are not read.
+hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t* off, const uint32_t* to,
+                               const uint32_t* tg, const uint32_t* ndisp, const uint32_t* pick, uint64_t out_cap,
+                               const uint64_t* total, const uint32_t* sub_to, const uint32_t* sub_id, uint64_t sub_cap,
+                               const uint64_t* sub_total, uint64_t* hdr, uint64_t* doff, void* deliv,
+                               uint64_t deliv_cap, void* pairs, uint64_t pair_cap, uint64_t* scan_tmp, hipStream_t st);
+
 // Sharded mode (shard.hip): merge per-topic match lists of S filter shards
 // for m topics.  counts [S][m]; source s's items start at src_base[s] of
 // ids / keys and are CSR-ordered by topic, each list in descending key order.

@@ -695,6 +695,25 @@ class Engine:
                                                     p(d_sub_total), strategy, p(d_keys), p(d_pick), st)
         return self._check(rc, "tm_match_publish_batch_device")
 
+    def publish_pack(self, n, d_counts, d_offs, d_to, d_target, d_ndisp, d_pick, out_cap, d_total, d_sub_off,
+                     d_sub_to, d_sub_id, sub_cap, d_sub_total, d_hdr, d_doff, d_deliv, deliv_cap, d_pairs, pair_cap,
+                     stream=None):
+        """tm_publish_pack_device over device pointers (tensors or ints; None =
+        NULL): the publish call's planes as dense 16 B delivery and 8 B pair
+        records, header and offsets"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_publish_pack_device(self.h, n, p(d_counts), p(d_offs), p(d_to), p(d_target), p(d_ndisp),
+                                             p(d_pick), out_cap, p(d_total), p(d_sub_off), p(d_sub_to), p(d_sub_id),
+                                             sub_cap, p(d_sub_total), p(d_hdr), p(d_doff), p(d_deliv), deliv_cap,
+                                             p(d_pairs), pair_cap, st)
+        return self._check(rc, "tm_publish_pack_device")
+
     # walk variants (A/B knobs of tm_walk_queue): one global dequeue head, or
     # per-XCD heads over contiguous ranges of the batch
     WALKS = {"queue": 0, "queue_xcd": 1}

@@ -715,6 +715,40 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, co
                                   uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
                                   const uint32_t* d_pub_key, uint32_t* d_out_pick, void* hip_stream);
 
+/* A publish batch's results as one dense record stream (emqx_amd/csrc/pack.hip),
+ * over what tm_match_publish_batch_device (or tm_match_dispatch_batch_device,
+ * with d_pick NULL: every pick = TM_NO_MEMBER) left on the device: publish/1 up
+ * to the sends (src/emqx_broker.erl:148-157, 175-192; src/emqx_shared_sub.erl:
+ * 89-111, 228-249).  That call's deliveries are four parallel planes over
+ * slots at route offsets, with holes after every list aggre/1 shortened, and
+ * its pairs two planes; read back plane by plane that is about ten copies.
+ * One pass here writes
+ *   d_doff[n+1]  the exclusive scan of d_count; d_doff[n] = D
+ *   d_deliv[d_doff[t] + k] = {to, target, ndisp, pick} of slot d_off[t] + k:
+ *                holes removed, topic order and list order kept
+ *   d_pairs[p] = {d_sub_to[p], d_sub_id[p]}, p < P = *d_sub_total; topic t's
+ *                pairs stay [d_sub_off[t], d_sub_off[t+1])
+ *   d_hdr[4]   = {*d_total, *d_sub_total, D, P}
+ * so one copy brings a batch back.  n == 0: a zero header and d_doff[0] = 0.
+ * out_cap / sub_cap are those of the publish call.  The batch FITS when
+ * *d_total <= out_cap, *d_sub_total <= sub_cap, D <= deliv_cap and P <=
+ * pair_cap; the host decides that from the four header words.  When it does
+ * not fit, d_hdr and d_doff are still exact and the record contents are
+ * unspecified; in every case nothing is written at or past deliv_cap records
+ * or pair_cap pairs.  Stream-ordered on hip_stream: no read-back, no host
+ * wait.  Runs on the replica that owns d_off.  TM_EINVAL: a null d_hdr, d_doff,
+ * d_off, d_total or d_sub_total, or a null plane with a capacity; TM_EDEVICE on
+ * a host-only engine. */
+typedef struct tm_delivery { uint32_t to, target, ndisp, pick; } tm_delivery;   /* 16 B */
+typedef struct tm_pair     { uint32_t to, sub; } tm_pair;                       /*  8 B */
+int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                           const uint32_t* d_to, const uint32_t* d_target, const uint32_t* d_ndisp,
+                           const uint32_t* d_pick, uint64_t out_cap, const uint64_t* d_total,
+                           const uint64_t* d_sub_off, const uint32_t* d_sub_to, const uint32_t* d_sub_id,
+                           uint64_t sub_cap, const uint64_t* d_sub_total, uint64_t* d_hdr, uint64_t* d_doff,
+                           tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
+                           void* hip_stream);
+
 /* ---- publish micro-batcher (emqx_amd/csrc/batcher.cpp) -----
  * emqx_broker:publish/1 (src/emqx_broker.erl:148-157) matches one topic per
  * call in the publisher's process.  The NIF instead submits the topic here
@@ -730,7 +764,32 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, co
  * batches complete independently
  * (a publisher waits for its own reply before publishing again).  The id /
  * dest arrays are valid only during the callback (the NIF copies them into a
- * term and enif_send()s it).  status != TM_OK: ids are null. */
+ * term and enif_send()s it).  status != TM_OK: ids are null.
+ *
+ * TM_BATCHER_PUBLISH: the batch is publish/1 up to the sends
+ * (src/emqx_broker.erl:148-157, 175-192; src/emqx_shared_sub.erl:89-111,
+ * 228-249).  A lane copies bytes, offsets and keys up, runs
+ * tm_match_publish_batch_device and tm_publish_pack_device on its stream and
+ * reads the packed block back: header, offsets and -- for batches of up to
+ * 32768 topics in the same round trip, up to the lane's capacities -- the
+ * records; a larger batch reads the header first, then exactly D deliveries
+ * and P pairs.  The capacities follow two running means (deliveries and pairs
+ * per topic); a batch that did not fit is rerun with capacities taken from
+ * its header (once more when the first run also dropped deliveries, whose
+ * pairs its header could not count).  The pick strategy is TM_SHARE_KEYED with
+ * the pub_key of each submit: `hash` with phash2(ClientId), `random` with a
+ * fresh draw.  Keyed picks are stateless, so a rerun returns what a first run
+ * would have.  Round robin (and `sticky`) are deliberately not offered here:
+ * a rerun would advance the set cursors twice.  Such a batcher takes
+ * tm_batcher_submit_publish only (tm_batcher_submit: TM_EINVAL, nothing
+ * queued), and tm_batcher_submit_publish needs the flag (else TM_EINVAL).
+ * done() gets topic's delivery records {to, target, ndisp, pick} in aggre's
+ * order and its (To, subscriber) pairs, valid only during the callback; on an
+ * error status is the device call's code (TM_EDEVICE on a host-only engine,
+ * TM_EINVAL before tm_set_local_node) and both pointers are null.
+ * tm_batcher_stats.results counts delivery records.  The flag excludes
+ * TM_BATCHER_ROUTES, TM_BATCHER_DELIVERIES and TM_BATCHER_CSR (tm_batcher_open:
+ * TM_EINVAL) and combines with TM_BATCHER_EAGER. */
 #define TM_BATCHER_ROUTES 1u   /* results are match_routes/1 (src ids + dest ids) */
 #define TM_BATCHER_DELIVERIES 2u   /* results are aggre(match_routes/1) (To ids + target ids) */
 #define TM_BATCHER_CSR 8u   /* small match/1 batches through tm_match_batch_device (four launches and a
@@ -743,13 +802,14 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, co
                                  thousands of them a second crowd the host: the p99 of sealing at every
                                  free lane was 4 ms at 1M publishes/s) */
 #define TM_BATCHER_EAGER_TOPICS 256u
+#define TM_BATCHER_PUBLISH 16u   /* results are publish/1 up to the sends: deliveries with Count and pick, and the pairs */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {
     uint32_t max_topics;      /* seal at this many pending topics (0 = 65536); a seal takes every pending topic */
     uint32_t deadline_us;     /* seal this long after the first topic (0 = 200)  */
     uint64_t max_bytes;       /* seal at this many topic bytes (0 = 64 MiB)      */
-    uint32_t flags;           /* TM_BATCHER_ROUTES | TM_BATCHER_DELIVERIES      */
+    uint32_t flags;           /* TM_BATCHER_ROUTES | TM_BATCHER_DELIVERIES | ... */
     uint32_t lanes_per_replica; /* batches in flight per GPU (0 = 2)            */
     uint32_t callback_threads;  /* threads that share a batch's callbacks with its lane
                                    (parts of >= 8192 topics; 0 = the lane alone) */
@@ -780,9 +840,15 @@ typedef struct tm_batcher_stats {
 typedef void (*tm_batch_done_fn)(void* ctx, uint64_t ticket, int status, const uint32_t* ids,
                                  const uint32_t* dests, uint32_t n);
 
+typedef void (*tm_publish_done_fn)(void* ctx, uint64_t ticket, int status, const tm_delivery* deliv,
+                                   uint32_t n_deliv, const tm_pair* pairs, uint32_t n_pairs);
+
 int  tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out);
 int  tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn done, void* ctx,
                        uint64_t* ticket_out);
+/* the same for a TM_BATCHER_PUBLISH batcher; pub_key picks the $share members of this publish */
+int  tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
+                               tm_publish_done_fn done, void* ctx, uint64_t* ticket_out);
 /* seal the open batch and wait until every submitted topic has completed */
 int  tm_batcher_flush(tm_batcher* b);
 /* the counters up to sync_ns (TM_BATCHER_STATS_V1_BYTES bytes; max_* untouched) */

@@ -1,0 +1,154 @@
+// san_batcher — drives the micro-batcher's publish mode (TM_BATCHER_PUBLISH,
+// batcher.cpp) on a host-only engine (device -1) for a sanitizer build of the
+// host code.  Nothing runs on a device: every callback must carry TM_EDEVICE
+// and null records, exactly once per submit.  Phases: threaded
+// tm_batcher_submit_publish calls; both mismatched submit kinds (TM_EINVAL,
+// nothing queued); partial takes (max_topics 64, one lane, producers far
+// ahead, so seals take a stripe's oldest topics and their keys and advance its
+// head); a close with requests in flight; the flag combinations
+// tm_batcher_open refuses; tm_publish_pack_device's argument checks.  Build
+// and run: make san_batcher (host code under -fsanitize=address,undefined; the
+// kernels are linked as built, never run).
+#include <atomic>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../include/topicmatch.h"
+
+static tm_engine* E;
+static void expect(bool cond, const char* what) {
+    if (!cond) {
+        std::fprintf(stderr, "san_batcher: %s failed (%s)\n", what, tm_last_error(E));
+        std::exit(1);
+    }
+}
+
+struct Tally {
+    std::vector<std::atomic<uint32_t>> seen;
+    std::atomic<uint64_t> bad{0}, plain{0};
+    explicit Tally(size_t n) : seen(n) {}
+};
+struct Ctx {
+    Tally* t;
+    uint32_t i;
+};
+static void on_publish(void* ctx, uint64_t, int status, const tm_delivery* deliv, uint32_t n_deliv,
+                       const tm_pair* pairs, uint32_t n_pairs) {
+    Ctx* c = static_cast<Ctx*>(ctx);
+    c->t->seen[c->i].fetch_add(1, std::memory_order_relaxed);
+    if (status != TM_EDEVICE || deliv || pairs || n_deliv || n_pairs) c->t->bad.fetch_add(1, std::memory_order_relaxed);
+}
+static void on_plain(void* ctx, uint64_t, int, const uint32_t*, const uint32_t*, uint32_t) {
+    static_cast<Tally*>(ctx)->plain.fetch_add(1, std::memory_order_relaxed);
+}
+
+// `threads` producers submit `per` topics each; close_early: tm_batcher_close
+// with requests in flight instead of a flush (close completes them all)
+static void flood(const char* name, tm_batcher_config cfg, int threads, uint32_t per, bool close_early) {
+    tm_batcher* b = nullptr;
+    expect(tm_batcher_open(E, &cfg, &b) == TM_OK, "tm_batcher_open");
+    Tally tally((size_t)threads * per);
+    std::vector<Ctx> ctx((size_t)threads * per);
+    for (uint32_t i = 0; i < ctx.size(); ++i) ctx[i] = Ctx{&tally, i};
+    std::vector<std::thread> th;
+    for (int k = 0; k < threads; ++k)
+        th.emplace_back([&, k] {
+            for (uint32_t i = 0; i < per; ++i) {
+                const uint32_t id = (uint32_t)k * per + i;
+                const std::string t = "p/" + std::to_string(k) + "/" + std::to_string(i);
+                uint64_t ticket = 0;
+                if (tm_batcher_submit_publish(b, reinterpret_cast<const uint8_t*>(t.data()), (uint32_t)t.size(),
+                                              id * 2654435761u, on_publish, &ctx[id], &ticket) != TM_OK ||
+                    ticket == 0)
+                    tally.bad.fetch_add(1, std::memory_order_relaxed);
+            }
+        });
+    for (auto& t : th) t.join();
+    tm_batcher_stats st{};
+    if (!close_early) {
+        expect(tm_batcher_flush(b) == TM_OK, "tm_batcher_flush");
+        expect(tm_batcher_get_stats2(b, &st, sizeof(st), 0) == TM_OK, "tm_batcher_get_stats2");
+        expect(st.topics == ctx.size() && st.failed_batches == st.batches && st.results == 0, "stats");
+    }
+    tm_batcher_close(b);
+    for (auto& s : tally.seen) expect(s.load() == 1, "every submit completes exactly once");
+    expect(tally.bad.load() == 0, "every callback carries TM_EDEVICE and no records");
+    std::printf("%-28s ok: %zu submits, %llu batches\n", name, ctx.size(), (unsigned long long)st.batches);
+}
+
+int main() {
+    tm_config ec{};
+    ec.device = -1;
+    expect(tm_open(&ec, &E) == TM_OK, "tm_open");
+    const uint8_t f[] = "a/+";
+    expect(tm_insert(E, f, 3) == TM_OK, "tm_insert");
+
+    tm_batcher_config cfg{};
+    cfg.flags = TM_BATCHER_PUBLISH;
+    cfg.max_topics = 1000;
+    cfg.deadline_us = 200;
+    flood("threaded submits", cfg, 8, 5000, false);
+    cfg.callback_threads = 2;
+    cfg.max_topics = 40000;
+    cfg.deadline_us = 2000;
+    flood("callback threads", cfg, 4, 20000, false);
+    cfg.callback_threads = 0;
+    cfg.max_topics = 64;
+    cfg.deadline_us = 50;
+    cfg.lanes_per_replica = 1;
+    flood("partial takes", cfg, 3, 5000, false);
+    flood("close with requests in flight", cfg, 3, 5000, true);
+    cfg.flags = TM_BATCHER_PUBLISH | TM_BATCHER_EAGER;
+    flood("eager", cfg, 4, 2000, false);
+
+    // the two submit kinds do not mix, and a refused submit queues nothing
+    {
+        Tally tally(1);
+        Ctx c{&tally, 0};
+        tm_batcher *pub = nullptr, *plain = nullptr;
+        tm_batcher_config pc{}, qc{};
+        pc.flags = TM_BATCHER_PUBLISH;
+        expect(tm_batcher_open(E, &pc, &pub) == TM_OK && tm_batcher_open(E, &qc, &plain) == TM_OK, "open");
+        expect(tm_batcher_submit(pub, f, 3, on_plain, &tally, nullptr) == TM_EINVAL, "plain submit, publish batcher");
+        expect(tm_batcher_submit_publish(plain, f, 3, 1, on_publish, &c, nullptr) == TM_EINVAL,
+               "publish submit, plain batcher");
+        expect(tm_batcher_submit_publish(pub, f, 3, 1, nullptr, &c, nullptr) == TM_EINVAL, "null callback");
+        tm_batcher_stats st{};
+        for (tm_batcher* b : {pub, plain}) {
+            expect(tm_batcher_flush(b) == TM_OK, "flush");
+            expect(tm_batcher_get_stats2(b, &st, sizeof(st), 0) == TM_OK && st.topics == 0 && st.batches == 0, "stats");
+            tm_batcher_close(b);
+        }
+        expect(tally.seen[0].load() == 0 && tally.plain.load() == 0, "no callback of a refused submit");
+        std::printf("%-28s ok\n", "mismatched submit kinds");
+    }
+    for (uint32_t other : {TM_BATCHER_ROUTES, TM_BATCHER_DELIVERIES, TM_BATCHER_CSR}) {
+        tm_batcher_config bc{};
+        bc.flags = TM_BATCHER_PUBLISH | other;
+        tm_batcher* b = nullptr;
+        expect(tm_batcher_open(E, &bc, &b) == TM_EINVAL && !b, "publish with another result kind");
+    }
+    {
+        uint64_t w[8] = {0};
+        void* p = w;
+        auto call = [&](void* hdr, void* doff, void* off, void* total) {
+            return tm_publish_pack_device(E, 1, (const uint32_t*)p, (const uint64_t*)off, (const uint32_t*)p,
+                                          (const uint32_t*)p, (const uint32_t*)p, nullptr, 1, (const uint64_t*)total,
+                                          (const uint64_t*)p, (const uint32_t*)p, (const uint32_t*)p, 1,
+                                          (const uint64_t*)p, (uint64_t*)hdr, (uint64_t*)doff, (tm_delivery*)p, 1,
+                                          (tm_pair*)p, 1, nullptr);
+        };
+        expect(call(nullptr, p, p, p) == TM_EINVAL && call(p, nullptr, p, p) == TM_EINVAL &&
+                   call(p, p, nullptr, p) == TM_EINVAL && call(p, p, p, nullptr) == TM_EINVAL,
+               "pack: null arguments");
+        expect(call(p, p, p, p) == TM_EDEVICE, "pack: host-only engine");
+        std::printf("%-28s ok\n", "pack argument checks");
+    }
+    tm_close(E);
+    std::printf("san_batcher: all phases ok\n");
+    return 0;
+}
