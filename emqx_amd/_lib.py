@@ -47,7 +47,15 @@ class TmBatcherStats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint64) for k in ("batches", "topics", "results", "max_batch", "size_seals",
                                                "deadline_seals", "failed_batches", "wait_ns", "pack_ns",
                                                "device_ns", "callback_ns", "launch_ns", "sync_ns", "max_wait_ns",
-                                               "max_pack_ns", "max_device_ns", "max_callback_ns", "max_sync_ns")]
+                                               "max_pack_ns", "max_device_ns", "max_callback_ns", "max_sync_ns",
+                                               "reruns")]
+
+
+class TmPublishCaps(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("ids", "routes", "pairs", "rr")]
+
+
+TM_PUBLISH_HDR_WORDS = 8
 
 
 class TmExchangeIn(ctypes.Structure):
@@ -89,6 +97,8 @@ TM_BATCHER_DELIVERIES = 2
 TM_BATCHER_EAGER = 4
 TM_BATCHER_CSR = 8
 TM_BATCHER_PUBLISH = 16
+TM_BATCHER_ROUND_ROBIN = 32
+TM_BATCHER_STREAM = 64
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
 
@@ -290,6 +300,15 @@ SIGNATURES = [
                                               ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                               ctypes.c_uint64, ctypes.c_void_p]),
+    ("tm_share_cursors_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    ("tm_share_cursors_close", None, [ctypes.c_void_p]),
+    ("tm_publish_stream_workspace_bytes", ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                                            ctypes.POINTER(TmPublishCaps)]),
+    ("tm_publish_stream_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.POINTER(TmPublishCaps), ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
     ("tm_batcher_open", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,

@@ -190,12 +190,16 @@ __global__ void __launch_bounds__(AG_BLOCK)
 tm_aggre(AggreView av, uint32_t n, const uint32_t* __restrict__ rcount, const uint64_t* __restrict__ roff,
          const uint32_t* __restrict__ src, const uint32_t* __restrict__ dest, const uint64_t* __restrict__ gkey,
          uint32_t* __restrict__ large, uint32_t* __restrict__ acount, uint32_t* __restrict__ out_to,
-         uint32_t* __restrict__ out_tg, uint64_t out_cap) {
+         uint32_t* __restrict__ out_tg, uint64_t out_cap, const uint64_t* __restrict__ gate) {
     __shared__ uint64_t lkey[AG_WAVES][AG_LDS];
     __shared__ uint16_t lidx[AG_WAVES][AG_LDS];
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t t = blockIdx.x * AG_WAVES + w;
     if (t >= n) return;   // whole wave; no block barriers below
+    // stream-ordered publish: the routes did not fit their capacity (pack.hip
+    // tm_stream_check).  The list of large topics then stays empty, so
+    // tm_aggre_large has nothing to do either.
+    if (gate && *gate) return;
     const uint32_t m = rcount[t];
     const uint64_t base = roff[t];
 #if defined(TM_AGGRE_VARIANT) && TM_AGGRE_VARIANT == 1   // EXPERIMENT: launch + index loads only
@@ -456,13 +460,14 @@ tm_aggre_large(AggreView av, const uint32_t* __restrict__ rcount, const uint64_t
 
 hipError_t launch_aggre(const AggreView& av, uint32_t n, const uint32_t* rcount, const uint64_t* roff,
                         const uint32_t* src, const uint32_t* dest, uint64_t* key, uint32_t* large,
-                        uint32_t* acount, uint32_t* out_to, uint32_t* out_tg, uint64_t out_cap, hipStream_t st) {
+                        uint32_t* acount, uint32_t* out_to, uint32_t* out_tg, uint64_t out_cap, hipStream_t st,
+                        const uint64_t* gate) {
     if (n == 0) return hipSuccess;
     hipError_t err = hipMemsetAsync(large, 0, 4, st);
     if (err != hipSuccess) return err;
     const dim3 g((n + AG_WAVES - 1) / AG_WAVES), blk(AG_BLOCK);
     hipLaunchKernelGGL(tm_aggre, g, blk, 0, st, av, n, rcount, roff, src, dest, key, large, acount, out_to, out_tg,
-                       out_cap);
+                       out_cap, gate);
     // persistent: 4 blocks per CU (40 KB of LDS each) over 256 CUs
     const dim3 gl(n < 1024u ? n : 1024u);
     hipLaunchKernelGGL(tm_aggre_large, gl, blk, 0, st, av, rcount, roff, src, dest, key, large, acount,

@@ -183,6 +183,14 @@ struct Lane {
     const tm_delivery* r_deliv = nullptr;
     const tm_pair* r_pairs = nullptr;
     double deliv_per_topic = 16.0, pairs_per_topic = 16.0;
+    // TM_BATCHER_STREAM / TM_BATCHER_ROUND_ROBIN: tm_publish_stream_device's
+    // workspace, the two further sizing estimates (match ids: ids_per_topic
+    // above; ranked slots), the lane's cursor context -- a lane is a publisher
+    // process -- and the passes beyond this batch's first
+    Dev d_ws;
+    double rr_per_topic = 16.0;
+    tm_share_cursors* cursors = nullptr;
+    uint64_t reruns = 0;
     clk::time_point sealed;           // when the batch was handed over
     uint64_t launch_ns = 0, sync_ns = 0;   // this batch: host time enqueueing the device work, waiting on it
 };
@@ -200,6 +208,8 @@ struct tm_batcher {
     tm_batcher_config cfg{};
     bool host_only = false;
     bool publish = false;   // TM_BATCHER_PUBLISH
+    bool stream = false;    // ... through tm_publish_stream_device (TM_BATCHER_STREAM, TM_BATCHER_ROUND_ROBIN)
+    bool round_robin = false;
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -602,6 +612,102 @@ struct tm_batcher {
         return TM_EDEVICE;
     }
 
+    // The same batch through tm_publish_stream_device: one call, no host wait
+    // inside it.  The packed block grows by the header's four further words:
+    // [hdr 8 u64][doff (n+1) u64][sub_off (n+1) u64][deliveries][pairs].  The
+    // four capacities follow running means (ids, routes, pairs, ranked slots per
+    // topic); on state != 0 the capacity the header names grows to its exact
+    // total with a quarter of slack and the batch runs again: no cursor moved,
+    // so the rerun picks what a first run would have.  At worst one rerun per
+    // stage.
+    static uint64_t ps_head(uint32_t n) { return 64 + 2 * ((uint64_t)n + 1) * 8; }
+    static uint64_t cap_of(double per_topic, uint64_t n) { return (uint64_t)(per_topic * n * 1.25) + 1024; }
+    tm_publish_caps stream_caps(const Lane& L, uint64_t n) const {
+        return tm_publish_caps{cap_of(L.ids_per_topic, n), cap_of(L.deliv_per_topic, n), cap_of(L.pairs_per_topic, n),
+                               round_robin ? cap_of(L.rr_per_topic, n) : 0};
+    }
+    int run_publish_stream(Lane& L, uint64_t& results) {
+        auto chk = [](hipError_t e) { return e == hipSuccess; };
+        const uint32_t n = L.n;
+        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), head = ps_head(n);
+        const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
+        if (!L.d_io.ensure(offb + keyb + nbytes + 16)) return TM_ENOMEM;
+        hipStream_t s = L.stream;
+        clk::time_point t0 = clk::now();
+        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + keyb + nbytes + 8, hipMemcpyHostToDevice, s)))
+            return TM_EDEVICE;
+        const uint64_t* d_off = (const uint64_t*)L.d_io.p;
+        const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
+        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + keyb;
+        tm_publish_caps caps = stream_caps(L, n);
+        const bool eager = n <= EAGER_TOPICS;
+        for (int pass = 0; pass < 5; ++pass) {
+            if (pass) {
+                t0 = clk::now();
+                ++L.reruns;
+            }
+            const uint64_t cap = caps.routes, scap = caps.pairs;
+            const uint64_t outb = head + cap * 16 + scap * 8;
+            const uint64_t wsb = tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
+            if (!wsb) return TM_ERANGE;
+            if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? outb : head)) return TM_ENOMEM;
+            uint8_t* d = (uint8_t*)L.d_out.p;
+            const int rc = tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes,
+                                                    round_robin ? TM_SHARE_ROUND_ROBIN : TM_SHARE_KEYED, d_key,
+                                                    L.cursors, &caps, L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
+                                                    (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
+                                                    (tm_pair*)(d + head + cap * 16), s);
+            if (rc != TM_OK) return rc;
+            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? outb : head, hipMemcpyDeviceToHost, s)))
+                return TM_EDEVICE;
+            L.launch_ns += ns_since(t0);
+            t0 = clk::now();
+            if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
+            L.sync_ns += ns_since(t0);
+            const uint8_t* h = (const uint8_t*)L.h_out.p;
+            const uint64_t* hdr = (const uint64_t*)h;
+            const uint64_t state = hdr[6], D = hdr[2], P = hdr[3];
+            // the totals the header holds exactly: every stage up to the one named
+            auto mean = [n](double& m, uint64_t total) { m = 0.9 * m + 0.1 * ((double)total / n); };
+            mean(L.ids_per_topic, hdr[4]);
+            if (state == 0 || state >= 2) mean(L.deliv_per_topic, hdr[0]);
+            if (state == 0 || state >= 3) mean(L.pairs_per_topic, hdr[1]);
+            if (round_robin && (state == 0 || state == 4)) mean(L.rr_per_topic, hdr[5]);
+            if (state == 0) {
+                if (!eager) {   // exactly D deliveries and P pairs
+                    if (!L.h_out.ensure(outb)) return TM_ENOMEM;   // may move: the head is read again below
+                    t0 = clk::now();
+                    if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, head + D * 16, hipMemcpyDeviceToHost, s)) ||
+                        (P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + head + cap * 16, d + head + cap * 16, P * 8,
+                                                  hipMemcpyDeviceToHost, s))) ||
+                        !chk(hipStreamSynchronize(s)))
+                        return TM_EDEVICE;
+                    L.sync_ns += ns_since(t0);
+                    h = (const uint8_t*)L.h_out.p;
+                }
+                L.r_doff = (const uint64_t*)(h + 64);
+                L.r_soff = (const uint64_t*)(h + 64 + offb);
+                L.r_deliv = (const tm_delivery*)(h + head);
+                L.r_pairs = (const tm_pair*)(h + head + cap * 16);
+                results = D;
+                return TM_OK;
+            }
+            // the stage that overflowed: its capacity from the exact total, and its
+            // mean raised to this batch's at once (a mean that creeps up by a tenth
+            // per batch would rerun the next batches too)
+            auto grown = [n](uint64_t& cap, double& m, uint64_t total) {
+                cap = total + total / 4 + 1024;
+                m = std::max(m, (double)total / n);
+            };
+            if (state == 1) grown(caps.ids, L.ids_per_topic, hdr[4]);
+            else if (state == 2) grown(caps.routes, L.deliv_per_topic, hdr[0]);
+            else if (state == 3) grown(caps.pairs, L.pairs_per_topic, hdr[1]);
+            else if (state == 4) grown(caps.rr, L.rr_per_topic, hdr[5]);
+            else return TM_EDEVICE;
+        }
+        return TM_EDEVICE;
+    }
+
     // callbacks of topics [lo, hi) of lane L's batch (gather order)
     void callbacks(const Lane& L, int rc, bool routes, uint32_t lo, uint32_t hi) {
         const uint32_t* cnt = L.r_counts;
@@ -689,6 +795,7 @@ struct tm_batcher {
             const uint32_t n = L.n;
             uint64_t total = 0, results = 0;
             L.launch_ns = L.sync_ns = 0;
+            L.reruns = 0;
             const clk::time_point t_start = clk::now();
             clk::time_point t_packed = t_start, t_dev = t_start;
             int rc = host_only ? TM_EDEVICE : TM_OK;   // host-only: the GPU path only
@@ -699,7 +806,7 @@ struct tm_batcher {
             if (rc == TM_OK && n && publish) {
                 const bool packed = pack_publish(L);
                 t_packed = clk::now();
-                rc = packed ? run_publish(L, results) : TM_ENOMEM;
+                rc = !packed ? TM_ENOMEM : stream ? run_publish_stream(L, results) : run_publish(L, results);
                 t_dev = clk::now();
             } else if (rc == TM_OK && n) {
                 const bool packed = pack(L, routes);
@@ -728,6 +835,7 @@ struct tm_batcher {
             st.callback_ns += c_ns;
             st.launch_ns += L.launch_ns;
             st.sync_ns += L.sync_ns;
+            st.reruns += L.reruns;
             st.max_wait_ns = std::max(st.max_wait_ns, w_ns);
             st.max_pack_ns = std::max(st.max_pack_ns, p_ns);
             st.max_device_ns = std::max(st.max_device_ns, d_ns);
@@ -813,6 +921,10 @@ struct tm_batcher {
             }
             L->cv.notify_all();
             if (L->th.joinable()) L->th.join();
+            if (L->cursors) {   // before the engine, as the header asks (waits for the lane's last batch)
+                tm_share_cursors_close(L->cursors);
+                L->cursors = nullptr;
+            }
             if (L->stream) {
                 (void)hipSetDevice(L->device);
                 (void)hipStreamDestroy(L->stream);
@@ -879,6 +991,12 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
         delete b;
         return TM_EINVAL;
     }
+    if (!b->publish && (b->cfg.flags & (TM_BATCHER_ROUND_ROBIN | TM_BATCHER_STREAM))) {
+        delete b;
+        return TM_EINVAL;
+    }
+    b->round_robin = (b->cfg.flags & TM_BATCHER_ROUND_ROBIN) != 0;
+    b->stream = b->round_robin || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
@@ -913,6 +1031,14 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
             delete b;
             return TM_EDEVICE;
         }
+        // a lane is a publisher process: its own round-robin dictionary on its replica
+        if (b->round_robin && L->device >= 0 &&
+            tm_share_cursors_open(e, k % (uint32_t)devs.size(), &L->cursors) != TM_OK) {
+            if (L->stream) (void)hipStreamDestroy(L->stream);
+            b->shutdown_lanes();
+            delete b;
+            return TM_EDEVICE;
+        }
         b->lanes.push_back(std::move(L));
     }
     // the workspaces sized up front (the engine's for batches of up to
@@ -930,6 +1056,14 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
         (void)tm_reserve(e, (uint32_t)eng, eng * 64);
         for (auto& L : b->lanes) {
             if (L->device < 0 || hipSetDevice(L->device) != hipSuccess) continue;
+            if (b->stream) {   // the first batch's four capacities
+                const tm_publish_caps c = b->stream_caps(*L, pre);
+                const uint64_t io = offb + tm_batcher::keyb_of((uint32_t)pre) + nbytes + 16;
+                const uint64_t outb = tm_batcher::ps_head((uint32_t)pre) + c.routes * 16 + c.pairs * 8;
+                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(outb) && L->h_out.ensure(outb) &&
+                       L->d_ws.ensure(tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
+                continue;
+            }
             if (b->publish) {   // the first batch's capacities (Lane::deliv_per_topic, pairs_per_topic)
                 const uint64_t pcap = (uint64_t)(L->deliv_per_topic * pre * 1.25) + 1024;
                 const uint64_t scap = (uint64_t)(L->pairs_per_topic * pre * 1.25) + 1024;
@@ -1006,7 +1140,7 @@ int tm_batcher_get_stats(tm_batcher* b, tm_batcher_stats* out) {
 int tm_batcher_get_stats2(tm_batcher* b, tm_batcher_stats* out, uint32_t out_size, uint32_t flags) {
     if (!b || !out || out_size < TM_BATCHER_STATS_V1_BYTES) return TM_EINVAL;
     std::lock_guard<std::mutex> lk(b->mu);
-    std::memcpy(out, &b->st, std::min<size_t>(out_size, sizeof(tm_batcher_stats)));
+    std::memcpy(out, &b->st, std::min<size_t>(out_size, sizeof(tm_batcher_stats)));   // reruns included, at the end
     if (flags & TM_BATCHER_STATS_RESET_MAX)
         b->st.max_wait_ns = b->st.max_pack_ns = b->st.max_device_ns = b->st.max_callback_ns = b->st.max_sync_ns = 0;
     return TM_OK;

@@ -56,9 +56,21 @@ __global__ void __launch_bounds__(DBLOCK)
 tm_dispatch_count(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
                   const uint32_t* __restrict__ acount, const uint64_t* __restrict__ aoff,
                   const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg, uint64_t slots,
-                  uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg) {
+                  uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg,
+                  const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate) {
     __shared__ uint64_t lds_inc[DBLOCK];   // inclusive prefix of the block's spans
     __shared__ uint64_t lds_scan[DBLOCK / 64];
+    if (gate && *gate) return;   // an earlier stage of a stream-ordered publish overflowed (wave-uniform)
+    // dtotal: the route total on the device; `slots` is then the capacity, the
+    // live slots are min(*dtotal, slots) and pcnt is zero from there to the
+    // capacity (the scan after this pass runs over the capacity)
+    const uint64_t cap = slots;
+    if (dtotal) {
+        const uint64_t r = *dtotal;
+        if (r < slots) slots = r;
+        for (uint64_t g = slots + (uint64_t)blockIdx.x * DBLOCK + threadIdx.x; g < cap; g += (uint64_t)gridDim.x * DBLOCK)
+            pcnt[g] = 0;
+    }
     const uint32_t t0 = blockIdx.x * DBLOCK;
     const uint32_t tn = n - t0 < (uint32_t)DBLOCK ? n - t0 : (uint32_t)DBLOCK;
     const uint32_t t = t0 + threadIdx.x;
@@ -113,9 +125,10 @@ tm_dispatch_lookup(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t
 // per topic: its pairs' offset and number, from the slot prefix
 __global__ void __launch_bounds__(DBLOCK)
 tm_dispatch_offsets(const uint64_t* __restrict__ P, uint64_t slots, const uint64_t* __restrict__ aoff, uint32_t n,
-                    uint32_t* __restrict__ sub_count, uint64_t* __restrict__ sub_off) {
+                    uint32_t* __restrict__ sub_count, uint64_t* __restrict__ sub_off,
+                    const uint64_t* __restrict__ gate) {
     const uint32_t t = blockIdx.x * DBLOCK + threadIdx.x;
-    if (t > n) return;
+    if (t > n || (gate && *gate)) return;
     const uint64_t a = aoff[t] < slots ? aoff[t] : slots;
     const uint64_t pa = P[a];
     sub_off[t] = pa;
@@ -131,7 +144,8 @@ tm_dispatch_offsets(const uint64_t* __restrict__ P, uint64_t slots, const uint64
 __global__ void __launch_bounds__(DBLOCK)
 tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
                  const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to, uint32_t* __restrict__ sub_to,
-                 uint32_t* __restrict__ sub_id, uint64_t cap) {
+                 uint32_t* __restrict__ sub_id, uint64_t cap, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * DBLOCK + threadIdx.x) >> 6;
     const uint64_t nwaves = (uint64_t)gridDim.x * (DBLOCK / 64);
@@ -185,10 +199,11 @@ static inline uint32_t ddiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + 
 
 hipError_t launch_dispatch_count(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                  const uint32_t* acount, const uint64_t* aoff, const uint32_t* to, const uint32_t* tg,
-                                 uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st) {
+                                 uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st,
+                                 const uint64_t* dtotal, const uint64_t* gate) {
     if (n == 0 || slots == 0) return hipSuccess;
     hipLaunchKernelGGL(tm_dispatch_count, dim3(ddiv_up(n, DBLOCK)), dim3(DBLOCK), 0, st, sv, bytes, off, n, acount,
-                       aoff, to, tg, slots, ndisp, pcnt, pseg);
+                       aoff, to, tg, slots, ndisp, pcnt, pseg, dtotal, gate);
     return hipGetLastError();
 }
 
@@ -201,15 +216,15 @@ hipError_t launch_dispatch_lookup(const SubView& sv, const uint8_t* bytes, const
 }
 
 hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint64_t* aoff, uint32_t n,
-                                   uint32_t* sub_count, uint64_t* sub_off, hipStream_t st) {
+                                   uint32_t* sub_count, uint64_t* sub_off, hipStream_t st, const uint64_t* gate) {
     hipLaunchKernelGGL(tm_dispatch_offsets, dim3(ddiv_up((uint64_t)n + 1, DBLOCK)), dim3(DBLOCK), 0, st, P, slots, aoff,
-                       n, sub_count, sub_off);
+                       n, sub_count, sub_off, gate);
     return hipGetLastError();
 }
 
 hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                 const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
-                                uint64_t pairs_bound, hipStream_t st) {
+                                uint64_t pairs_bound, hipStream_t st, const uint64_t* gate) {
     const uint64_t bound = pairs_bound < cap ? pairs_bound : cap;
     if (slots == 0 || bound == 0) return hipSuccess;
     // a wave per DCHUNK pairs up to a full machine of resident waves; the
@@ -217,7 +232,7 @@ hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t s
     uint32_t blocks = ddiv_up(bound, (uint64_t)DCHUNK * (DBLOCK / 64));
     if (blocks > 2048u) blocks = 2048u;
     hipLaunchKernelGGL(tm_dispatch_emit, dim3(blocks), dim3(DBLOCK), 0, st, sv.pool, P, slots, pseg, to, sub_to, sub_id,
-                       cap);
+                       cap, gate);
     return hipGetLastError();
 }
 

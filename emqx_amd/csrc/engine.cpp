@@ -583,6 +583,9 @@ struct DevState {
     // whichever image each was launched on
     DevBuf sh_cursor;
     uint32_t sh_cursor_n = 0;   // entries
+    // the open cursor contexts of this replica (tm_share_cursors_open): one
+    // more such array each, kept by commit exactly as sh_cursor is
+    std::vector<tm_share_cursors*> cursor_ctx;
     DevBuf w_mpre, w_mscan, w_bytes, w_off, w_counts, w_outoff, w_ids, w_total;
     // the route / aggre workspaces are shared by every stream:
     // rw_done is recorded after the last route or aggre kernel of a batch;
@@ -662,6 +665,17 @@ struct DevState {
 };
 
 }  // namespace
+
+// One publisher process's {shared_sub_round_robin, Group, Topic} dictionary
+// (src/emqx_shared_sub.erl:243-249) on one replica: a u32 per set index,
+// 0xFFFFFFFF = undefined.  e == nullptr: the engine was closed first and took
+// the device memory with it; only the host struct is left to delete.
+struct tm_share_cursors {
+    tm_engine* e = nullptr;
+    uint32_t replica = 0;
+    DevBuf buf;
+    uint32_t n = 0;   // entries
+};
 
 struct tm_engine {
     std::recursive_mutex mu;
@@ -2018,34 +2032,52 @@ struct tm_engine {
     // (grown with its contents kept, after every batch that could still write
     // the old array), and the cursors of the indices in `reset` go back to
     // undefined with this commit's scatters
+    // The same holds for every open cursor context of the replica
+    // (d.cursor_ctx): one rule for the built-in array and for each of them, so
+    // "a set index is reused only after both epochs dropped its set, and the
+    // commit that frees it resets its cursor" is true of every dictionary.
+    static uint32_t cursor_capacity(uint32_t need) {
+        return (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(1024, (uint64_t)need * 2));
+    }
+    // buf becomes an array of cap entries: its n old ones kept, the rest undefined (synchronous on d.ustream)
+    static void cursor_array_grow(DevState& d, DevBuf& buf, uint32_t& n, uint32_t cap) {
+        DevBuf nb;
+        nb.ensure((size_t)cap * 4, 1.0);
+        HIPCHK(hipMemsetAsync(nb.p, 0xFF, (size_t)cap * 4, d.ustream));
+        if (buf.p && n) HIPCHK(hipMemcpyAsync(nb.p, buf.p, (size_t)n * 4, hipMemcpyDeviceToDevice, d.ustream));
+        HIPCHK(hipStreamSynchronize(d.ustream));
+        buf.release();
+        buf = nb;
+        n = cap;
+    }
     void share_cursor_prepare(DevState& d, Image& g, const std::vector<uint32_t>& reset) {
         const uint32_t need = std::max<uint32_t>(sh_next_six, 1);
-        if (d.sh_cursor_n < need) {
+        bool grow = d.sh_cursor_n < need;
+        for (tm_share_cursors* c : d.cursor_ctx) grow = grow || c->n < need;
+        if (grow) {
             d.drain_image(0);
             d.drain_image(1);
             d.rw_drain();
-            const uint32_t cap = (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(1024, (uint64_t)need * 2));
-            DevBuf nb;
-            nb.ensure((size_t)cap * 4, 1.0);
-            HIPCHK(hipMemsetAsync(nb.p, 0xFF, (size_t)cap * 4, d.ustream));
-            if (d.sh_cursor.p && d.sh_cursor_n)
-                HIPCHK(hipMemcpyAsync(nb.p, d.sh_cursor.p, (size_t)d.sh_cursor_n * 4, hipMemcpyDeviceToDevice, d.ustream));
-            HIPCHK(hipStreamSynchronize(d.ustream));
-            d.sh_cursor.release();
-            d.sh_cursor = nb;
-            d.sh_cursor_n = cap;
+            const uint32_t cap = cursor_capacity(need);
+            if (d.sh_cursor_n < need) cursor_array_grow(d, d.sh_cursor, d.sh_cursor_n, cap);
+            for (tm_share_cursors* c : d.cursor_ctx)
+                if (c->n < need) cursor_array_grow(d, c->buf, c->n, cap);
         }
         g.cursor = d.sh_cursor.as<uint32_t>();
         if (reset.empty()) return;
         const size_t n = reset.size();
-        const uint64_t off = (d.stage_host.size() + 15) & ~uint64_t(15);
-        d.stage_host.resize(off + n * 8);
-        uint32_t* ix = reinterpret_cast<uint32_t*>(d.stage_host.data() + off);
-        for (size_t k = 0; k < n; ++k) {
-            ix[k] = reset[k];
-            ix[n + k] = 0xFFFFFFFFu;
-        }
-        d.stage_ops.push_back(DevState::ScatterOp{d.sh_cursor.p, off, n, 1u});
+        auto reset_in = [&](void* table) {
+            const uint64_t off = (d.stage_host.size() + 15) & ~uint64_t(15);
+            d.stage_host.resize(off + n * 8);
+            uint32_t* ix = reinterpret_cast<uint32_t*>(d.stage_host.data() + off);
+            for (size_t k = 0; k < n; ++k) {
+                ix[k] = reset[k];
+                ix[n + k] = 0xFFFFFFFFu;
+            }
+            d.stage_ops.push_back(DevState::ScatterOp{table, off, n, 1u});
+        };
+        reset_in(d.sh_cursor.p);
+        for (tm_share_cursors* c : d.cursor_ctx) reset_in(c->buf.p);
     }
 
     // ---- to_rank labels (order maintenance) ----
@@ -3110,6 +3142,150 @@ struct tm_engine {
         d.rw_release(st);
     }
 
+    // ---- tm_publish_stream_device: publish/1 up to the sends without a host wait ----
+    // Every intermediate of run_dispatch + the pack lives in the caller's
+    // workspace, cut up here (256 B aligned pieces, each a monotone function of
+    // n and of the capacities).  ctl: pack.hip tm_stream_check; raw: the totals
+    // the walk and the route scan write before the check copies them.
+    struct StreamLayout {
+        uint64_t ctl, raw, rcounts, roff, rids, rexact, rscan, dcount, aoff, dsrc, ddest, akey, alarge, acount, to, tg,
+            ndisp, pick, sub_count, sub_to, sub_id, xpcnt, xpseg, xpre, xscan, hcnt, hseg, hset, hflag, hpre, hscan,
+            hk, hnew, hcounts, hoff, hsscan, pscan, bytes;
+    };
+    static StreamLayout stream_layout(uint32_t n, const tm_publish_caps& c) {
+        StreamLayout L{};
+        uint64_t at = 0;
+        auto take = [&](uint64_t bytes) {
+            const uint64_t o = at;
+            at += (bytes + 255) & ~255ull;
+            return o;
+        };
+        const uint64_t n1 = (uint64_t)n + 1, R = c.routes, R1 = c.routes + 1;
+        const uint32_t pc = presort_counts((uint32_t)c.rr);
+        L.ctl = take(64);
+        L.raw = take(64);
+        L.rcounts = take(n1 * 4);
+        L.roff = take(n1 * 8);
+        L.rids = take(c.ids * 4);
+        L.rexact = take(n1 * 16);
+        L.rscan = take(scan_tmp_elems(n) * 8 + 8);
+        L.dcount = take(n1 * 4);
+        L.aoff = take(n1 * 8);
+        L.dsrc = take(R * 4);
+        L.ddest = take(R * 4);
+        L.akey = take(R * 8);
+        L.alarge = take(n1 * 4 + 16);
+        L.acount = take(n1 * 4);
+        L.to = take(R * 4);
+        L.tg = take(R * 4);
+        L.ndisp = take(R * 4);
+        L.pick = take(R * 4);
+        L.sub_count = take(n1 * 4);
+        L.sub_to = take(c.pairs * 4);
+        L.sub_id = take(c.pairs * 4);
+        L.xpcnt = take(R1 * 4);
+        L.xpseg = take(R1 * 4);
+        L.xpre = take(R1 * 8);
+        L.xscan = take(scan_tmp_elems((uint32_t)R) * 8 + 8);
+        L.hcnt = take(R1 * 4);
+        L.hseg = take(R1 * 4);
+        L.hset = take(R1 * 4);
+        L.hflag = take(R1 * 4);
+        L.hpre = take(R1 * 8);
+        L.hscan = take(scan_tmp_elems((uint32_t)R) * 8 + 8);
+        L.hk = take(c.rr * 16);
+        L.hnew = take(c.rr * 4);
+        L.hcounts = take((uint64_t)pc * 4);
+        L.hoff = take(((uint64_t)pc + 1) * 8);
+        L.hsscan = take(scan_tmp_elems(pc) * 8 + 8);
+        L.pscan = take(scan_tmp_elems(n) * 8 + 8);
+        L.bytes = at;
+        return L;
+    }
+    static bool stream_caps_ok(const tm_publish_caps& c) {
+        const uint64_t lim = 0xFFFFFFFEull;   // slots, pairs and ranked slots are u32 indices on the device
+        return c.ids < lim && c.routes < lim && c.pairs < lim && c.rr < lim;
+    }
+    // The stages of run_dispatch and launch_publish_pack in their order, each
+    // bounded by its capacity and followed by tm_stream_check; enqueues only.
+    // The walk takes the replica's next slot as tm_match_batch_device does.
+    // cur: the cursor array round robin reads and (last kernel, state 0 only)
+    // writes.
+    void run_publish_stream(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, uint64_t nbytes,
+                            uint32_t strategy, const uint32_t* pub_key, uint32_t* cur, const tm_publish_caps& c,
+                            uint8_t* ws, uint64_t* hdr, uint64_t* doff, uint64_t* sub_off, void* deliv, void* pairs,
+                            hipStream_t st) {
+        const StreamLayout L = stream_layout(n, c);
+        auto u32 = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(ws + o); };
+        auto u64 = [&](uint64_t o) { return reinterpret_cast<uint64_t*>(ws + o); };
+        uint64_t* ctl = u64(L.ctl);
+        uint64_t* raw = u64(L.raw);   // [0] match ids, [1] routes
+        const uint64_t* gate = ctl;
+        HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+        // 1. emqx_trie:match/1
+        run_batch(d, bytes, off, n, nbytes, u32(L.rcounts), u64(L.roff), c.ids ? u32(L.rids) : nullptr, c.ids, raw, st);
+        HIPCHK(launch_stream_check(ctl, 1, raw, c.ids, st));
+        // 2. emqx_router:match_routes/1, with the aggre keys
+        const AggreView av = aggre_view(d);
+        uint32_t* src = u32(L.dsrc);
+        uint32_t* dest = u32(L.ddest);
+        HIPCHK(launch_routes(route_view(d), bytes, off, n, u32(L.rcounts), u64(L.roff), u32(L.rids),
+                             reinterpret_cast<uint4*>(ws + L.rexact), u32(L.dcount), u64(L.aoff), src, dest, c.routes,
+                             raw + 1, u64(L.rscan), st, &av, u64(L.akey), gate));
+        HIPCHK(launch_stream_check(ctl, 2, raw + 1, c.routes, st));
+        // 3. aggre/1 and the local dispatch: slots = min(route total, caps.routes), read on the device
+        const uint64_t R = c.routes;
+        uint32_t *acount = u32(L.acount), *to = u32(L.to), *tg = u32(L.tg), *ndisp = u32(L.ndisp), *pick = u32(L.pick);
+        HIPCHK(launch_aggre(av, n, u32(L.dcount), u64(L.aoff), src, dest, u64(L.akey), u32(L.alarge), acount, to, tg, R,
+                            st, gate));
+        uint64_t* P = u64(L.xpre);
+        HIPCHK(launch_dispatch_count(sub_view(d), bytes, off, n, acount, u64(L.aoff), to, tg, R, ndisp, u32(L.xpcnt),
+                                     u32(L.xpseg), st, raw + 1, gate));
+        HIPCHK(launch_scan0(u32(L.xpcnt), (uint32_t)R, P, P + R, u64(L.xscan), st));
+        HIPCHK(launch_stream_check(ctl, 3, P + R, c.pairs, st));
+        HIPCHK(launch_dispatch_offsets(P, R, u64(L.aoff), n, u32(L.sub_count), sub_off, st, gate));
+        HIPCHK(launch_dispatch_emit(sub_view(d), P, R, u32(L.xpseg), to, u32(L.sub_to), u32(L.sub_id), c.pairs, c.pairs,
+                                    st, gate));
+        // 4. the $share picks
+        ShareView hv = share_view(d);
+        hv.cursor = cur;
+        const uint32_t local = sub_view(d).local_target;
+        const bool rr = strategy == TM_SHARE_ROUND_ROBIN;
+        uint64_t* HP = u64(L.hpre);
+        uint32_t *k0 = u32(L.hk), *v0 = k0 + c.rr, *k1 = v0 + c.rr, *v1 = k1 + c.rr;
+        bool odd = false;
+        if (!rr) {
+            HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, R, pub_key, pick, nullptr,
+                                       nullptr, nullptr, nullptr, st, raw + 1, gate));
+        } else {
+            HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, R, nullptr, pick,
+                                       u32(L.hcnt), u32(L.hseg), u32(L.hset), u32(L.hflag), st, raw + 1, gate));
+            HIPCHK(launch_scan0(u32(L.hflag), (uint32_t)R, HP, HP + R, u64(L.hscan), st));
+            HIPCHK(launch_stream_check(ctl, 4, HP + R, c.rr, st));
+            // the radix passes cover the bits the set indices need; the padding
+            // key's digits are all 255 and the sort is stable, so it stays last
+            uint32_t bits = 0;
+            while (bits < 32 && ((uint64_t)1 << bits) < hv.n_sets) ++bits;
+            const uint32_t passes = (bits + 7) / 8;
+            HIPCHK(launch_share_compact_pad(u32(L.hflag), HP, u32(L.hset), R, k0, v0, c.rr, n, raw + 1, gate, st));
+            HIPCHK(launch_sort_pairs(k0, v0, k1, v1, (uint32_t)c.rr, passes, u32(L.hcounts), u64(L.hoff),
+                                     u64(L.hsscan), st));
+            odd = passes & 1u;
+            HIPCHK(launch_share_rr_pick(hv, odd ? k1 : k0, odd ? v1 : v0, (uint32_t)c.rr, u32(L.hcnt), u32(L.hseg), pick,
+                                        u32(L.hnew), HP + R, gate, st));
+        }
+        // 5. the dense records and the header
+        HIPCHK(launch_publish_pack(n, acount, u64(L.aoff), to, tg, ndisp, pick, R, raw + 1, u32(L.sub_to), u32(L.sub_id),
+                                   c.pairs, P + R, hdr, doff, deliv, R, pairs, c.pairs, u64(L.pscan), st, gate));
+        HIPCHK(launch_stream_finish(ctl, doff, n, hdr, st));
+        // 6. the new cursors, only when the whole batch fitted: a rerun of a
+        // batch that did not starts from the cursors its first run found
+        if (rr)
+            HIPCHK(launch_share_rr_store(hv, odd ? k1 : k0, u32(L.hnew), (uint32_t)c.rr, HP + R, gate, st));
+        d.note_use(st);   // the pinned images (and the cursor array) are read until this point of st
+        d.rw_release(st);
+    }
+
     void finish_batch(uint32_t n) {
         last_stats = tm_batch_stats{};
         last_stats.topics = n;
@@ -3478,6 +3654,21 @@ int tm_open_devices(const tm_config* cfg, const int32_t* devices, uint32_t n_dev
 void tm_close(tm_engine* e) {
     if (!e) return;
     e->pool.reset();
+    // contexts still open: their device memory goes with the replica (after
+    // its streams have drained), the host structs stay for their owners'
+    // tm_share_cursors_close, which then only deletes them
+    for (auto& d : e->devs) {
+        (void)hipSetDevice(d->device);
+        if (d->stream) (void)hipStreamSynchronize(d->stream);
+        if (d->ustream) (void)hipStreamSynchronize(d->ustream);
+        if (!d->cursor_ctx.empty()) (void)hipDeviceSynchronize();   // their last calls ran on callers' streams
+        for (tm_share_cursors* c : d->cursor_ctx) {
+            c->buf.release();
+            c->n = 0;
+            c->e = nullptr;
+        }
+        d->cursor_ctx.clear();
+    }
     for (auto& d : e->devs) d->release();
     delete e;
 }
@@ -4668,6 +4859,96 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
             return rc;
         });
     return rc;
+}
+
+int tm_share_cursors_open(tm_engine* e, uint32_t replica, tm_share_cursors** out) {
+    if (!e || !out) return TM_EINVAL;
+    *out = nullptr;
+    if (e->devs.empty()) return no_device(e, "a cursor context");
+    if (replica >= e->devs.size()) return TM_EINVAL;
+    DevState& d = *e->devs[replica];
+    std::unique_lock<std::mutex> held(d.bmu);   // commits of this replica run under its batch lock or the engine's
+    return guarded(e, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        std::unique_ptr<tm_share_cursors> c(new tm_share_cursors());
+        c->e = e;
+        c->replica = replica;
+        // as large as the built-in array is (or would be): covers every set
+        // index handed out, all undefined
+        const uint32_t cap = std::max(d.sh_cursor_n, tm_engine::cursor_capacity(std::max<uint32_t>(e->sh_next_six, 1)));
+        tm_engine::cursor_array_grow(d, c->buf, c->n, cap);
+        d.cursor_ctx.push_back(c.get());
+        *out = c.release();
+        return TM_OK;
+    });
+}
+
+void tm_share_cursors_close(tm_share_cursors* c) {
+    if (!c) return;
+    tm_engine* e = c->e;
+    if (e) {   // else the engine went first and released the array
+        DevState& d = *e->devs[c->replica];
+        std::unique_lock<std::mutex> held(d.bmu);
+        (void)guarded(e, [&]() -> int {
+            tm_engine::Guard g(d.device);
+            // every call that could still read or write the array, and the
+            // commit scatters that reset entries of it
+            d.drain_image(0);
+            d.drain_image(1);
+            d.rw_drain();
+            HIPCHK(hipStreamSynchronize(d.ustream));
+            return TM_OK;
+        });
+        std::lock_guard<std::recursive_mutex> lk(e->mu);
+        auto& v = d.cursor_ctx;
+        v.erase(std::remove(v.begin(), v.end(), c), v.end());
+        tm_engine::Guard g(d.device);
+        c->buf.release();
+    }
+    delete c;
+}
+
+uint64_t tm_publish_stream_workspace_bytes(tm_engine* e, uint32_t n, uint64_t topic_bytes, const tm_publish_caps* caps) {
+    (void)e;             // a function of the sizes alone: the same on every replica and on a host-only engine
+    (void)topic_bytes;   // the topic bytes are read in place; the walk's rows live in the replica's slots
+    if (!caps || !tm_engine::stream_caps_ok(*caps)) return 0;
+    return tm_engine::stream_layout(n, *caps).bytes;
+}
+
+int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                             uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                             tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                             uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                             tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream) {
+    if (!d_off || !d_hdr || !d_doff || !d_sub_off || !caps || !d_workspace) return TM_EINVAL;
+    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
+    if (strategy == TM_SHARE_KEYED && n && !d_pub_key) return TM_EINVAL;
+    if ((caps->routes && !d_deliv) || (caps->pairs && !d_pairs)) return TM_EINVAL;
+    tm_publish_caps c = *caps;
+    if (strategy == TM_SHARE_KEYED) c.rr = 0;   // ignored: keyed picks rank nothing
+    if (!tm_engine::stream_caps_ok(c)) return TM_ERANGE;
+    if (workspace_bytes < tm_engine::stream_layout(n, c).bytes) return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "publish");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->replica_for(d_off);
+    if (cursors && (cursors->e != e || e->devs[cursors->replica].get() != &d)) return TM_EINVAL;
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (n == 0) {
+            HIPCHK(hipMemsetAsync(d_hdr, 0, 8 * TM_PUBLISH_HDR_WORDS, st));
+            HIPCHK(hipMemsetAsync(d_doff, 0, 8, st));
+            HIPCHK(hipMemsetAsync(d_sub_off, 0, 8, st));
+            return TM_OK;
+        }
+        // under the batch lock: a commit (which may move a cursor array) runs
+        // under it too, or under the engine lock before the pin above
+        uint32_t* cur = cursors ? cursors->buf.as<uint32_t>() : tm_engine::share_view(d).cursor;
+        e->run_publish_stream(d, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cur, c,
+                              static_cast<uint8_t*>(d_workspace), d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, st);
+        return TM_OK;
+    }, [&] { e->finish_batch(n); });
 }
 
 int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,

@@ -138,7 +138,7 @@ hipError_t launch_routes(const RouteView& rv, const uint8_t* bytes, const uint64
                          const uint32_t* counts, const uint64_t* ids_off, const uint32_t* ids, uint4* exact,
                          uint32_t* rcount, uint64_t* out_off, uint32_t* out_src, uint32_t* out_dest,
                          uint64_t out_cap, uint64_t* total, uint64_t* scan_tmp, hipStream_t st,
-                         const AggreView* av = nullptr, uint64_t* out_key = nullptr);
+                         const AggreView* av = nullptr, uint64_t* out_key = nullptr, const uint64_t* gate = nullptr);
 
 // emqx_broker:aggre/1 (aggre.hip) over a match_routes CSR (rcount, roff,
 // src, dest, key from launch_routes with av; key rows of topics with > 4096
@@ -148,7 +148,20 @@ hipError_t launch_routes(const RouteView& rv, const uint8_t* bytes, const uint64
 // or a filter id, out_tg = target id); entries at or past out_cap are dropped.
 hipError_t launch_aggre(const AggreView& av, uint32_t n, const uint32_t* rcount, const uint64_t* roff,
                         const uint32_t* src, const uint32_t* dest, uint64_t* key, uint32_t* large, uint32_t* acount, uint32_t* out_to, uint32_t* out_tg, uint64_t out_cap,
-                        hipStream_t st);
+                        hipStream_t st, const uint64_t* gate = nullptr);
+
+// The stream-ordered publish call (engine.cpp run_publish_stream, pack.hip
+// tm_stream_check / tm_stream_finish) runs the route, aggre, dispatch, share
+// and pack passes without ever reading a total back.  Its launchers take two
+// optional device words, both null for every other caller (today's behaviour
+// exactly):
+//   gate    the call's state word: a kernel whose gate is not 0 leaves at once
+//   dtotal  the route total (slot passes): `slots` is then the CAPACITY, the
+//           live slots are min(*dtotal, slots), and the pass zeroes the array
+//           its scan reads (pcnt / flag) from the live slots to the capacity
+// ctl: 8 u64 {state, ids, routes, pairs, rr slots, ...}, zeroed by the caller.
+hipError_t launch_stream_check(uint64_t* ctl, uint32_t stage, const uint64_t* total, uint64_t cap, hipStream_t st);
+hipError_t launch_stream_finish(const uint64_t* ctl, const uint64_t* doff, uint32_t n, uint64_t* hdr, hipStream_t st);
 
 // emqx_broker:dispatch/2 fan-out (dispatch.hip) over the deliveries CSR that
 // launch_aggre left (acount, aoff = the route offsets, to, tg); slots =
@@ -163,14 +176,16 @@ hipError_t launch_aggre(const AggreView& av, uint32_t n, const uint32_t* rcount,
 //                            upper bound of the pairs the caller knows (sizes the grid)
 hipError_t launch_dispatch_count(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                  const uint32_t* acount, const uint64_t* aoff, const uint32_t* to, const uint32_t* tg,
-                                 uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st);
+                                 uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st,
+                                 const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr);
 hipError_t launch_dispatch_lookup(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                   uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st);
 hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint64_t* aoff, uint32_t n,
-                                   uint32_t* sub_count, uint64_t* sub_off, hipStream_t st);
+                                   uint32_t* sub_count, uint64_t* sub_off, hipStream_t st,
+                                   const uint64_t* gate = nullptr);
 hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                 const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
-                                uint64_t pairs_bound, hipStream_t st);
+                                uint64_t pairs_bound, hipStream_t st, const uint64_t* gate = nullptr);
 
 // emqx_shared_sub:dispatch/3 member pick (share.hip) over the same deliveries
 // CSR and slot geometry as launch_dispatch_count.
@@ -187,11 +202,25 @@ hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t s
 hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const uint8_t* bytes, const uint64_t* off,
                                uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
                                const uint32_t* tg, uint64_t slots, const uint32_t* pub_key, uint32_t* pick,
-                               uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st);
+                               uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st,
+                               const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr);
 hipError_t launch_share_compact(const uint32_t* flag, const uint64_t* P, const uint32_t* set, uint64_t slots,
                                 uint32_t* keys, uint32_t* vals, hipStream_t st);
 hipError_t launch_share_rr(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
                            const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur, hipStream_t st);
+// round robin with the number of pairs m = P[slots] known only on the device
+// (the stream-ordered publish call): the compaction pads the pairs from m to
+// rr_cap with key 0xFFFFFFFF (grid sized from the batch's n, grid-stride),
+// launch_sort_pairs runs over rr_cap pairs, and the pick and the store run
+// apart over rr_cap lanes bounded by *dm (the store is the call's last kernel)
+hipError_t launch_share_compact_pad(const uint32_t* flag, const uint64_t* P, const uint32_t* set, uint64_t slots,
+                                    uint32_t* keys, uint32_t* vals, uint64_t rr_cap, uint32_t n,
+                                    const uint64_t* dtotal, const uint64_t* gate, hipStream_t st);
+hipError_t launch_share_rr_pick(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
+                                const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur,
+                                const uint64_t* dm, const uint64_t* gate, hipStream_t st);
+hipError_t launch_share_rr_store(const ShareView& hv, const uint32_t* keys, const uint32_t* newcur, uint32_t m,
+                                 const uint64_t* dm, const uint64_t* gate, hipStream_t st);
 
 // A publish batch's results as dense records (pack.hip) over what
 // tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:
@@ -204,7 +233,8 @@ hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t
                                const uint32_t* tg, const uint32_t* ndisp, const uint32_t* pick, uint64_t out_cap,
                                const uint64_t* total, const uint32_t* sub_to, const uint32_t* sub_id, uint64_t sub_cap,
                                const uint64_t* sub_total, uint64_t* hdr, uint64_t* doff, void* deliv,
-                               uint64_t deliv_cap, void* pairs, uint64_t pair_cap, uint64_t* scan_tmp, hipStream_t st);
+                               uint64_t deliv_cap, void* pairs, uint64_t pair_cap, uint64_t* scan_tmp, hipStream_t st,
+                               const uint64_t* gate = nullptr);
 
 // Sharded mode (shard.hip): merge per-topic match lists of S filter shards
 // for m topics.  counts [S][m]; source s's items start at src_base[s] of

@@ -45,9 +45,10 @@ tm_publish_pack(uint32_t n, const uint32_t* __restrict__ count, const uint64_t* 
                 const uint32_t* __restrict__ sub_to, const uint32_t* __restrict__ sub_id, uint64_t sub_cap,
                 const uint64_t* __restrict__ sub_total, uint64_t* __restrict__ hdr, const uint64_t* __restrict__ doff,
                 uint4* __restrict__ deliv, uint64_t deliv_cap, uint2* __restrict__ pairs, uint64_t pair_cap,
-                uint32_t split) {
+                uint32_t split, const uint64_t* __restrict__ gate) {
     __shared__ uint64_t lds_inc[PKBLOCK];   // inclusive prefix of the block's delivery counts
     __shared__ uint64_t lds_scan[PKBLOCK / 64];
+    if (gate && *gate) return;   // a stage of a stream-ordered publish overflowed: tm_stream_finish writes the header
     const uint64_t rtotal = *total, ptotal = *sub_total;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         hdr[0] = rtotal;
@@ -96,7 +97,7 @@ hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t
                                const uint64_t* total, const uint32_t* sub_to, const uint32_t* sub_id, uint64_t sub_cap,
                                const uint64_t* sub_total, uint64_t* hdr, uint64_t* doff, void* deliv,
                                uint64_t deliv_cap, void* pairs, uint64_t pair_cap, uint64_t* scan_tmp,
-                               hipStream_t st) {
+                               hipStream_t st, const uint64_t* gate) {
     hipError_t err = launch_scan0(count, n, doff, doff + n, scan_tmp, st);
     if (err != hipSuccess) return err;
     if (n == 0) return hipMemsetAsync(hdr, 0, 32, st);
@@ -114,7 +115,50 @@ hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(tm_publish_pack, dim3((uint32_t)grid), dim3(PKBLOCK), 0, st, n, count, off, to, tg, ndisp, pick,
                        out_cap, total, sub_to, sub_id, sub_cap, sub_total, hdr, doff, (uint4*)deliv, deliv_cap,
-                       (uint2*)pairs, pair_cap, (uint32_t)split);
+                       (uint2*)pairs, pair_cap, (uint32_t)split, gate);
+    return hipGetLastError();
+}
+
+// ---- the state word of the stream-ordered publish call ----------------------
+// tm_publish_stream_device bounds every stage by a capacity given up front and
+// never reads a total back.  ctl is 8 u64 of its workspace, zeroed first:
+// ctl[0] = state (0, or the first stage whose total exceeded its capacity: 1
+// ids, 2 routes, 3 pairs, 4 round-robin slots), ctl[stage] = that stage's
+// total.  After a stage's total is known, tm_stream_check records it and sets
+// the state when it does not fit; it does nothing once the state is set, so
+// ctl holds exact totals up to and including the stage named and zeros after.
+// Every later kernel of the call gets &ctl[0] as its gate and leaves at once
+// when it is not 0: none reads a truncated predecessor.
+__global__ void tm_stream_check(uint64_t* __restrict__ ctl, uint32_t stage, const uint64_t* __restrict__ total,
+                                uint64_t cap) {
+    if (threadIdx.x != 0 || ctl[0]) return;
+    const uint64_t v = *total;
+    ctl[stage] = v;
+    if (v > cap) ctl[0] = stage;
+}
+// the call's header, after the pack: hdr[0..3] as tm_publish_pack writes them
+// when the state is 0 ({route total, pair total, D, P}); D = doff[n] is exact
+// whenever aggre ran (state 0, 3 or 4), else 0
+__global__ void tm_stream_finish(const uint64_t* __restrict__ ctl, const uint64_t* __restrict__ doff, uint32_t n,
+                                 uint64_t* __restrict__ hdr) {
+    if (threadIdx.x != 0) return;
+    const uint64_t state = ctl[0];
+    hdr[0] = ctl[2];
+    hdr[1] = ctl[3];
+    hdr[2] = (state == 0 || state >= 3) ? doff[n] : 0ull;
+    hdr[3] = ctl[3];
+    hdr[4] = ctl[1];
+    hdr[5] = ctl[4];
+    hdr[6] = state;
+    hdr[7] = 0;
+}
+
+hipError_t launch_stream_check(uint64_t* ctl, uint32_t stage, const uint64_t* total, uint64_t cap, hipStream_t st) {
+    hipLaunchKernelGGL(tm_stream_check, dim3(1), dim3(64), 0, st, ctl, stage, total, cap);
+    return hipGetLastError();
+}
+hipError_t launch_stream_finish(const uint64_t* ctl, const uint64_t* doff, uint32_t n, uint64_t* hdr, hipStream_t st) {
+    hipLaunchKernelGGL(tm_stream_finish, dim3(1), dim3(64), 0, st, ctl, doff, n, hdr);
     return hipGetLastError();
 }
 

@@ -52,10 +52,12 @@ __device__ __forceinline__ uint32_t topic_of(const uint32_t* lds_inc, uint32_t t
 __global__ void __launch_bounds__(RBLOCK)
 tm_route_count(RouteView rv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
                const uint32_t* __restrict__ counts, const uint64_t* __restrict__ ids_off,
-               const uint32_t* __restrict__ ids, uint4* __restrict__ exact, uint32_t* __restrict__ rcount) {
+               const uint32_t* __restrict__ ids, uint4* __restrict__ exact, uint32_t* __restrict__ rcount,
+               const uint64_t* __restrict__ gate) {
     __shared__ uint32_t lds_inc[RBLOCK];
     __shared__ uint32_t lds_mr[RBLOCK];
     __shared__ uint64_t lds_scan[RBLOCK / 64];
+    if (gate && *gate) return;   // stream-ordered publish: the ids did not fit their capacity (pack.hip tm_stream_check)
     const uint32_t t0 = blockIdx.x * RBLOCK;
     const uint32_t tn = n - t0 < (uint32_t)RBLOCK ? n - t0 : (uint32_t)RBLOCK;
     const uint32_t t = t0 + threadIdx.x;
@@ -87,10 +89,11 @@ tm_route_emit(RouteView rv, AggreView av, uint32_t n, const uint32_t* __restrict
               const uint64_t* __restrict__ ids_off, const uint32_t* __restrict__ ids,
               const uint4* __restrict__ exact, const uint32_t* __restrict__ rcount,
               const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_src, uint32_t* __restrict__ out_dest,
-              uint64_t* __restrict__ out_key, uint64_t out_cap) {
+              uint64_t* __restrict__ out_key, uint64_t out_cap, const uint64_t* __restrict__ gate) {
     __shared__ uint32_t lds_inc[RBLOCK];
     __shared__ uint64_t lds_m[RBLOCK];      // exclusive prefix of matched-route counts
     __shared__ uint64_t lds_scan[RBLOCK / 64];
+    if (gate && *gate) return;
     const uint32_t t0 = blockIdx.x * RBLOCK;
     const uint32_t tn = n - t0 < (uint32_t)RBLOCK ? n - t0 : (uint32_t)RBLOCK;
     const uint32_t t = t0 + threadIdx.x;
@@ -152,18 +155,18 @@ hipError_t launch_routes(const RouteView& rv, const uint8_t* bytes, const uint64
                          const uint32_t* counts, const uint64_t* ids_off, const uint32_t* ids, uint4* exact,
                          uint32_t* rcount, uint64_t* out_off, uint32_t* out_src, uint32_t* out_dest,
                          uint64_t out_cap, uint64_t* total, uint64_t* scan_tmp, hipStream_t st, const AggreView* av,
-                         uint64_t* out_key) {
+                         uint64_t* out_key, const uint64_t* gate) {
     if (n == 0) {
         hipError_t err = hipMemsetAsync(out_off, 0, 8, st);
         return err == hipSuccess ? hipMemsetAsync(total, 0, 8, st) : err;
     }
     const dim3 g(rdiv_up(n, RBLOCK)), blk(RBLOCK);
-    hipLaunchKernelGGL(tm_route_count, g, blk, 0, st, rv, bytes, off, n, counts, ids_off, ids, exact, rcount);
+    hipLaunchKernelGGL(tm_route_count, g, blk, 0, st, rv, bytes, off, n, counts, ids_off, ids, exact, rcount, gate);
     hipError_t err = launch_scan(rcount, n, out_off, total, scan_tmp, st);
     if (err != hipSuccess) return err;
     if (out_cap)
         hipLaunchKernelGGL(tm_route_emit, g, blk, 0, st, rv, av ? *av : AggreView{nullptr, nullptr, nullptr}, n, counts,
-                           ids_off, ids, exact, rcount, out_off, out_src, out_dest, av ? out_key : nullptr, out_cap);
+                           ids_off, ids, exact, rcount, out_off, out_src, out_dest, av ? out_key : nullptr, out_cap, gate);
     return hipGetLastError();
 }
 

@@ -63,9 +63,22 @@ tm_share_lookup(ShareView hv, uint32_t local_target, const uint8_t* __restrict__
                 const uint64_t* __restrict__ aoff, const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg,
                 uint64_t slots, const uint32_t* __restrict__ pub_key, uint32_t* __restrict__ pick,
                 uint32_t* __restrict__ cnt, uint32_t* __restrict__ seg, uint32_t* __restrict__ set,
-                uint32_t* __restrict__ flag) {
+                uint32_t* __restrict__ flag, const uint64_t* __restrict__ dtotal,
+                const uint64_t* __restrict__ gate) {
     __shared__ uint64_t lds_inc[HBLOCK];   // inclusive prefix of the block's spans
     __shared__ uint64_t lds_scan[HBLOCK / 64];
+    if (gate && *gate) return;   // an earlier stage of a stream-ordered publish overflowed (wave-uniform)
+    // dtotal: the route total on the device, `slots` the capacity (dispatch.hip
+    // tm_dispatch_count): flag is zero from the live slots to the capacity
+    const uint64_t cap = slots;
+    if (dtotal) {
+        const uint64_t r = *dtotal;
+        if (r < slots) slots = r;
+        if (flag)
+            for (uint64_t g = slots + (uint64_t)blockIdx.x * HBLOCK + threadIdx.x; g < cap;
+                 g += (uint64_t)gridDim.x * HBLOCK)
+                flag[g] = 0;
+    }
     const uint32_t t0 = blockIdx.x * HBLOCK;
     const uint32_t tn = n - t0 < (uint32_t)HBLOCK ? n - t0 : (uint32_t)HBLOCK;
     const uint32_t t = t0 + threadIdx.x;
@@ -137,13 +150,47 @@ tm_share_compact(const uint32_t* __restrict__ flag, const uint64_t* __restrict__
     vals[p] = g;
 }
 
+// the same for the stream-ordered publish call, which knows the number of
+// flagged slots m = P[slots] only on the device: `slots` is the capacity the
+// flags were scanned over (zero past the live slots), and the pairs are padded
+// from m to rr_cap with key 0xFFFFFFFF, so that the sort can run over rr_cap
+// pairs.  The sort is stable and the sentinel's digits are all 255: it stays
+// behind every real pair whichever bits are sorted.  m <= rr_cap: the call's
+// state word (gate) is set when it is not.  Grid-stride, the grid sized by the
+// launcher for the batch, not for the capacities.
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_compact_pad(const uint32_t* __restrict__ flag, const uint64_t* __restrict__ P,
+                     const uint32_t* __restrict__ set, uint32_t slots, uint32_t* __restrict__ keys,
+                     uint32_t* __restrict__ vals, uint32_t rr_cap, const uint64_t* __restrict__ dtotal,
+                     const uint64_t* __restrict__ gate) {
+    if (*gate) return;
+    const uint64_t tid = (uint64_t)blockIdx.x * HBLOCK + threadIdx.x, stride = (uint64_t)gridDim.x * HBLOCK;
+    const uint64_t m = P[slots];
+    const uint64_t live = *dtotal < slots ? *dtotal : slots;
+    for (uint64_t g = tid; g < live; g += stride)
+        if (flag[g]) {
+            const uint64_t p = P[g];
+            keys[p] = set[g];
+            vals[p] = (uint32_t)g;
+        }
+    for (uint64_t p = m + tid; p < rr_cap; p += stride) {
+        keys[p] = 0xFFFFFFFFu;
+        vals[p] = 0;
+    }
+}
+
 // one lane per sorted pair: rank in its run, the pick, and for the last pair
 // of a run the cursor the run leaves (newcur[p], 0xFFFFFFFF for every other
 // pair: a stored Rem is below its Count, never that value)
 __global__ void __launch_bounds__(HBLOCK)
 tm_share_rr_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t m,
                  const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ seg, uint32_t* __restrict__ pick,
-                 uint32_t* __restrict__ newcur) {
+                 uint32_t* __restrict__ newcur, const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;
+    // dm: the number of pairs on the device (the stream-ordered call sorts its
+    // capacity of pairs, padded with the sentinel key): the pairs past it are
+    // neither ranked nor given a newcur entry
+    if (dm && *dm < m) m = (uint32_t)*dm;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;   // m <= 2^32 - 2: the grid never wraps p
     const bool valid = p < m;
@@ -185,7 +232,10 @@ tm_share_rr_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t
 }
 
 __global__ void __launch_bounds__(HBLOCK)
-tm_share_rr_store(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ newcur, uint32_t m) {
+tm_share_rr_store(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ newcur, uint32_t m,
+                  const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;   // the batch did not fit: no cursor changes, its rerun picks what a first run would
+    if (dm && *dm < m) m = (uint32_t)*dm;
     const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;
     if (p >= m) return;
     const uint32_t v = newcur[p];
@@ -197,10 +247,11 @@ static inline uint32_t hdiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + 
 hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const uint8_t* bytes, const uint64_t* off,
                                uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
                                const uint32_t* tg, uint64_t slots, const uint32_t* pub_key, uint32_t* pick,
-                               uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st) {
+                               uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st,
+                               const uint64_t* dtotal, const uint64_t* gate) {
     if (n == 0 || slots == 0) return hipSuccess;
     hipLaunchKernelGGL(tm_share_lookup, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, local_target, bytes, off, n,
-                       acount, aoff, to, tg, slots, pub_key, pick, cnt, seg, set, flag);
+                       acount, aoff, to, tg, slots, pub_key, pick, cnt, seg, set, flag, dtotal, gate);
     return hipGetLastError();
 }
 
@@ -212,12 +263,42 @@ hipError_t launch_share_compact(const uint32_t* flag, const uint64_t* P, const u
     return hipGetLastError();
 }
 
+hipError_t launch_share_compact_pad(const uint32_t* flag, const uint64_t* P, const uint32_t* set, uint64_t slots,
+                                    uint32_t* keys, uint32_t* vals, uint64_t rr_cap, uint32_t n,
+                                    const uint64_t* dtotal, const uint64_t* gate, hipStream_t st) {
+    if (rr_cap == 0) return hipSuccess;   // m > 0 is then an overflow: nothing to compact
+    // a thread for about sixteen slots of the batch's usual fan-out; the loops stride over whatever is there
+    uint32_t blocks = hdiv_up((uint64_t)n + 1, 16);
+    if (blocks > 1024u) blocks = 1024u;
+    hipLaunchKernelGGL(tm_share_compact_pad, dim3(blocks), dim3(HBLOCK), 0, st, flag, P, set, (uint32_t)slots, keys,
+                       vals, (uint32_t)rr_cap, dtotal, gate);
+    return hipGetLastError();
+}
+
 hipError_t launch_share_rr(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
                            const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur, hipStream_t st) {
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(tm_share_rr_pick, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, vals, m, cnt, seg,
-                       pick, newcur);
-    hipLaunchKernelGGL(tm_share_rr_store, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, newcur, m);
+                       pick, newcur, nullptr, nullptr);
+    hipLaunchKernelGGL(tm_share_rr_store, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, newcur, m, nullptr,
+                       nullptr);
+    return hipGetLastError();
+}
+
+// the two halves apart for the stream-ordered publish call: m = the pair
+// capacity, *dm the pairs there are; the store is that call's last kernel
+hipError_t launch_share_rr_pick(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
+                                const uint32_t* cnt, const uint32_t* seg, uint32_t* pick, uint32_t* newcur,
+                                const uint64_t* dm, const uint64_t* gate, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_rr_pick, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, vals, m, cnt, seg,
+                       pick, newcur, dm, gate);
+    return hipGetLastError();
+}
+hipError_t launch_share_rr_store(const ShareView& hv, const uint32_t* keys, const uint32_t* newcur, uint32_t m,
+                                 const uint64_t* dm, const uint64_t* gate, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_rr_store, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, newcur, m, dm, gate);
     return hipGetLastError();
 }
 

@@ -45,3 +45,8 @@ class SharedSub:
     def cleanup_down(self, sub: int):
         self.engine.share_member_down(sub)
         return "ok"
+
+    def cursors(self, replica=0):
+        """one publisher process's round-robin dictionary (:243-249) on a
+        replica, for Engine.publish_stream_device; close() it before the engine"""
+        return self.engine.share_cursors(replica)

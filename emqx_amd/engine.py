@@ -714,6 +714,36 @@ class Engine:
                                              p(d_pairs), pair_cap, st)
         return self._check(rc, "tm_publish_pack_device")
 
+    def share_cursors(self, replica=0):
+        """tm_share_cursors_open: one publisher's round-robin dictionary on a replica"""
+        return ShareCursors(self, replica)
+
+    def publish_stream_workspace_bytes(self, n, topic_bytes, caps):
+        """caps: (ids, routes, pairs, rr)"""
+        c = L.TmPublishCaps(*[int(x) for x in caps])
+        return int(self.lib.tm_publish_stream_workspace_bytes(self.h, n, topic_bytes, ctypes.byref(c)))
+
+    def publish_stream_device(self, d_bytes, d_off, n, topic_bytes, strategy, d_keys, cursors, caps, d_workspace,
+                              workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, stream=None):
+        """tm_publish_stream_device over device pointers (tensors or ints; None
+        = NULL): publish/1 up to the sends, enqueued on `stream` without a
+        host wait.  caps: (ids, routes, pairs, rr); cursors: a ShareCursors or
+        None (the replica's built-in array).  The header's state word says
+        whether every stage fitted."""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        c = L.TmPublishCaps(*[int(x) for x in caps])
+        rc = self.lib.tm_publish_stream_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, strategy, p(d_keys),
+                                               cursors.h if cursors is not None else None, ctypes.byref(c),
+                                               p(d_workspace), workspace_bytes, p(d_hdr), p(d_doff), p(d_sub_off),
+                                               p(d_deliv), p(d_pairs), st)
+        return self._check(rc, "tm_publish_stream_device")
+
     # walk variants (A/B knobs of tm_walk_queue): one global dequeue head, or
     # per-XCD heads over contiguous ranges of the batch
     WALKS = {"queue": 0, "queue_xcd": 1}
@@ -743,3 +773,29 @@ class Engine:
         if k < 0:
             self._check(k, "tm_last_kernel_times")
         return {names[i].decode(): ms[i] for i in range(k)}
+
+
+class ShareCursors:
+    """One publisher process's round-robin cursors on one replica
+    (tm_share_cursors; src/emqx_shared_sub.erl:243-249).  Close it before the
+    engine; closing it afterwards only frees the host handle."""
+
+    def __init__(self, engine, replica=0):
+        self.lib = engine.lib
+        self.replica = replica
+        h = ctypes.c_void_p()
+        rc = self.lib.tm_share_cursors_open(engine.h, replica, ctypes.byref(h))
+        if rc != L.TM_OK:
+            raise L.TopicMatchError(rc, "tm_share_cursors_open")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.lib.tm_share_cursors_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -692,9 +692,11 @@ uint64_t tm_share_count(tm_engine* e);
  * touching its cursor (:231); otherwise Rem = 0 on the first use and (N + 1)
  * rem Count after (:243-249), with the Count of the image the batch runs on
  * (also when N >= Count after a shrink).  Two deviations: the reference keeps
- * the cursor per publisher process (erlang:get), the engine per set -- equal
- * for one publisher --; and a set that loses its last member forgets its
- * cursor, which the reference never erases.
+ * the cursor per publisher process (erlang:get), these calls per set on the
+ * replica's built-in array -- equal for one publisher; a tm_share_cursors
+ * context per publisher with tm_publish_stream_device (below) removes this
+ * one --; and a set that loses its last member forgets its cursor, which the
+ * reference never erases.
  *
  * Host buffers: TM_ENOSPC as tm_match_dispatch_batch; such a call writes no
  * out_pick and advances no cursor, so its retry picks what a first call
@@ -749,6 +751,102 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
                            tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
                            void* hip_stream);
 
+/* ---- round-robin cursor contexts ---------------------------------------------
+ * do_pick_subscriber(Group, Topic, round_robin, _ClientId, Count) keeps its
+ * counter in the PUBLISHER's process dictionary, under {shared_sub_round_robin,
+ * Group, Topic} (src/emqx_shared_sub.erl:243-249): every publisher process
+ * walks every set from Rem 0 on its own.  A tm_share_cursors is one such
+ * dictionary on one replica: a u32 per set index in that GPU's memory,
+ * 0xFFFFFFFF = undefined (erlang:get/1 -> undefined).  The engine keeps the
+ * open contexts of a replica beside its built-in array and treats each as it
+ * treats that one: tm_commit grows them to cover every set index handed out
+ * (contents kept, after the batches that could still write the old array),
+ * and the commit that frees a set index resets it in every context, so an
+ * index is reused only after both image epochs dropped its set and no context
+ * remembers it.  A context opened after sets exist starts all-undefined.  Two
+ * contexts are independent: each one's first use of a set gives Rem 0.  With
+ * one context per publisher the first deviation listed at TM_SHARE_ROUND_ROBIN
+ * (cursor per set instead of per publisher) is gone.
+ * TM_EDEVICE on a host-only engine, TM_EINVAL for a replica out of range.
+ * Order of closing: close a context before its engine.  tm_close with
+ * contexts still open waits for the device, releases their device memory
+ * with the replica and leaves each context detached; tm_share_cursors_close
+ * of a detached context only frees the host struct (no device call, no
+ * double free), and must still be called once.  A detached context is
+ * refused by every call (TM_EINVAL). */
+typedef struct tm_share_cursors tm_share_cursors;
+int  tm_share_cursors_open(tm_engine* e, uint32_t replica, tm_share_cursors** out);
+/* waits for the replica's batches in flight, then releases the array */
+void tm_share_cursors_close(tm_share_cursors* c);
+
+/* publish/1 up to the sends (src/emqx_broker.erl:148-157, 175-192;
+ * src/emqx_shared_sub.erl:89-111, 228-249), stream-ordered: what
+ * tm_match_publish_batch_device followed by tm_publish_pack_device compute,
+ * without a host wait.  Between entry and return the call only enqueues work
+ * on hip_stream: no stream synchronisation, no read-back, no wait for other
+ * streams' batches and no allocation of a replica workspace (the walk takes
+ * the replica's next slot exactly as tm_match_batch_device does; the other
+ * launchers on the way read nothing back either -- aggre's list of large
+ * topics is built and consumed on the device).  Every intermediate (match
+ * counts / offsets / ids, route planes and aggre keys, per-slot dispatch and
+ * share arrays, scan temporaries, the sort's ping-pong and counters, the new
+ * cursors) lives in d_workspace, tm_publish_stream_workspace_bytes(n,
+ * topic_bytes, caps) bytes of the device that owns d_topic_off (non-decreasing
+ * in n and in each capacity; 0 for null or out-of-range caps).
+ *
+ * Each stage is bounded by a capacity given up front:
+ *   caps.ids     match ids (emqx_trie:match/1 total)
+ *   caps.routes  the match_routes/1 total = delivery slots (aggre writes each
+ *                topic's list at its route offset) = records of d_deliv
+ *   caps.pairs   (To, subscriber) pairs = records of d_pairs
+ *   caps.rr      delivery slots with Count >= 2 that round robin ranks
+ *                (ignored for TM_SHARE_KEYED)
+ * each below 2^32 - 2 (TM_ERANGE).  d_hdr[TM_PUBLISH_HDR_WORDS]:
+ *   [0..3] {route total, pair total, D, P} as tm_publish_pack_device
+ *   [4]    match id total        [5] slots ranked by round robin (0 for keyed)
+ *   [6]    state: 0 = every stage ran within its capacity, else the first
+ *          stage whose total exceeded it: 1 ids, 2 routes, 3 pairs, 4 rr
+ *   [7]    0
+ * State 0: d_hdr[0..3], d_doff[n+1], d_sub_off[n+1], the D records and the P
+ * pairs are bit for bit what the two calls above leave with out_cap =
+ * deliv_cap = caps.routes and sub_cap = pair_cap = caps.pairs; the picks
+ * follow TM_SHARE_KEYED / TM_SHARE_ROUND_ROBIN as documented at
+ * tm_match_publish_batch, with `cursors` as the publisher's dictionary (NULL:
+ * the replica's built-in array, the one tm_match_publish_batch_device uses).
+ * Round-robin publishes count in topic-index order within the call and in
+ * stream order between calls.
+ * State != 0: the totals of the stages up to and including the one named are
+ * exact (and D whenever the state is 3 or 4), later totals are 0, d_doff,
+ * d_sub_off and the records are unspecified, nothing has been written at or
+ * past any capacity in outputs or workspace, and NO CURSOR HAS CHANGED: a
+ * state word in the workspace is set once a stage's total is known, every
+ * later kernel tests it first and leaves, and the store of the new cursors is
+ * the call's last kernel and runs only in state 0.  The caller sizes a rerun
+ * from the header; the rerun picks what a first run would have.
+ * The radix sort of the (set index, slot) pairs runs over caps.rr pairs padded
+ * with key 0xFFFFFFFF, over the bits the set indices need: the padding's
+ * digits are all 255 and the sort is stable, so it stays last.
+ * Two calls in flight on different streams must not share a context (nor
+ * both pass NULL with round robin): the second would read cursors the first
+ * has not stored yet.  Calls on one stream may.
+ * n == 0: a zero header and d_doff[0] = d_sub_off[0] = 0.
+ * TM_EINVAL: a null d_topic_off, d_hdr, d_doff, d_sub_off, caps or
+ * d_workspace; a null d_pub_key with TM_SHARE_KEYED (n > 0); caps.routes with
+ * a null d_deliv or caps.pairs with a null d_pairs; a strategy that is neither
+ * of the two; workspace_bytes below the need (all before anything is
+ * enqueued); tm_set_local_node not called; a context of another engine or
+ * replica than the one that owns d_topic_off.  TM_EDEVICE on a host-only
+ * engine. */
+typedef struct tm_publish_caps { uint64_t ids, routes, pairs, rr; } tm_publish_caps;
+#define TM_PUBLISH_HDR_WORDS 8
+uint64_t tm_publish_stream_workspace_bytes(tm_engine* e, uint32_t n, uint64_t topic_bytes,
+                                           const tm_publish_caps* caps);
+int tm_publish_stream_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off, uint32_t n,
+                             uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                             tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                             uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                             tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream);
+
 /* ---- publish micro-batcher (emqx_amd/csrc/batcher.cpp) -----
  * emqx_broker:publish/1 (src/emqx_broker.erl:148-157) matches one topic per
  * call in the publisher's process.  The NIF instead submits the topic here
@@ -779,8 +877,30 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
  * pairs its header could not count).  The pick strategy is TM_SHARE_KEYED with
  * the pub_key of each submit: `hash` with phash2(ClientId), `random` with a
  * fresh draw.  Keyed picks are stateless, so a rerun returns what a first run
- * would have.  Round robin (and `sticky`) are deliberately not offered here:
- * a rerun would advance the set cursors twice.  Such a batcher takes
+ * would have.
+ * TM_BATCHER_ROUND_ROBIN (with TM_BATCHER_PUBLISH, else tm_batcher_open:
+ * TM_EINVAL): the picks are `round_robin`, the reference's default strategy
+ * (emqx_shared_sub:strategy/0, src/emqx_shared_sub.erl:113-115), and pub_key
+ * is ignored.  A LANE IS A PUBLISHER PROCESS, the granularity at which the
+ * reference keeps its counters (:243-249): each lane opens one
+ * tm_share_cursors on its replica and closes it with the batcher, and the
+ * batches of one lane count on from each other; with lanes_per_replica = 1 on
+ * one GPU the batcher is one publisher.  Such a batcher runs
+ * tm_publish_stream_device, whose capacities follow four running means (match
+ * ids, routes, pairs and ranked slots per topic; workspace and outputs
+ * reserved at open for the first batch); when the header's state names a
+ * stage, that capacity grows to the exact total it reports (plus a quarter)
+ * and the batch runs again, at worst once per stage.  The rule that makes this
+ * safe replaces the old refusal: the call stores its new cursors in its last
+ * kernel and only when every stage fitted, so a batch that is rerun has not
+ * moved any cursor and its rerun picks what a first run would have.  The
+ * read-back is as above: header, offsets and (small batches) records in one
+ * copy and one stream synchronisation per pass.
+ * TM_BATCHER_STREAM (with TM_BATCHER_PUBLISH, else TM_EINVAL): a keyed batcher
+ * runs tm_publish_stream_device instead of the two calls above and returns
+ * the same records.  An A/B switch like TM_BATCHER_CSR, not a tuning knob: the
+ * next change keeps one of the two keyed paths, on the measurements.
+ * `sticky` stays with the caller.  A publish batcher takes
  * tm_batcher_submit_publish only (tm_batcher_submit: TM_EINVAL, nothing
  * queued), and tm_batcher_submit_publish needs the flag (else TM_EINVAL).
  * done() gets topic's delivery records {to, target, ndisp, pick} in aggre's
@@ -803,6 +923,8 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
                                  free lane was 4 ms at 1M publishes/s) */
 #define TM_BATCHER_EAGER_TOPICS 256u
 #define TM_BATCHER_PUBLISH 16u   /* results are publish/1 up to the sends: deliveries with Count and pick, and the pairs */
+#define TM_BATCHER_ROUND_ROBIN 32u   /* publish mode: round-robin picks, one cursor context per lane */
+#define TM_BATCHER_STREAM 64u   /* publish mode: keyed picks through tm_publish_stream_device (A/B) */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {
@@ -831,6 +953,9 @@ typedef struct tm_batcher_stats {
      * round-4 header, whose struct ends before them, keeps calling
      * tm_batcher_get_stats, which writes exactly that prefix) */
     uint64_t max_wait_ns, max_pack_ns, max_device_ns, max_callback_ns, max_sync_ns;
+    /* passes beyond a batch's first, summed over batches (a publish batch
+     * that did not fit its capacities runs again); tm_batcher_get_stats2 only */
+    uint64_t reruns;
 } tm_batcher_stats;
 #define TM_BATCHER_STATS_V1_BYTES (13u * 8u)   /* the prefix tm_batcher_get_stats writes */
 #define TM_BATCHER_STATS_RESET_MAX 1u          /* tm_batcher_get_stats2: zero the max_* fields after this read */

@@ -16,6 +16,10 @@ Per batch: device_us split into launch_us and sync_us, and packed_bytes, the
 header, offsets and records a publish batch brings back (a batch of up to
 32768 topics reads up to its capacities instead, about 1.25 x + 24 KiB).
 --legs deliveries runs on a commit without the publish mode (the baseline).
+Two further legs ride the publish leg's workload: publish_stream, the same
+keyed picks through tm_publish_stream_device (TM_BATCHER_STREAM), and
+publish_rr, round robin with one cursor context per lane
+(TM_BATCHER_ROUND_ROBIN); every leg reports its reruns.
 
 Run: python tools/bench_batcher.py --publish [--topics 1000000 --rate 1e6 --rounds 3 --out FILE]"""
 import argparse
@@ -34,6 +38,7 @@ from emqx_amd import workload as W  # noqa: E402
 
 
 NODE = b"emqx@node00"
+LEGS = {"deliveries": 0, "publish": 1, "publish_stream": 2, "publish_rr": 3}   # tools/ubench/pubdrive.cpp
 GROUPS = [b"grp%d" % i for i in range(8)]
 HOT = [b"hot0", b"hot1"]
 
@@ -94,11 +99,11 @@ def publish_main(a):
     for rnd in range(a.rounds):
         for leg in a.legs.split(","):
             for run in a.runs.split(","):
-                res = (ctypes.c_double * 14)()
+                res = (ctypes.c_double * 16)()
                 flood = run == "flood"
                 rc = drv.tm_bench_publish(e.h, tb.ctypes.data, to.ctypes.data, n, 16, 0.0 if flood else a.rate,
                                           0 if flood else int(a.rate * a.secs), 200,
-                                          int(a.max_topics.split(",")[0]), 4, int(leg == "publish"),
+                                          int(a.max_topics.split(",")[0]), 4, LEGS[leg],
                                           0 if flood else 1, res)
                 mean_batch, results = res[3], res[13]
                 line = {"leg": leg, "run": run, "round": rnd, "rc": rc, "filters": nf, "topics": n,
@@ -107,9 +112,10 @@ def publish_main(a):
                         "batches": int(res[2]), "mean_batch": mean_batch, "lat_us_p50": res[4], "lat_us_p99": res[5],
                         "failed": int(res[6]), "deliveries_per_topic": res[7], "pairs_per_topic": res[8],
                         "per_batch": {"device_us": res[9], "launch_us": res[10], "sync_us": res[11],
-                                      "callbacks_us": res[12], "results": results}}
-                if leg == "publish":    # header + both offset arrays + 16 B records + 8 B pairs
-                    line["per_batch"]["packed_bytes"] = 32 + 16 * (mean_batch + 1) + 16 * results + \
+                                      "callbacks_us": res[12], "results": results},
+                        "reruns": int(res[14])}
+                if leg != "deliveries":    # header + both offset arrays + 16 B records + 8 B pairs
+                    line["per_batch"]["packed_bytes"] = (32 if leg == "publish" else 64) + 16 * (mean_batch + 1) + 16 * results + \
                         8 * res[8] * mean_batch
                 else:                   # total + counts + offsets + To ids + target ids
                     line["per_batch"]["result_bytes"] = 8 + 4 * mean_batch + 8 * (mean_batch + 1) + 8 * results
@@ -126,7 +132,7 @@ def publish_main(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--publish", action="store_true", help="deliveries and publish batchers on the C2 publish world")
-    ap.add_argument("--legs", default="deliveries,publish")
+    ap.add_argument("--legs", default="deliveries,publish,publish_stream,publish_rr")
     ap.add_argument("--runs", default="flood,paced")
     ap.add_argument("--rate", type=float, default=1e6)
     ap.add_argument("--secs", type=float, default=1.0)

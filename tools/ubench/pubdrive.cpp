@@ -49,13 +49,14 @@ inline int submit(tm_batcher* b, bool publish, const uint8_t* t, uint32_t len, u
 }
 }  // namespace
 
-// publish != 0: TM_BATCHER_PUBLISH (TM_EINVAL when built without it), else
+// publish != 0: TM_BATCHER_PUBLISH (TM_EINVAL when built without it) -- 2: with
+// TM_BATCHER_STREAM, 3: with TM_BATCHER_ROUND_ROBIN --, else
 // TM_BATCHER_DELIVERIES; `eager`: TM_BATCHER_EAGER.  rate 0: a flood of the nt
 // topics; else `total` publishes at `rate` per second (the batch cycled).
-// out[14]: seconds, topics/s, batches, mean batch, p50 us, p99 us, failed,
+// out[15]: seconds, topics/s, batches, mean batch, p50 us, p99 us, failed,
 // delivery records and pairs per timed topic (means), then per batch (us):
-// device path, its enqueue and its wait, callbacks, and the stats' results
-// per batch
+// device path, its enqueue and its wait, callbacks, the stats' results
+// per batch, and the reruns of the timed part
 extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t* to, uint64_t nt, int producers,
                                 double rate, uint64_t total, uint32_t deadline_us, uint32_t max_topics,
                                 uint32_t lanes, int publish, int eager, double* out) {
@@ -66,6 +67,12 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     bc.flags = (eager ? TM_BATCHER_EAGER : 0u);
 #ifdef TM_BATCHER_PUBLISH
     bc.flags |= publish ? TM_BATCHER_PUBLISH : TM_BATCHER_DELIVERIES;
+#ifdef TM_BATCHER_STREAM
+    if (publish == 2) bc.flags |= TM_BATCHER_STREAM;
+    if (publish == 3) bc.flags |= TM_BATCHER_ROUND_ROBIN;
+#else
+    if (publish > 1) return TM_EINVAL;
+#endif
 #else
     if (publish) return TM_EINVAL;
     bc.flags |= TM_BATCHER_DELIVERIES;
@@ -92,7 +99,7 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     const uint64_t settle = rate > 0 ? (uint64_t)(rate * 0.1) : 0;   // 100 ms at the offered rate, unmeasured
     total += settle;
     std::vector<Rec> recs(total / LAT_EVERY + 1);
-    tm_batcher_stats st0;
+    tm_batcher_stats st0{};
     tm_batcher_get_stats2(b, &st0, sizeof st0, TM_BATCHER_STATS_RESET_MAX);
     const auto t_begin = clk::now();
     const auto t0 = t_begin + std::chrono::milliseconds(2);
@@ -134,7 +141,7 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     for (auto& x : th) x.join();
     tm_batcher_flush(b);
     const double secs = std::chrono::duration<double>(clk::now() - t_meas).count();
-    tm_batcher_stats st;
+    tm_batcher_stats st{};
     tm_batcher_get_stats2(b, &st, sizeof st, TM_BATCHER_STATS_RESET_MAX);
     tm_batcher_close(b);
     std::vector<int64_t> lat;
@@ -159,5 +166,10 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     out[11] = (st.sync_ns - st0.sync_ns) / nb / 1e3;
     out[12] = (st.callback_ns - st0.callback_ns) / nb / 1e3;
     out[13] = (double)(st.results - st0.results) / nb;
+#ifdef TM_BATCHER_STREAM
+    out[14] = (double)(st.reruns - st0.reruns);
+#else
+    out[14] = 0;
+#endif
     return TM_OK;
 }
