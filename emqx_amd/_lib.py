@@ -99,6 +99,7 @@ TM_BATCHER_CSR = 8
 TM_BATCHER_PUBLISH = 16
 TM_BATCHER_ROUND_ROBIN = 32
 TM_BATCHER_STREAM = 64
+TM_BATCHER_STICKY = 128
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
 
@@ -309,6 +310,9 @@ SIGNATURES = [
                                                 ctypes.POINTER(TmPublishCaps), ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_share_pick_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("tm_batcher_open", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,

@@ -7,7 +7,8 @@ routes, or (deliveries=True) aggre(match_routes/1): To ids + target ids, or
 (publish=True, submit_publish) publish/1 up to the sends: the deliveries with
 their dispatch Count and $share pick, and the (To, subscriber) pairs; with
 round_robin=True the picks are the reference's default strategy, each lane a
-publisher process with its own cursors, and stream=True runs the keyed picks
+publisher process with its own cursors (sticky=True: `sticky` picks, a lane
+likewise a publisher with its own entries), and stream=True runs the keyed picks
 through tm_publish_stream_device too (an A/B switch).  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
@@ -21,12 +22,13 @@ from . import _lib as L
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
                  lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0, round_robin=False,
-                 stream=False):
+                 stream=False, sticky=False):
         self.engine = engine
         self.lib = engine.lib
         flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
             (L.TM_BATCHER_PUBLISH if publish else 0) | (L.TM_BATCHER_EAGER if eager else 0) | \
-            (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0)
+            (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0) | \
+            (L.TM_BATCHER_STICKY if sticky else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
         rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))

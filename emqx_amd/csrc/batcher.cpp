@@ -210,6 +210,7 @@ struct tm_batcher {
     bool publish = false;   // TM_BATCHER_PUBLISH
     bool stream = false;    // ... through tm_publish_stream_device (TM_BATCHER_STREAM, TM_BATCHER_ROUND_ROBIN)
     bool round_robin = false;
+    bool sticky = false;    // TM_BATCHER_STICKY: sticky picks, a context per lane as with round robin
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -624,7 +625,7 @@ struct tm_batcher {
     static uint64_t cap_of(double per_topic, uint64_t n) { return (uint64_t)(per_topic * n * 1.25) + 1024; }
     tm_publish_caps stream_caps(const Lane& L, uint64_t n) const {
         return tm_publish_caps{cap_of(L.ids_per_topic, n), cap_of(L.deliv_per_topic, n), cap_of(L.pairs_per_topic, n),
-                               round_robin ? cap_of(L.rr_per_topic, n) : 0};
+                               (round_robin || sticky) ? cap_of(L.rr_per_topic, n) : 0};
     }
     int run_publish_stream(Lane& L, uint64_t& results) {
         auto chk = [](hipError_t e) { return e == hipSuccess; };
@@ -653,7 +654,10 @@ struct tm_batcher {
             if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? outb : head)) return TM_ENOMEM;
             uint8_t* d = (uint8_t*)L.d_out.p;
             const int rc = tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes,
-                                                    round_robin ? TM_SHARE_ROUND_ROBIN : TM_SHARE_KEYED, d_key,
+                                                    round_robin ? TM_SHARE_ROUND_ROBIN
+                                                    : sticky    ? TM_SHARE_STICKY
+                                                                : TM_SHARE_KEYED,
+                                                    d_key,
                                                     L.cursors, &caps, L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
                                                     (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
                                                     (tm_pair*)(d + head + cap * 16), s);
@@ -672,7 +676,7 @@ struct tm_batcher {
             mean(L.ids_per_topic, hdr[4]);
             if (state == 0 || state >= 2) mean(L.deliv_per_topic, hdr[0]);
             if (state == 0 || state >= 3) mean(L.pairs_per_topic, hdr[1]);
-            if (round_robin && (state == 0 || state == 4)) mean(L.rr_per_topic, hdr[5]);
+            if ((round_robin || sticky) && (state == 0 || state == 4)) mean(L.rr_per_topic, hdr[5]);
             if (state == 0) {
                 if (!eager) {   // exactly D deliveries and P pairs
                     if (!L.h_out.ensure(outb)) return TM_ENOMEM;   // may move: the head is read again below
@@ -991,12 +995,17 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
         delete b;
         return TM_EINVAL;
     }
-    if (!b->publish && (b->cfg.flags & (TM_BATCHER_ROUND_ROBIN | TM_BATCHER_STREAM))) {
+    if (!b->publish && (b->cfg.flags & (TM_BATCHER_ROUND_ROBIN | TM_BATCHER_STREAM | TM_BATCHER_STICKY))) {
+        delete b;
+        return TM_EINVAL;
+    }
+    if ((b->cfg.flags & TM_BATCHER_STICKY) && (b->cfg.flags & TM_BATCHER_ROUND_ROBIN)) {   // one strategy
         delete b;
         return TM_EINVAL;
     }
     b->round_robin = (b->cfg.flags & TM_BATCHER_ROUND_ROBIN) != 0;
-    b->stream = b->round_robin || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
+    b->sticky = (b->cfg.flags & TM_BATCHER_STICKY) != 0;
+    b->stream = b->round_robin || b->sticky || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
@@ -1031,8 +1040,8 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
             delete b;
             return TM_EDEVICE;
         }
-        // a lane is a publisher process: its own round-robin dictionary on its replica
-        if (b->round_robin && L->device >= 0 &&
+        // a lane is a publisher process: its own dictionary (cursors and sticky entries) on its replica
+        if ((b->round_robin || b->sticky) && L->device >= 0 &&
             tm_share_cursors_open(e, k % (uint32_t)devs.size(), &L->cursors) != TM_OK) {
             if (L->stream) (void)hipStreamDestroy(L->stream);
             b->shutdown_lanes();

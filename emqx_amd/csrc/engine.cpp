@@ -461,6 +461,7 @@ struct Image {
     // cursors (DevState::sh_cursor) as they were when this image was written
     DevBuf d_hsets, d_htx, d_harena, d_hpool, d_hfx;
     uint32_t* cursor = nullptr;
+    uint32_t* sticky = nullptr;   // the replica's sticky entries (DevState::sh_sticky), likewise
     DevBuf d_wheat;    // word id -> heat (option "presort" 2: the tail order's cost estimate)
     size_t arena_uploaded = 0, woff_uploaded = 0;
     uint64_t heat_uploaded = ~0ull;   // word_heat version in d_wheat
@@ -577,12 +578,18 @@ struct DevState {
     // the runs' new cursors, and the host-buffer call's keys and picks
     DevBuf w_hcnt, w_hseg, w_hset, w_hflag, w_hpre, w_hscan, w_hpairs, w_hnew, w_hcounts, w_hoff, w_hsscan, w_hkey,
         w_hpick;
+    // sticky: the flagged slots' keys; tm_share_pick_batch: the requests' group
+    // targets, failed lists and offsets; commit: the sorted downed members
+    DevBuf w_hkplane, w_htg, w_hfail, w_hfoff, w_hdown;
     DevBuf w_pscan;   // publish pack (pack.hip): the scan of the topics' delivery counts
     // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
     // the image epochs, so a batch continues where the one before it stopped
     // whichever image each was launched on
     DevBuf sh_cursor;
     uint32_t sh_cursor_n = 0;   // entries
+    // {shared_sub_sticky, Group, Topic} per set index beside the cursor (a
+    // member id, 0xFFFFFFFF = undefined): same length, same upkeep
+    DevBuf sh_sticky;
     // the open cursor contexts of this replica (tm_share_cursors_open): one
     // more such array each, kept by commit exactly as sh_cursor is
     std::vector<tm_share_cursors*> cursor_ctx;
@@ -628,7 +635,8 @@ struct DevState {
                           &w_alarge, &w_mpre, &w_mscan, &w_bytes, &w_off, &w_counts, &w_outoff, &w_ids, &w_total,
                           &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
                           &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
-                          &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor,
+                          &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor, &sh_sticky, &w_hkplane,
+                          &w_htg, &w_hfail, &w_hfoff, &w_hdown,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -668,13 +676,14 @@ struct DevState {
 
 // One publisher process's {shared_sub_round_robin, Group, Topic} dictionary
 // (src/emqx_shared_sub.erl:243-249) on one replica: a u32 per set index,
-// 0xFFFFFFFF = undefined.  e == nullptr: the engine was closed first and took
+// 0xFFFFFFFF = undefined; sbuf: its {shared_sub_sticky, Group, Topic} entries
+// (:212, :222), as many.  e == nullptr: the engine was closed first and took
 // the device memory with it; only the host struct is left to delete.
 struct tm_share_cursors {
     tm_engine* e = nullptr;
     uint32_t replica = 0;
-    DevBuf buf;
-    uint32_t n = 0;   // entries
+    DevBuf buf, sbuf;
+    uint32_t n = 0;   // entries (of each)
 };
 
 struct tm_engine {
@@ -965,6 +974,7 @@ struct tm_engine {
     // member -> the sets that hold it: cleanup_down/1 without a table scan,
     // and the bag's "already present" test
     std::unordered_map<uint32_t, std::vector<ShareSet*>> sh_member_sets;
+    std::vector<uint32_t> sh_downed;   // tm_share_member_down since the last commit (sticky reset at commit)
     size_t sh_total = 0;
     // The share image, kept in place like the subscriber image: the set table
     // (sh_sets: (group target, xid) -> {Count, segment, set index}), the
@@ -1990,6 +2000,10 @@ struct tm_engine {
     }
     // cleanup_down/1 (:316-321): every record of the member, whatever the group or topic
     uint32_t share_member_down(uint32_t member) {
+        // the process exited: the next commit resets the sticky entries equal
+        // to it, also when it has no record left
+        sh_downed.push_back(member);
+        dev_dirty = true;
         auto mi = sh_member_sets.find(member);
         if (mi == sh_member_sets.end()) return 0;
         const std::vector<ShareSet*> of = std::move(mi->second);
@@ -2025,6 +2039,7 @@ struct tm_engine {
         hv.fx = g.d_hfx.as<const uint32_t>();
         hv.n_filters = (uint32_t)sh_fx.meta.size();
         hv.cursor = g.cursor;
+        hv.sticky = g.sticky;
         hv.n_sets = sh_next_six;
         return hv;
     }
@@ -2040,30 +2055,52 @@ struct tm_engine {
         return (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(1024, (uint64_t)need * 2));
     }
     // buf becomes an array of cap entries: its n old ones kept, the rest undefined (synchronous on d.ustream)
-    static void cursor_array_grow(DevState& d, DevBuf& buf, uint32_t& n, uint32_t cap) {
-        DevBuf nb;
-        nb.ensure((size_t)cap * 4, 1.0);
-        HIPCHK(hipMemsetAsync(nb.p, 0xFF, (size_t)cap * 4, d.ustream));
-        if (buf.p && n) HIPCHK(hipMemcpyAsync(nb.p, buf.p, (size_t)n * 4, hipMemcpyDeviceToDevice, d.ustream));
-        HIPCHK(hipStreamSynchronize(d.ustream));
-        buf.release();
-        buf = nb;
+    // the cursors and the sticky entries of one dictionary always have one length
+    static void cursor_array_grow(DevState& d, DevBuf& buf, DevBuf& sbuf, uint32_t& n, uint32_t cap) {
+        for (DevBuf* b : {&buf, &sbuf}) {
+            DevBuf nb;
+            nb.ensure((size_t)cap * 4, 1.0);
+            HIPCHK(hipMemsetAsync(nb.p, 0xFF, (size_t)cap * 4, d.ustream));
+            if (b->p && n) HIPCHK(hipMemcpyAsync(nb.p, b->p, (size_t)n * 4, hipMemcpyDeviceToDevice, d.ustream));
+            HIPCHK(hipStreamSynchronize(d.ustream));
+            b->release();
+            *b = nb;
+        }
         n = cap;
     }
-    void share_cursor_prepare(DevState& d, Image& g, const std::vector<uint32_t>& reset) {
+    // down: the members tm_share_member_down reported since the last commit
+    // (sorted, distinct).  Every sticky entry equal to one of them goes back to
+    // undefined (share.hip tm_share_sticky_down) after every batch that could
+    // still store such an entry has finished: a batch launched before this
+    // commit may pick the member, none launched after it can.
+    void share_cursor_prepare(DevState& d, Image& g, const std::vector<uint32_t>& reset,
+                              const std::vector<uint32_t>& down) {
         const uint32_t need = std::max<uint32_t>(sh_next_six, 1);
         bool grow = d.sh_cursor_n < need;
         for (tm_share_cursors* c : d.cursor_ctx) grow = grow || c->n < need;
-        if (grow) {
+        if (grow || !down.empty()) {
             d.drain_image(0);
             d.drain_image(1);
             d.rw_drain();
+        }
+        if (grow) {
             const uint32_t cap = cursor_capacity(need);
-            if (d.sh_cursor_n < need) cursor_array_grow(d, d.sh_cursor, d.sh_cursor_n, cap);
+            if (d.sh_cursor_n < need) cursor_array_grow(d, d.sh_cursor, d.sh_sticky, d.sh_cursor_n, cap);
             for (tm_share_cursors* c : d.cursor_ctx)
-                if (c->n < need) cursor_array_grow(d, c->buf, c->n, cap);
+                if (c->n < need) cursor_array_grow(d, c->buf, c->sbuf, c->n, cap);
         }
         g.cursor = d.sh_cursor.as<uint32_t>();
+        g.sticky = d.sh_sticky.as<uint32_t>();
+        if (!down.empty()) {
+            const uint32_t k = (uint32_t)down.size();
+            d.w_hdown.ensure((size_t)k * 4);
+            HIPCHK(hipMemcpyAsync(d.w_hdown.p, down.data(), (size_t)k * 4, hipMemcpyHostToDevice, d.ustream));
+            HIPCHK(launch_share_sticky_down(d.sh_sticky.as<uint32_t>(), d.sh_cursor_n, d.w_hdown.as<uint32_t>(), k,
+                                            d.ustream));
+            for (tm_share_cursors* c : d.cursor_ctx)
+                HIPCHK(launch_share_sticky_down(c->sbuf.as<uint32_t>(), c->n, d.w_hdown.as<uint32_t>(), k, d.ustream));
+            HIPCHK(hipStreamSynchronize(d.ustream));   // `down` is the caller's; the scatters below follow in order
+        }
         if (reset.empty()) return;
         const size_t n = reset.size();
         auto reset_in = [&](void* table) {
@@ -2077,7 +2114,11 @@ struct tm_engine {
             d.stage_ops.push_back(DevState::ScatterOp{table, off, n, 1u});
         };
         reset_in(d.sh_cursor.p);
-        for (tm_share_cursors* c : d.cursor_ctx) reset_in(c->buf.p);
+        reset_in(d.sh_sticky.p);
+        for (tm_share_cursors* c : d.cursor_ctx) {
+            reset_in(c->buf.p);
+            reset_in(c->sbuf.p);
+        }
     }
 
     // ---- to_rank labels (order maintenance) ----
@@ -2589,6 +2630,7 @@ struct tm_engine {
         if (targets_dirty && !devs.empty()) rank_targets();
         if (devs.empty()) {
             (void)release_share_indices();
+            sh_downed.clear();
             ++epoch;
             dev_dirty = false;
             release_quarantine();
@@ -2610,6 +2652,11 @@ struct tm_engine {
         // set indices whose quarantine is over: their cursors go back to
         // undefined on every replica before a new set can take them
         const std::vector<uint32_t> six_reset = release_share_indices();
+        // the processes that exited since the last commit (tm_share_member_down)
+        std::vector<uint32_t> downed;
+        downed.swap(sh_downed);
+        std::sort(downed.begin(), downed.end());
+        downed.erase(std::unique(downed.begin(), downed.end()), downed.end());
         for (auto& dp : devs) {
             DevState& d = *dp;
             Guard gd(d.device);
@@ -2619,7 +2666,7 @@ struct tm_engine {
             for_each_table([&](const auto& host, Track& t, DevBuf Image::*buf, bool upload) {
                 if (upload) upload_table(d, g, g.*buf, host, t.cur, t.prev);
             });
-            share_cursor_prepare(d, g, six_reset);
+            share_cursor_prepare(d, g, six_reset, downed);
             flush_stage(d);
             // append-only arrays: upload the new tail (or all after a realloc)
             {
@@ -3081,6 +3128,9 @@ struct tm_engine {
     // (share.hip): pick[slot] for slot < slots.  TM_SHARE_KEYED is one pass;
     // round robin reads the number of slots to rank back (one 8 B copy) to
     // size the sort, which covers the bits of the set indices handed out.
+    // TM_SHARE_STICKY takes the same path over the slots whose entry is
+    // undefined (none in the steady state: the call ends after the lookup and a
+    // 4 B read-back that says so, without the scan).
     void share_pick(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, const uint32_t* acount,
                     const uint64_t* aoff, const uint32_t* to, const uint32_t* tg, uint64_t slots, uint32_t strategy,
                     const uint32_t* pub_key, uint32_t* pick, hipStream_t st) {
@@ -3093,13 +3143,24 @@ struct tm_engine {
                                        nullptr, nullptr, nullptr, st));
             return;
         }
+        const bool sticky = strategy == TM_SHARE_STICKY;
         for (DevBuf* b : {&d.w_hcnt, &d.w_hseg, &d.w_hset, &d.w_hflag}) b->ensure((size_t)slots * 4 + 4);
+        if (sticky) d.w_hkplane.ensure((size_t)slots * 4 + 4);   // the spare word: "a slot was flagged"
         d.w_hpre.ensure((size_t)(slots + 1) * 8);
         d.w_hscan.ensure(scan_tmp_elems((uint32_t)slots) * 8 + 8);
         uint64_t* P = d.w_hpre.as<uint64_t>();
-        HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, aoff, to, tg, slots, nullptr, pick,
-                                   d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(), d.w_hset.as<uint32_t>(),
-                                   d.w_hflag.as<uint32_t>(), st));
+        uint32_t* any = sticky ? d.w_hkplane.as<uint32_t>() + slots : nullptr;
+        if (sticky) HIPCHK(hipMemsetAsync(any, 0, 4, st));
+        HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, aoff, to, tg, slots, sticky ? pub_key : nullptr,
+                                   pick, d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(), d.w_hset.as<uint32_t>(),
+                                   d.w_hflag.as<uint32_t>(), st, nullptr, nullptr,
+                                   sticky ? d.w_hkplane.as<uint32_t>() : nullptr, any));
+        if (sticky) {   // the steady state: every entry defined, nothing to scan or sort
+            uint32_t flagged = 0;
+            HIPCHK(hipMemcpyAsync(&flagged, any, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (!flagged) return;
+        }
         HIPCHK(launch_scan0(d.w_hflag.as<uint32_t>(), (uint32_t)slots, P, P + slots, d.w_hscan.as<uint64_t>(), st));
         uint64_t m64 = 0;
         HIPCHK(hipMemcpyAsync(&m64, P + slots, 8, hipMemcpyDeviceToHost, st));
@@ -3120,6 +3181,13 @@ struct tm_engine {
         HIPCHK(launch_sort_pairs(k0, v0, k1, v1, m, passes, d.w_hcounts.as<uint32_t>(), d.w_hoff.as<uint64_t>(),
                                  d.w_hsscan.as<uint64_t>(), st));
         const bool odd = passes & 1u;
+        if (sticky) {
+            HIPCHK(launch_share_sticky_pick(hv, odd ? k1 : k0, odd ? v1 : v0, m, d.w_hcnt.as<uint32_t>(),
+                                            d.w_hseg.as<uint32_t>(), d.w_hkplane.as<uint32_t>(), pick,
+                                            d.w_hnew.as<uint32_t>(), nullptr, nullptr, st));
+            HIPCHK(launch_share_sticky_store(hv, odd ? k1 : k0, d.w_hnew.as<uint32_t>(), m, nullptr, nullptr, st));
+            return;
+        }
         HIPCHK(launch_share_rr(hv, odd ? k1 : k0, odd ? v1 : v0, m, d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(),
                                pick, d.w_hnew.as<uint32_t>(), st));
     }
@@ -3150,7 +3218,7 @@ struct tm_engine {
     struct StreamLayout {
         uint64_t ctl, raw, rcounts, roff, rids, rexact, rscan, dcount, aoff, dsrc, ddest, akey, alarge, acount, to, tg,
             ndisp, pick, sub_count, sub_to, sub_id, xpcnt, xpseg, xpre, xscan, hcnt, hseg, hset, hflag, hpre, hscan,
-            hk, hnew, hcounts, hoff, hsscan, pscan, bytes;
+            hk, hnew, hcounts, hoff, hsscan, pscan, hkplane, bytes;
     };
     static StreamLayout stream_layout(uint32_t n, const tm_publish_caps& c) {
         StreamLayout L{};
@@ -3199,6 +3267,9 @@ struct tm_engine {
         L.hoff = take(((uint64_t)pc + 1) * 8);
         L.hsscan = take(scan_tmp_elems(pc) * 8 + 8);
         L.pscan = take(scan_tmp_elems(n) * 8 + 8);
+        // sticky: the flagged slots' keys.  Last, so the other pieces keep their offsets; taken for every
+        // strategy, because the need is one function of n and the capacities (tm_publish_stream_workspace_bytes)
+        L.hkplane = take(R1 * 4);
         L.bytes = at;
         return L;
     }
@@ -3209,10 +3280,11 @@ struct tm_engine {
     // The stages of run_dispatch and launch_publish_pack in their order, each
     // bounded by its capacity and followed by tm_stream_check; enqueues only.
     // The walk takes the replica's next slot as tm_match_batch_device does.
-    // cur: the cursor array round robin reads and (last kernel, state 0 only)
-    // writes.
+    // cur / stk: the cursor array round robin, or the sticky entries sticky,
+    // reads and (last kernel, state 0 only) writes.
     void run_publish_stream(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, uint64_t nbytes,
-                            uint32_t strategy, const uint32_t* pub_key, uint32_t* cur, const tm_publish_caps& c,
+                            uint32_t strategy, const uint32_t* pub_key, uint32_t* cur, uint32_t* stk,
+                            const tm_publish_caps& c,
                             uint8_t* ws, uint64_t* hdr, uint64_t* doff, uint64_t* sub_off, void* deliv, void* pairs,
                             hipStream_t st) {
         const StreamLayout L = stream_layout(n, c);
@@ -3249,8 +3321,10 @@ struct tm_engine {
         // 4. the $share picks
         ShareView hv = share_view(d);
         hv.cursor = cur;
+        hv.sticky = stk;
         const uint32_t local = sub_view(d).local_target;
-        const bool rr = strategy == TM_SHARE_ROUND_ROBIN;
+        const bool sticky = strategy == TM_SHARE_STICKY;
+        const bool rr = strategy == TM_SHARE_ROUND_ROBIN || sticky;   // the flagged-slot passes
         uint64_t* HP = u64(L.hpre);
         uint32_t *k0 = u32(L.hk), *v0 = k0 + c.rr, *k1 = v0 + c.rr, *v1 = k1 + c.rr;
         bool odd = false;
@@ -3258,8 +3332,9 @@ struct tm_engine {
             HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, R, pub_key, pick, nullptr,
                                        nullptr, nullptr, nullptr, st, raw + 1, gate));
         } else {
-            HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, R, nullptr, pick,
-                                       u32(L.hcnt), u32(L.hseg), u32(L.hset), u32(L.hflag), st, raw + 1, gate));
+            HIPCHK(launch_share_lookup(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, R,
+                                       sticky ? pub_key : nullptr, pick, u32(L.hcnt), u32(L.hseg), u32(L.hset),
+                                       u32(L.hflag), st, raw + 1, gate, sticky ? u32(L.hkplane) : nullptr));
             HIPCHK(launch_scan0(u32(L.hflag), (uint32_t)R, HP, HP + R, u64(L.hscan), st));
             HIPCHK(launch_stream_check(ctl, 4, HP + R, c.rr, st));
             // the radix passes cover the bits the set indices need; the padding
@@ -3268,11 +3343,17 @@ struct tm_engine {
             while (bits < 32 && ((uint64_t)1 << bits) < hv.n_sets) ++bits;
             const uint32_t passes = (bits + 7) / 8;
             HIPCHK(launch_share_compact_pad(u32(L.hflag), HP, u32(L.hset), R, k0, v0, c.rr, n, raw + 1, gate, st));
+            // HP[R] = the flagged slots: with none (sticky's steady state, or a batch without a set of two for
+            // round robin) the compaction, the sort's kernels and the pick leave at once
             HIPCHK(launch_sort_pairs(k0, v0, k1, v1, (uint32_t)c.rr, passes, u32(L.hcounts), u64(L.hoff),
-                                     u64(L.hsscan), st));
+                                     u64(L.hsscan), st, HP + R));
             odd = passes & 1u;
-            HIPCHK(launch_share_rr_pick(hv, odd ? k1 : k0, odd ? v1 : v0, (uint32_t)c.rr, u32(L.hcnt), u32(L.hseg), pick,
-                                        u32(L.hnew), HP + R, gate, st));
+            if (sticky)
+                HIPCHK(launch_share_sticky_pick(hv, odd ? k1 : k0, odd ? v1 : v0, (uint32_t)c.rr, u32(L.hcnt),
+                                                u32(L.hseg), u32(L.hkplane), pick, u32(L.hnew), HP + R, gate, st));
+            else
+                HIPCHK(launch_share_rr_pick(hv, odd ? k1 : k0, odd ? v1 : v0, (uint32_t)c.rr, u32(L.hcnt), u32(L.hseg),
+                                            pick, u32(L.hnew), HP + R, gate, st));
         }
         // 5. the dense records and the header
         HIPCHK(launch_publish_pack(n, acount, u64(L.aoff), to, tg, ndisp, pick, R, raw + 1, u32(L.sub_to), u32(L.sub_id),
@@ -3280,7 +3361,9 @@ struct tm_engine {
         HIPCHK(launch_stream_finish(ctl, doff, n, hdr, st));
         // 6. the new cursors, only when the whole batch fitted: a rerun of a
         // batch that did not starts from the cursors its first run found
-        if (rr)
+        if (sticky)
+            HIPCHK(launch_share_sticky_store(hv, odd ? k1 : k0, u32(L.hnew), (uint32_t)c.rr, HP + R, gate, st));
+        else if (rr)
             HIPCHK(launch_share_rr_store(hv, odd ? k1 : k0, u32(L.hnew), (uint32_t)c.rr, HP + R, gate, st));
         d.note_use(st);   // the pinned images (and the cursor array) are read until this point of st
         d.rw_release(st);
@@ -3664,6 +3747,7 @@ void tm_close(tm_engine* e) {
         if (!d->cursor_ctx.empty()) (void)hipDeviceSynchronize();   // their last calls ran on callers' streams
         for (tm_share_cursors* c : d->cursor_ctx) {
             c->buf.release();
+            c->sbuf.release();
             c->n = 0;
             c->e = nullptr;
         }
@@ -4550,6 +4634,10 @@ int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const u
 // tm_match_publish_batch share every step up to the picks
 extern "C++" {
 namespace {
+inline bool share_strategy_ok(uint32_t s) {
+    return s == TM_SHARE_KEYED || s == TM_SHARE_ROUND_ROBIN || s == TM_SHARE_STICKY;
+}
+inline bool share_strategy_keyed(uint32_t s) { return s == TM_SHARE_KEYED || s == TM_SHARE_STICKY; }
 int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
@@ -4558,8 +4646,8 @@ int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topi
     if (!topic_off || !out_off || !sub_off || (n && (!out_count || !sub_count)) ||
         (out_cap && (!out_to || !out_target || !out_ndisp || (strategy && !out_pick))) || (sub_cap && (!sub_to || !sub_id)))
         return TM_EINVAL;
-    if (strategy && strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
-    if (strategy == TM_SHARE_KEYED && n && !pub_key) return TM_EINVAL;
+    if (strategy && !share_strategy_ok(strategy)) return TM_EINVAL;
+    if (share_strategy_keyed(strategy) && n && !pub_key) return TM_EINVAL;
     if (!e) return TM_EINVAL;
     if (e->devs.empty()) return no_device(e, strategy ? "publish" : "dispatch");
     if (int rc = local_node_unset(e)) return rc;
@@ -4612,7 +4700,7 @@ int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topi
         if (strategy && fits && rtotal) {
             d.w_hpick.ensure(rtotal * 4);
             const uint32_t* key = nullptr;
-            if (strategy == TM_SHARE_KEYED) {
+            if (share_strategy_keyed(strategy)) {
                 d.w_hkey.ensure((size_t)n * 4);
                 HIPCHK(hipMemcpyAsync(d.w_hkey.p, pub_key, (size_t)n * 4, hipMemcpyHostToDevice, s));
                 key = d.w_hkey.as<uint32_t>();
@@ -4796,8 +4884,8 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const ui
     if (!d_off || !d_out_off || !d_total || !d_sub_off || !d_sub_total || (n && (!d_count || !d_sub_count)) ||
         (out_cap && (!d_to || !d_target || !d_ndisp || !d_pick)) || (sub_cap && (!d_sub_to || !d_sub_id)))
         return TM_EINVAL;
-    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
-    if (strategy == TM_SHARE_KEYED && n && !d_pub_key) return TM_EINVAL;
+    if (!share_strategy_ok(strategy)) return TM_EINVAL;
+    if (share_strategy_keyed(strategy) && n && !d_pub_key) return TM_EINVAL;
     if (!e) return TM_EINVAL;
     if (e->devs.empty()) return no_device(e, "publish");
     if (int rc = local_node_unset(e)) return rc;
@@ -4876,7 +4964,7 @@ int tm_share_cursors_open(tm_engine* e, uint32_t replica, tm_share_cursors** out
         // as large as the built-in array is (or would be): covers every set
         // index handed out, all undefined
         const uint32_t cap = std::max(d.sh_cursor_n, tm_engine::cursor_capacity(std::max<uint32_t>(e->sh_next_six, 1)));
-        tm_engine::cursor_array_grow(d, c->buf, c->n, cap);
+        tm_engine::cursor_array_grow(d, c->buf, c->sbuf, c->n, cap);
         d.cursor_ctx.push_back(c.get());
         *out = c.release();
         return TM_OK;
@@ -4904,6 +4992,7 @@ void tm_share_cursors_close(tm_share_cursors* c) {
         v.erase(std::remove(v.begin(), v.end(), c), v.end());
         tm_engine::Guard g(d.device);
         c->buf.release();
+        c->sbuf.release();
     }
     delete c;
 }
@@ -4921,8 +5010,8 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_
                              uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
                              tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream) {
     if (!d_off || !d_hdr || !d_doff || !d_sub_off || !caps || !d_workspace) return TM_EINVAL;
-    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
-    if (strategy == TM_SHARE_KEYED && n && !d_pub_key) return TM_EINVAL;
+    if (!share_strategy_ok(strategy)) return TM_EINVAL;
+    if (share_strategy_keyed(strategy) && n && !d_pub_key) return TM_EINVAL;
     if ((caps->routes && !d_deliv) || (caps->pairs && !d_pairs)) return TM_EINVAL;
     tm_publish_caps c = *caps;
     if (strategy == TM_SHARE_KEYED) c.rr = 0;   // ignored: keyed picks rank nothing
@@ -4945,10 +5034,112 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_
         // under the batch lock: a commit (which may move a cursor array) runs
         // under it too, or under the engine lock before the pin above
         uint32_t* cur = cursors ? cursors->buf.as<uint32_t>() : tm_engine::share_view(d).cursor;
-        e->run_publish_stream(d, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cur, c,
+        uint32_t* stk = cursors ? cursors->sbuf.as<uint32_t>() : tm_engine::share_view(d).sticky;
+        e->run_publish_stream(d, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cur, stk, c,
                               static_cast<uint8_t*>(d_workspace), d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, st);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
+}
+
+// pick/5 with FailedSubs (share.hip tm_share_retry_resolve / tm_share_retry_pick):
+// the groups resolved to target ids here (interned names never change; an
+// unknown group is "no such set"), everything else on the device against the
+// committed image.  The stateful strategies sort the (set index, request)
+// pairs stably over every bit a key has, so a set's requests are contiguous
+// and one wave walks them in index order.
+int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* cursors, const uint8_t* groups,
+                        const uint64_t* group_off, const uint8_t* topics, const uint64_t* topic_off,
+                        const uint32_t* pub_key, const uint32_t* failed, const uint64_t* failed_off, uint32_t n,
+                        uint32_t* out_pick) {
+    if (!share_strategy_ok(strategy)) return TM_EINVAL;
+    if (n && (!group_off || !topic_off || !failed_off || !out_pick || (share_strategy_keyed(strategy) && !pub_key)))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (cursors && (cursors->e != e || cursors->replica != 0)) return TM_EINVAL;
+    if (n) {
+        for (uint32_t i = 0; i < n; ++i)
+            if (group_off[i + 1] < group_off[i] || topic_off[i + 1] < topic_off[i] || failed_off[i + 1] < failed_off[i])
+                return TM_EINVAL;
+        if ((group_off[n] > group_off[0] && !groups) || (topic_off[n] > topic_off[0] && !topics) ||
+            (failed_off[n] > failed_off[0] && !failed))
+            return TM_EINVAL;
+    }
+    if (e->devs.empty()) return no_device(e, "a retry pick");
+    if (n == 0) return TM_OK;
+    DevState& d = *e->devs[0];
+    // the groups' target ids under the engine lock, before the batch pins an
+    // image: a commit holds that lock while it waits for the pins
+    std::vector<uint32_t> tg(n);
+    const int rc = guarded(e, [&] {
+        std::string gk;
+        for (uint32_t i = 0; i < n; ++i) {
+            gk.assign(1, (char)TM_TARGET_GROUP);
+            if (group_off[i + 1] > group_off[i])
+                gk.append(reinterpret_cast<const char*>(groups + group_off[i]), group_off[i + 1] - group_off[i]);
+            auto ti = e->target_index.find(gk);
+            tg[i] = ti == e->target_index.end() ? 0xFFFFFFFFu : ti->second;
+        }
+        return TM_OK;
+    });
+    if (rc != TM_OK) return rc;
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        const uint64_t base = topic_off[0], nb = topic_off[n] - base;
+        const uint64_t fbase = failed_off[0], nf = failed_off[n] - fbase;
+        std::vector<uint64_t> rel(topic_off, topic_off + n + 1), frel(failed_off, failed_off + n + 1);
+        for (auto& x : rel) x -= base;
+        for (auto& x : frel) x -= fbase;
+        d.rw_drain();
+        d.w_bytes.ensure(nb + 16);
+        d.w_off.ensure((size_t)(n + 1) * 8);
+        d.w_htg.ensure((size_t)n * 4);
+        d.w_hfail.ensure((size_t)nf * 4 + 4);
+        d.w_hfoff.ensure((size_t)(n + 1) * 8);
+        d.w_hcnt.ensure((size_t)n * 4);
+        d.w_hseg.ensure((size_t)n * 4);
+        d.w_hpick.ensure((size_t)n * 4);
+        d.w_hpairs.ensure((size_t)n * 16);
+        if (pub_key) d.w_hkey.ensure((size_t)n * 4);
+        if (nb) HIPCHK(hipMemcpyAsync(d.w_bytes.p, topics + base, nb, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.w_off.p, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.w_htg.p, tg.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        if (nf) HIPCHK(hipMemcpyAsync(d.w_hfail.p, failed + fbase, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d.w_hfoff.p, frel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        if (pub_key) HIPCHK(hipMemcpyAsync(d.w_hkey.p, pub_key, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        ShareView hv = tm_engine::share_view(d);
+        if (cursors) {
+            hv.cursor = cursors->buf.as<uint32_t>();
+            hv.sticky = cursors->sbuf.as<uint32_t>();
+        }
+        uint32_t* k0 = d.w_hpairs.as<uint32_t>();
+        uint32_t *v0 = k0 + n, *k1 = v0 + n, *v1 = k1 + n;
+        HIPCHK(launch_share_retry_resolve(hv, d.w_bytes.as<uint8_t>(), d.w_off.as<uint64_t>(), d.w_htg.as<uint32_t>(), n,
+                                          d.w_hcnt.as<uint32_t>(), d.w_hseg.as<uint32_t>(), k0, v0, s));
+        bool odd = false;
+        if (strategy != TM_SHARE_KEYED && n > 1) {
+            // keys are set indices below n_sets and n_sets itself for "no such
+            // set": the passes cover the bits of n_sets, so every key sorts whole
+            uint32_t bits = 0;
+            while (bits < 32 && ((uint64_t)1 << bits) <= hv.n_sets) ++bits;
+            const uint32_t passes = (bits + 7) / 8, pc = presort_counts(n);
+            d.w_hcounts.ensure((size_t)pc * 4);
+            d.w_hoff.ensure((size_t)(pc + 1) * 8);
+            d.w_hsscan.ensure(scan_tmp_elems(pc) * 8 + 8);
+            HIPCHK(launch_sort_pairs(k0, v0, k1, v1, n, passes, d.w_hcounts.as<uint32_t>(), d.w_hoff.as<uint64_t>(),
+                                     d.w_hsscan.as<uint64_t>(), s));
+            odd = passes & 1u;
+        }
+        HIPCHK(launch_share_retry_pick(hv, strategy, odd ? k1 : k0, odd ? v1 : v0, n, d.w_hcnt.as<uint32_t>(),
+                                       d.w_hseg.as<uint32_t>(), pub_key ? d.w_hkey.as<uint32_t>() : nullptr,
+                                       d.w_hfail.as<uint32_t>(), d.w_hfoff.as<uint64_t>(), d.w_hpick.as<uint32_t>(),
+                                       s));
+        d.note_use(s);
+        d.rw_release(s);
+        HIPCHK(hipMemcpyAsync(out_pick, d.w_hpick.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return TM_OK;
+    }, [&] {});
 }
 
 int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
@@ -4956,7 +5147,7 @@ int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint6
                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
                            uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick) {
-    if (strategy != TM_SHARE_KEYED && strategy != TM_SHARE_ROUND_ROBIN) return TM_EINVAL;
+    if (!share_strategy_ok(strategy)) return TM_EINVAL;
     return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
                          out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, strategy, pub_key,
                          out_pick);

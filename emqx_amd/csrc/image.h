@@ -254,6 +254,7 @@ struct ShareView {
     const uint32_t*       fx;        // n_filters: filter id -> xid of that wildcard topic (0xFFFFFFFF: none)
     uint32_t              n_filters;
     uint32_t*             cursor;    // set index -> stored Rem, 0xFFFFFFFF = undefined (per replica)
+    uint32_t*             sticky;    // set index -> {shared_sub_sticky, Group, Topic}: a member id, 0xFFFFFFFF = undefined
     uint32_t              n_sets;    // set indices handed out so far (cursor entries in use)
 };
 

@@ -89,7 +89,8 @@ hipError_t launch_presort(const uint32_t* twords, const uint32_t* meta, uint32_t
 // odd one.  counts: presort_counts(n) u32, off: presort_counts(n) + 1 u64,
 // tmp: scan_tmp_elems(presort_counts(n)).
 hipError_t launch_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
-                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st);
+                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st,
+                             const uint64_t* live = nullptr);
 // true when launch_queue's walk of a presorted batch writes stage row p for
 // queue position p (the copy-out then moves row p to topic perm[p]): without
 // chunk rows, or keyed / stats walks.  With chunk rows the walk reads each
@@ -203,7 +204,8 @@ hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const
                                uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
                                const uint32_t* tg, uint64_t slots, const uint32_t* pub_key, uint32_t* pick,
                                uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st,
-                               const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr);
+                               const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr,
+                               uint32_t* kplane = nullptr, uint32_t* any = nullptr);
 hipError_t launch_share_compact(const uint32_t* flag, const uint64_t* P, const uint32_t* set, uint64_t slots,
                                 uint32_t* keys, uint32_t* vals, hipStream_t st);
 hipError_t launch_share_rr(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
@@ -221,6 +223,32 @@ hipError_t launch_share_rr_pick(const ShareView& hv, const uint32_t* keys, const
                                 const uint64_t* dm, const uint64_t* gate, hipStream_t st);
 hipError_t launch_share_rr_store(const ShareView& hv, const uint32_t* keys, const uint32_t* newcur, uint32_t m,
                                  const uint64_t* dm, const uint64_t* gate, hipStream_t st);
+// TM_SHARE_STICKY: launch_share_lookup with kplane != null (slots entries) and
+// pub_key -- a slot whose sticky entry (ShareView::sticky) is defined is final,
+// the others are flagged with cnt / seg / set / kplane (their publish's key),
+// and *any (optional, zeroed by the caller) is set when a slot was flagged --
+// then the scan, the compaction and the sort of round robin, and
+//   launch_share_sticky_pick   every pair of a run takes the draw of the run's head (its
+//                              lowest slot) with the head's key; newst[p] = the run's new entry
+//   launch_share_sticky_store  the new entries (the call's last kernel)
+// dm / gate as for round robin (null: m pairs, no gate).
+hipError_t launch_share_sticky_pick(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
+                                    const uint32_t* cnt, const uint32_t* seg, const uint32_t* kplane, uint32_t* pick,
+                                    uint32_t* newst, const uint64_t* dm, const uint64_t* gate, hipStream_t st);
+hipError_t launch_share_sticky_store(const ShareView& hv, const uint32_t* keys, const uint32_t* newst, uint32_t m,
+                                     const uint64_t* dm, const uint64_t* gate, hipStream_t st);
+// commit: the entries of sticky[0, n) equal to one of down[0, k) (sorted, distinct) back to undefined
+hipError_t launch_share_sticky_down(uint32_t* sticky, uint32_t n, const uint32_t* down, uint32_t k, hipStream_t st);
+// tm_share_pick_batch: resolve request i = (group target tg[i], To bytes) to
+// rcnt / rseg and the pair (set index, or n_sets for "no such set", i); then, the pairs
+// sorted by that key over the bits of n_sets for the stateful strategies, one wave per pair picks
+// pick(Strategy, _, Group, Topic, failed[failed_off[i] .. failed_off[i+1]))
+hipError_t launch_share_retry_resolve(const ShareView& hv, const uint8_t* bytes, const uint64_t* off,
+                                      const uint32_t* tg, uint32_t n, uint32_t* rcnt, uint32_t* rseg, uint32_t* keys,
+                                      uint32_t* vals, hipStream_t st);
+hipError_t launch_share_retry_pick(const ShareView& hv, uint32_t strategy, const uint32_t* keys, const uint32_t* vals,
+                                   uint32_t n, const uint32_t* rcnt, const uint32_t* rseg, const uint32_t* pub_key,
+                                   const uint32_t* failed, const uint64_t* failed_off, uint32_t* pick, hipStream_t st);
 
 // A publish batch's results as dense records (pack.hip) over what
 // tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:

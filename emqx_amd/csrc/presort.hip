@@ -40,8 +40,8 @@ constexpr uint32_t PS_META_N = (1u << 29) - 1;           // kernels.hip meta: le
 uint32_t presort_counts(uint32_t n) { return 256u * ((n + PS_TILE - 1) / PS_TILE); }
 
 // digit counts of a tile: counts[digit * tiles + tile]
-__global__ void __launch_bounds__(PS_BLOCK)
-tm_presort_count(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t* __restrict__ counts) {
+__device__ __forceinline__ void presort_count_tile(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift,
+                                                   uint32_t* __restrict__ counts) {
     __shared__ uint32_t hist[256];
     hist[threadIdx.x] = 0;
     __syncthreads();
@@ -54,12 +54,24 @@ tm_presort_count(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, 
     __syncthreads();
     counts[(size_t)threadIdx.x * gridDim.x + tile] = hist[threadIdx.x];
 }
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_count(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t* __restrict__ counts) {
+    presort_count_tile(keys, n, shift, counts);
+}
+// the same, skipped when *live == 0: launch_sort_pairs over a capacity of pairs
+// that holds padding only (the stream-ordered publish call with nothing to rank)
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_count_if(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t* __restrict__ counts,
+                    const uint64_t* __restrict__ live) {
+    if (*live == 0) return;
+    presort_count_tile(keys, n, shift, counts);
+}
 
 // stable scatter of a tile to its digits' ranges
-__global__ void __launch_bounds__(PS_BLOCK)
-tm_presort_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
-                   uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
-                   uint32_t* __restrict__ vals_out) {
+__device__ __forceinline__ void presort_scatter_tile(const uint32_t* __restrict__ keys_in,
+                                                     const uint32_t* __restrict__ vals_in, uint32_t n, uint32_t shift,
+                                                     const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
+                                                     uint32_t* __restrict__ vals_out) {
     __shared__ uint32_t start[256];                // tile's first position per digit + keys placed so far
     __shared__ uint32_t wcnt[PS_WAVES][256];       // this round: keys per digit in each wave
     const uint32_t tile = blockIdx.x, base = tile * PS_TILE;
@@ -97,6 +109,19 @@ tm_presort_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restr
         start[threadIdx.x] += add;
     }
 }
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
+                   uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
+                   uint32_t* __restrict__ vals_out) {
+    presort_scatter_tile(keys_in, vals_in, n, shift, off, keys_out, vals_out);
+}
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_scatter_if(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
+                      uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
+                      uint32_t* __restrict__ vals_out, const uint64_t* __restrict__ live) {
+    if (*live == 0) return;
+    presort_scatter_tile(keys_in, vals_in, n, shift, off, keys_out, vals_out);
+}
 
 // the same stable scatter through LDS (TM_PS_LOCAL): each wave ranks a
 // contiguous quarter of the tile (1024 keys, 16 rounds of 64) with its own
@@ -121,10 +146,11 @@ __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t x, uint32_t* tmp
     for (uint32_t w = 0; w < wave; ++w) pre += tmp[w];
     return pre + inc - x;
 }
-__global__ void __launch_bounds__(PS_BLOCK)
-tm_presort_scatter_ls(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
-                      uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
-                      uint32_t* __restrict__ vals_out) {
+__device__ __forceinline__ void presort_scatter_ls_tile(const uint32_t* __restrict__ keys_in,
+                                                        const uint32_t* __restrict__ vals_in, uint32_t n,
+                                                        uint32_t shift, const uint64_t* __restrict__ off,
+                                                        uint32_t* __restrict__ keys_out,
+                                                        uint32_t* __restrict__ vals_out) {
     __shared__ uint32_t skey[PS_TILE];
     __shared__ uint32_t sval[PS_TILE];
     __shared__ uint32_t wcnt[PS_WAVES][256];   // keys per digit in each wave, then that wave's base per digit
@@ -196,6 +222,19 @@ tm_presort_scatter_ls(const uint32_t* __restrict__ keys_in, const uint32_t* __re
         vals_out[g] = sval[j];
     }
 }
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_scatter_ls(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
+                      uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
+                      uint32_t* __restrict__ vals_out) {
+    presort_scatter_ls_tile(keys_in, vals_in, n, shift, off, keys_out, vals_out);
+}
+__global__ void __launch_bounds__(PS_BLOCK)
+tm_presort_scatter_ls_if(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
+                         uint32_t shift, const uint64_t* __restrict__ off, uint32_t* __restrict__ keys_out,
+                         uint32_t* __restrict__ vals_out, const uint64_t* __restrict__ live) {
+    if (*live == 0) return;
+    presort_scatter_ls_tile(keys_in, vals_in, n, shift, off, keys_out, vals_out);
+}
 
 // the rows in walk order: the 16 B chunks of words the walk reads (all of a
 // long topic's row, whose later levels it reads as memory words)
@@ -263,19 +302,31 @@ hipError_t launch_presort(const uint32_t* twords, const uint32_t* meta, uint32_t
 }
 
 // the same passes over plain arrays (share.hip sorts (set index, slot) pairs):
-// the keys' low 8 * passes bits, input in (k0, v0), ping-pong with (k1, v1)
+// the keys' low 8 * passes bits, input in (k0, v0), ping-pong with (k1, v1).
+// live (optional, a device word): the number of real pairs among the n; when
+// it is 0 the count and scatter kernels leave at once (nothing is sorted and
+// the outputs are not written: the caller reads no pair then)
 hipError_t launch_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
-                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st) {
+                             uint32_t* counts, uint64_t* off, uint64_t* tmp, hipStream_t st, const uint64_t* live) {
     if (n == 0 || passes == 0) return hipSuccess;
     if (passes > 4) return hipErrorInvalidValue;
     const uint32_t tiles = (n + PS_TILE - 1) / PS_TILE, nc = 256u * tiles;
     uint32_t *ka = k0, *kb = k1, *va = v0, *vb = v1;
     for (uint32_t pass = 0; pass < passes; ++pass) {
         const uint32_t shift = 8 * pass;
-        hipLaunchKernelGGL(tm_presort_count, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, n, shift, counts);
+        if (live)
+            hipLaunchKernelGGL(tm_presort_count_if, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, n, shift, counts, live);
+        else
+            hipLaunchKernelGGL(tm_presort_count, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, n, shift, counts);
         hipError_t err = launch_scan(counts, nc, off, off + nc, tmp, st);
         if (err != hipSuccess) return err;
-        if (TM_PS_LOCAL)
+        if (live && TM_PS_LOCAL)
+            hipLaunchKernelGGL(tm_presort_scatter_ls_if, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb,
+                               vb, live);
+        else if (live)
+            hipLaunchKernelGGL(tm_presort_scatter_if, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb, vb,
+                               live);
+        else if (TM_PS_LOCAL)
             hipLaunchKernelGGL(tm_presort_scatter_ls, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb, vb);
         else
             hipLaunchKernelGGL(tm_presort_scatter, dim3(tiles), dim3(PS_BLOCK), 0, st, ka, va, n, shift, off, kb, vb);

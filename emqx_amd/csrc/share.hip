@@ -32,11 +32,22 @@
 //            search in every lane.  The last pair of a run owns the new
 //            cursor; a second kernel stores it (plain vector stores), so no
 //            pair reads a cursor another wave already advanced.
+//   sticky (pick/5's first clause, :211-224): the lookup loads the set's entry
+//            {shared_sub_sticky, Group, Topic}; defined = the pick (the stored
+//            member id: is_active_sub/2 tests no membership), final.  The slots
+//            that found it undefined take round robin's compaction and sort;
+//            a run's head draws pool[seg + key % Count] with its publish's
+//            key, every pair of the run takes that draw, and a last kernel
+//            stores the heads' draws.  Liveness is evaluated at the commit
+//            (tm_share_sticky_down), so defined implies alive.
+//   retry    tm_share_pick_batch, pick/5 with FailedSubs (dispatch/4, :92-111):
+//            one wave per request, requests on one set in index order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
 #include "device_bytes.h"
+#include "../../include/topicmatch.h"
 
 namespace tmx {
 
@@ -56,15 +67,21 @@ __device__ __forceinline__ bool share_topic_lookup(const ShareView& hv, const ui
 // lookup over blocks of 256 topics (the slot walk of dispatch.hip
 // tm_dispatch_count).  pub_key != null: TM_SHARE_KEYED, every pick is final;
 // null: round robin, cnt / seg / set / flag are written for the later passes
-// and the slots with flag 1 get their pick there
+// and the slots with flag 1 get their pick there.  STICKY (TM_SHARE_STICKY,
+// pub_key given): a slot whose set has a defined sticky entry is final -- the
+// pick is the stored member id itself, no pool load, no flag -- and a slot
+// whose entry is undefined is flagged with its Count / segment / set index and
+// its publish's key (kplane) for tm_share_sticky_pick; *any (optional, zeroed
+// by the caller) becomes 1 when at least one slot was flagged
+template <bool STICKY>
 __global__ void __launch_bounds__(HBLOCK)
 tm_share_lookup(ShareView hv, uint32_t local_target, const uint8_t* __restrict__ bytes,
                 const uint64_t* __restrict__ off, uint32_t n, const uint32_t* __restrict__ acount,
                 const uint64_t* __restrict__ aoff, const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg,
                 uint64_t slots, const uint32_t* __restrict__ pub_key, uint32_t* __restrict__ pick,
                 uint32_t* __restrict__ cnt, uint32_t* __restrict__ seg, uint32_t* __restrict__ set,
-                uint32_t* __restrict__ flag, const uint64_t* __restrict__ dtotal,
-                const uint64_t* __restrict__ gate) {
+                uint32_t* __restrict__ flag, uint32_t* __restrict__ kplane, uint32_t* __restrict__ any,
+                const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate) {
     __shared__ uint64_t lds_inc[HBLOCK];   // inclusive prefix of the block's spans
     __shared__ uint64_t lds_scan[HBLOCK / 64];
     if (gate && *gate) return;   // an earlier stage of a stream-ordered publish overflowed (wave-uniform)
@@ -126,7 +143,21 @@ tm_share_lookup(ShareView hv, uint32_t local_target, const uint8_t* __restrict__
             }
         }
         uint32_t pk = TM_NO_MEMBER_ID;
-        if (pub_key) {
+        if (STICKY) {
+            uint32_t f = 0;
+            if (c && si < hv.n_sets) {   // the arrays cover the set indices handed out
+                pk = hv.sticky[si];
+                if (pk == TM_NO_MEMBER_ID) {   // undefined: the batch's first publish on the set picks (sticky_pick)
+                    f = 1;
+                    cnt[g] = c;
+                    seg[g] = sg;
+                    set[g] = si;
+                    kplane[g] = pub_key[tl];
+                    if (any) *any = 1u;   // every writer stores the same value: the host skips the scan when none did
+                }
+            }
+            flag[g] = f;
+        } else if (pub_key) {
             if (c) pk = hv.pool[sg + pub_key[tl] % c];
         } else {
             if (c == 1) pk = hv.pool[sg];
@@ -166,6 +197,7 @@ tm_share_compact_pad(const uint32_t* __restrict__ flag, const uint64_t* __restri
     if (*gate) return;
     const uint64_t tid = (uint64_t)blockIdx.x * HBLOCK + threadIdx.x, stride = (uint64_t)gridDim.x * HBLOCK;
     const uint64_t m = P[slots];
+    if (m == 0) return;   // nothing flagged: the sort and the pick leave too (launch_sort_pairs `live`), no padding is read
     const uint64_t live = *dtotal < slots ? *dtotal : slots;
     for (uint64_t g = tid; g < live; g += stride)
         if (flag[g]) {
@@ -179,27 +211,21 @@ tm_share_compact_pad(const uint32_t* __restrict__ flag, const uint64_t* __restri
     }
 }
 
-// one lane per sorted pair: rank in its run, the pick, and for the last pair
-// of a run the cursor the run leaves (newcur[p], 0xFFFFFFFF for every other
-// pair: a stored Rem is below its Count, never that value)
-__global__ void __launch_bounds__(HBLOCK)
-tm_share_rr_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t m,
-                 const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ seg, uint32_t* __restrict__ pick,
-                 uint32_t* __restrict__ newcur, const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
-    if (gate && *gate) return;
-    // dm: the number of pairs on the device (the stream-ordered call sorts its
-    // capacity of pairs, padded with the sentinel key): the pairs past it are
-    // neither ranked nor given a newcur entry
-    if (dm && *dm < m) m = (uint32_t)*dm;
+// lane p of the sorted pairs: its key, whether it is the head / the last pair
+// of its run, and the run's start + 1.  A run's start comes from a max-scan of
+// the head flags over the wave's registers; only a wave whose first run began
+// before it searches for that one start, the same search in every lane, so
+// runs may cross wave, block and sort-tile edges.
+__device__ __forceinline__ uint32_t share_run_start(const uint32_t* __restrict__ keys, uint32_t p, uint32_t m,
+                                                    uint32_t& key, bool& valid, bool& head, bool& last) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;   // m <= 2^32 - 2: the grid never wraps p
-    const bool valid = p < m;
-    const uint32_t key = valid ? keys[p] : 0xFFFFFFFFu;
+    valid = p < m;
+    key = valid ? keys[p] : 0xFFFFFFFFu;
     uint32_t prev = __shfl_up(key, 1, 64), next = __shfl_down(key, 1, 64);
     if (lane == 0) prev = (valid && p > 0) ? keys[p - 1] : ~key;
     if (lane == 63) next = (valid && p + 1 < m) ? keys[p + 1] : ~key;
-    const bool head = valid && (p == 0 || prev != key);
-    const bool last = valid && (p + 1 == m || next != key);
+    head = valid && (p == 0 || prev != key);
+    last = valid && (p + 1 == m || next != key);
     // run start + 1 of every lane whose run begins in this wave (max-scan), 0 for the others
     uint32_t h = head ? p + 1 : 0u;
     for (int o = 1; o < 64; o <<= 1) {
@@ -218,6 +244,25 @@ tm_share_rr_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t
         }
         if (h == 0) h = lo + 1;
     }
+    return h;
+}
+
+// one lane per sorted pair: rank in its run, the pick, and for the last pair
+// of a run the cursor the run leaves (newcur[p], 0xFFFFFFFF for every other
+// pair: a stored Rem is below its Count, never that value)
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_rr_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t m,
+                 const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ seg, uint32_t* __restrict__ pick,
+                 uint32_t* __restrict__ newcur, const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;
+    // dm: the number of pairs on the device (the stream-ordered call sorts its
+    // capacity of pairs, padded with the sentinel key): the pairs past it are
+    // neither ranked nor given a newcur entry
+    if (dm && *dm < m) m = (uint32_t)*dm;
+    const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;   // m <= 2^32 - 2: the grid never wraps p
+    uint32_t key;
+    bool valid, head, last;
+    const uint32_t h = share_run_start(keys, p, m, key, valid, head, last);
     uint32_t nc = 0xFFFFFFFFu;
     if (valid && key < hv.n_sets) {
         const uint32_t k = p - (h - 1);
@@ -242,16 +287,233 @@ tm_share_rr_store(ShareView hv, const uint32_t* __restrict__ keys, const uint32_
     if (v != 0xFFFFFFFFu) hv.cursor[keys[p]] = v;   // v set only for key < n_sets
 }
 
+// TM_SHARE_STICKY over the sorted pairs of the flagged slots (sticky entry
+// undefined).  The sort is stable and the pairs were compacted in slot order,
+// so a run's head is its set's lowest slot = the first publish of the batch
+// that reaches the set: pick(sticky, ...) of src/emqx_shared_sub.erl:218-223
+// draws there with that publish's key, and every later publish of the batch
+// finds the entry it stored.  Every pair of the run computes the head's draw
+// itself (Count and segment are the set's, the same in every pair); the head
+// owns the new entry (newst[p], 0xFFFFFFFF for every other pair: no member id
+// is that value), which tm_share_sticky_store writes.
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_sticky_pick(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t m,
+                     const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ seg,
+                     const uint32_t* __restrict__ kplane, uint32_t* __restrict__ pick, uint32_t* __restrict__ newst,
+                     const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;
+    if (dm && *dm < m) m = (uint32_t)*dm;
+    const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;
+    uint32_t key;
+    bool valid, head, last;
+    const uint32_t h = share_run_start(keys, p, m, key, valid, head, last);
+    (void)last;
+    uint32_t ns = 0xFFFFFFFFu;
+    if (valid && key < hv.n_sets) {
+        const uint32_t g = vals[p];
+        const uint32_t hk = kplane[vals[h - 1]];   // the head publish's key
+        const uint32_t pk = hv.pool[seg[g] + hk % cnt[g]];   // Count >= 1; [Sub] -> Sub is entry 0
+        pick[g] = pk;
+        if (head) ns = pk;
+    }
+    if (valid) newst[p] = ns;
+}
+
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_sticky_store(ShareView hv, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ newst, uint32_t m,
+                      const uint64_t* __restrict__ dm, const uint64_t* __restrict__ gate) {
+    if (gate && *gate) return;   // the batch did not fit: no entry changes, its rerun picks what a first run would
+    if (dm && *dm < m) m = (uint32_t)*dm;
+    const uint32_t p = blockIdx.x * HBLOCK + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t v = newst[p];
+    if (v != 0xFFFFFFFFu) hv.sticky[keys[p]] = v;   // v set only for key < n_sets
+}
+
+// commit: is_alive_sub/1 (:330-334) evaluated eagerly.  Every sticky entry
+// equal to one of the commit's downed members (sorted, distinct) goes back to
+// undefined, so a defined entry is a live process and the pick passes need no
+// liveness table.  One lane per entry, a binary search of the list.
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_sticky_down(uint32_t* __restrict__ sticky, uint32_t n, const uint32_t* __restrict__ down, uint32_t k) {
+    const uint32_t i = blockIdx.x * HBLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = sticky[i];
+    if (v == 0xFFFFFFFFu) return;
+    uint32_t lo = 0, hi = k;   // first position with down[.] >= v
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (down[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < k && down[lo] == v) sticky[i] = 0xFFFFFFFFu;
+}
+
+// ---- tm_share_pick_batch: pick/5 with a non-empty FailedSubs (the retry of dispatch/4, :92-111) ----
+//
+// resolve: one lane per request -- the set of (group target, To bytes):
+// rcnt / rseg and the pair (set index, request); "no such set" gets the key
+// n_sets, one past every set index, so that a sort over the bits of n_sets
+// puts those requests behind every set's whatever the number of sets.
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_retry_resolve(ShareView hv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                       const uint32_t* __restrict__ tg, uint32_t n, uint32_t* __restrict__ rcnt,
+                       uint32_t* __restrict__ rseg, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * HBLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t c = 0, sg = 0, si = hv.n_sets, xid = 0;
+    const uint32_t gt = tg[i];
+    if (gt != 0xFFFFFFFFu && share_topic_lookup(hv, bytes, off[i], (uint32_t)(off[i + 1] - off[i]), xid)) {
+        for (uint64_t s = share_set_hash(gt, xid) & hv.set_mask;; s = (s + 1) & hv.set_mask) {
+            const ShareSetSlot e = hv.sets[s];
+            if (e.count == 0) break;
+            if (e.tg == gt && e.xid == xid) {
+                c = e.count;
+                sg = e.seg;
+                si = e.set < hv.n_sets ? e.set : hv.n_sets;
+                break;
+            }
+        }
+    }
+    if (si >= hv.n_sets) c = 0;
+    rcnt[i] = c;
+    rseg[i] = sg;
+    keys[i] = si;
+    vals[i] = i;
+}
+
+constexpr uint32_t RETRY_WIN = 256;   // failed members held in LDS at a time
+
+// v in failed[0, f)?  Wave-uniform call (every lane takes part in the loads
+// and barriers; v may differ per lane).  f <= RETRY_WIN: the list is in win
+// already (loaded once per request).  Longer lists: window by window.
+__device__ __forceinline__ bool retry_failed(uint32_t v, const uint32_t* __restrict__ failed, uint32_t f,
+                                             uint32_t* win) {
+    bool hit = false;
+    if (f <= RETRY_WIN) {
+        for (uint32_t j = 0; j < f; ++j) hit = hit || win[j] == v;
+        return hit;
+    }
+    for (uint32_t base = 0; base < f; base += RETRY_WIN) {
+        const uint32_t w = f - base < RETRY_WIN ? f - base : RETRY_WIN;
+        __syncthreads();   // the window's readers of the round before
+        for (uint32_t j = threadIdx.x; j < w; j += 64) win[j] = failed[base + j];
+        __syncthreads();
+        for (uint32_t j = 0; j < w; ++j) hit = hit || win[j] == v;
+    }
+    return hit;
+}
+
+// the members of [sg, sg + c) not in the failed list: their number, and (nth
+// != 0xFFFFFFFF) the nth of them in list order.  64 members at a time, the
+// survivors of a chunk as a ballot: its popcount counts, and the nth set bit
+// names the lane that holds the pick.
+__device__ __forceinline__ uint32_t retry_scan(const uint32_t* __restrict__ pool, uint32_t sg, uint32_t c,
+                                               const uint32_t* __restrict__ failed, uint32_t f, uint32_t* win,
+                                               uint32_t nth, uint32_t& member) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t total = 0;
+    for (uint32_t j0 = 0; j0 < c; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        const bool live = j < c;   // j0 + lane: c < 2^32 - 64 (a pool segment)
+        const uint32_t v = live ? pool[sg + j] : 0u;
+        const bool gone = retry_failed(v, failed, f, win);
+        uint64_t b = __ballot(live && !gone);
+        const uint32_t k = (uint32_t)__popcll(b);
+        if (nth != 0xFFFFFFFFu && nth >= total && nth - total < k) {
+            for (uint32_t r = nth - total; r; --r) b &= b - 1;   // drop the r lowest survivors
+            member = __shfl(v, (int)__builtin_ctzll(b), 64);
+            return total + k;
+        }
+        total += k;
+    }
+    return total;
+}
+
+// one wave per sorted pair; the wave of a run's head walks the run in request
+// order with the set's cursor and sticky entry in registers, so two requests
+// on one set see each other's state as two one-request calls would, and stores
+// both after the run's last pick (no other wave reads that set's state).
+// stateless (TM_SHARE_KEYED): every pair is a run of its own, no sort needed.
+__global__ void __launch_bounds__(64)
+tm_share_retry_pick(ShareView hv, uint32_t strategy, const uint32_t* __restrict__ keys,
+                    const uint32_t* __restrict__ vals, uint32_t n, const uint32_t* __restrict__ rcnt,
+                    const uint32_t* __restrict__ rseg, const uint32_t* __restrict__ pub_key,
+                    const uint32_t* __restrict__ failed, const uint64_t* __restrict__ failed_off,
+                    uint32_t* __restrict__ pick) {
+    __shared__ uint32_t win[RETRY_WIN];
+    const uint32_t p = blockIdx.x;
+    const uint32_t key = keys[p];
+    const bool found = key < hv.n_sets;   // else "no such set": a run of its own, TM_NO_MEMBER_ID
+    const bool stateful = strategy != TM_SHARE_KEYED && found;
+    if (stateful && p > 0 && keys[p - 1] == key) return;   // not a head (block-uniform)
+    uint32_t cur = 0xFFFFFFFFu, stk = 0xFFFFFFFFu;
+    if (stateful) {
+        cur = hv.cursor[key];
+        stk = hv.sticky[key];
+    }
+    const uint32_t cur0 = cur, stk0 = stk;
+    for (uint32_t q = p; q < n && (q == p || (stateful && keys[q] == key)); ++q) {
+        const uint32_t i = vals[q];
+        const uint32_t c = rcnt[i], sg = rseg[i];
+        const uint64_t fo = failed_off[i];
+        const uint32_t f = (uint32_t)(failed_off[i + 1] - fo);
+        const uint32_t* fl = failed + fo;
+        uint32_t out = TM_NO_MEMBER_ID;
+        if (found) {
+            __syncthreads();   // the window's readers of the request before
+            if (f <= RETRY_WIN) {
+                for (uint32_t j = threadIdx.x; j < f; j += 64) win[j] = fl[j];
+                __syncthreads();
+            }
+            // pick(sticky, ...): the stored member when defined (= alive, tm_share_sticky_down) and not failed
+            const bool stuck = strategy == TM_SHARE_STICKY && stk != 0xFFFFFFFFu && !retry_failed(stk, fl, f, win);
+            if (stuck) {
+                out = stk;
+            } else {
+                // Count' = length(subscribers(Group, Topic) -- FailedSubs)
+                uint32_t unused = 0;
+                const uint32_t left = f ? retry_scan(hv.pool, sg, c, fl, f, win, 0xFFFFFFFFu, unused) : c;
+                if (left) {
+                    uint32_t nth = 0;   // [Sub] -> Sub: no cursor, no key
+                    if (left > 1) {
+                        if (strategy == TM_SHARE_ROUND_ROBIN) {
+                            nth = cur == 0xFFFFFFFFu ? 0u : (uint32_t)(((uint64_t)cur + 1) % left);
+                            cur = nth;
+                        } else {
+                            nth = pub_key[i] % left;
+                        }
+                    }
+                    if (f) (void)retry_scan(hv.pool, sg, c, fl, f, win, nth, out);
+                    else out = hv.pool[sg + nth];
+                }
+                if (strategy == TM_SHARE_STICKY) stk = out;   // stored in every case, `false` as undefined
+            }
+        }
+        if (threadIdx.x == 0) pick[i] = out;
+    }
+    if (stateful && threadIdx.x == 0) {
+        if (cur != cur0) hv.cursor[key] = cur;
+        if (stk != stk0) hv.sticky[key] = stk;
+    }
+}
+
 static inline uint32_t hdiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const uint8_t* bytes, const uint64_t* off,
                                uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
                                const uint32_t* tg, uint64_t slots, const uint32_t* pub_key, uint32_t* pick,
                                uint32_t* cnt, uint32_t* seg, uint32_t* set, uint32_t* flag, hipStream_t st,
-                               const uint64_t* dtotal, const uint64_t* gate) {
+                               const uint64_t* dtotal, const uint64_t* gate, uint32_t* kplane, uint32_t* any) {
     if (n == 0 || slots == 0) return hipSuccess;
-    hipLaunchKernelGGL(tm_share_lookup, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, local_target, bytes, off, n,
-                       acount, aoff, to, tg, slots, pub_key, pick, cnt, seg, set, flag, dtotal, gate);
+    if (kplane)
+        hipLaunchKernelGGL(tm_share_lookup<true>, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, local_target,
+                           bytes, off, n, acount, aoff, to, tg, slots, pub_key, pick, cnt, seg, set, flag, kplane,
+                           any, dtotal, gate);
+    else
+        hipLaunchKernelGGL(tm_share_lookup<false>, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, local_target,
+                           bytes, off, n, acount, aoff, to, tg, slots, pub_key, pick, cnt, seg, set, flag, kplane,
+                           any, dtotal, gate);
     return hipGetLastError();
 }
 
@@ -299,6 +561,44 @@ hipError_t launch_share_rr_store(const ShareView& hv, const uint32_t* keys, cons
                                  const uint64_t* dm, const uint64_t* gate, hipStream_t st) {
     if (m == 0) return hipSuccess;
     hipLaunchKernelGGL(tm_share_rr_store, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, newcur, m, dm, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_share_sticky_pick(const ShareView& hv, const uint32_t* keys, const uint32_t* vals, uint32_t m,
+                                    const uint32_t* cnt, const uint32_t* seg, const uint32_t* kplane, uint32_t* pick,
+                                    uint32_t* newst, const uint64_t* dm, const uint64_t* gate, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_sticky_pick, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, vals, m, cnt,
+                       seg, kplane, pick, newst, dm, gate);
+    return hipGetLastError();
+}
+hipError_t launch_share_sticky_store(const ShareView& hv, const uint32_t* keys, const uint32_t* newst, uint32_t m,
+                                     const uint64_t* dm, const uint64_t* gate, hipStream_t st) {
+    if (m == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_sticky_store, dim3(hdiv_up(m, HBLOCK)), dim3(HBLOCK), 0, st, hv, keys, newst, m, dm,
+                       gate);
+    return hipGetLastError();
+}
+hipError_t launch_share_sticky_down(uint32_t* sticky, uint32_t n, const uint32_t* down, uint32_t k, hipStream_t st) {
+    if (n == 0 || k == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_sticky_down, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, sticky, n, down, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_share_retry_resolve(const ShareView& hv, const uint8_t* bytes, const uint64_t* off,
+                                      const uint32_t* tg, uint32_t n, uint32_t* rcnt, uint32_t* rseg, uint32_t* keys,
+                                      uint32_t* vals, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_retry_resolve, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, bytes, off, tg, n,
+                       rcnt, rseg, keys, vals);
+    return hipGetLastError();
+}
+hipError_t launch_share_retry_pick(const ShareView& hv, uint32_t strategy, const uint32_t* keys, const uint32_t* vals,
+                                   uint32_t n, const uint32_t* rcnt, const uint32_t* rseg, const uint32_t* pub_key,
+                                   const uint32_t* failed, const uint64_t* failed_off, uint32_t* pick, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_retry_pick, dim3(n), dim3(64), 0, st, hv, strategy, keys, vals, n, rcnt, rseg, pub_key,
+                       failed, failed_off, pick);
     return hipGetLastError();
 }
 

@@ -94,7 +94,7 @@ class Broker:
     def publish_shared_many(self, topics, strategy=None, keys=None):
         """publish_many with the $share clause: Published.picks = [(To, Group,
         member | None)] per $share delivery.  strategy: "round_robin", or
-        "hash" / "random" / "keyed" with keys = one u32 per topic
+        "hash" / "random" / "keyed" / "sticky" with keys = one u32 per topic
         (erlang:phash2(ClientId), or a uniform draw); default: self.shared.strategy"""
         topics = list(topics)
         buf, off = pack(topics)

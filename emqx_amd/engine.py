@@ -579,7 +579,7 @@ class Engine:
 
     # -- emqx_shared_sub: the $share member table and the pick (share.hip) ---------
     NO_MEMBER = 0xFFFFFFFF            # pick: `false`, or not a $share delivery
-    SHARE_KEYED, SHARE_ROUND_ROBIN = 1, 2
+    SHARE_KEYED, SHARE_ROUND_ROBIN, SHARE_STICKY = 1, 2, 3
 
     def share_add(self, group: bytes, topic: bytes, member: int):
         """subscribe/3: a record already in the bag leaves it as it was"""
@@ -642,8 +642,9 @@ class Engine:
     def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None):
         """match_dispatch_batch's tuple plus pick u32 (one per delivery slot):
         the member picked for a $share delivery, NO_MEMBER otherwise.
-        strategy SHARE_KEYED takes keys (u32[n]); SHARE_ROUND_ROBIN none.  A
-        short out_cap / sub_cap: as match_dispatch_batch (no cursor moves)."""
+        strategy SHARE_KEYED and SHARE_STICKY take keys (u32[n]);
+        SHARE_ROUND_ROBIN none.  A short out_cap / sub_cap: as
+        match_dispatch_batch (no cursor moves, no sticky entry is stored)."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         n = len(off) - 1
@@ -715,8 +716,35 @@ class Engine:
         return self._check(rc, "tm_publish_pack_device")
 
     def share_cursors(self, replica=0):
-        """tm_share_cursors_open: one publisher's round-robin dictionary on a replica"""
+        """tm_share_cursors_open: one publisher's dictionary (round-robin
+        cursors and sticky entries) on a replica"""
         return ShareCursors(self, replica)
+
+    def share_pick_batch(self, strategy, gbuf, goff, tbuf, toff, keys, failed, failed_off, cursors=None):
+        """tm_share_pick_batch: pick/5 with FailedSubs (the retry of
+        dispatch/4).  Request i = (group i of (gbuf, goff), To i of (tbuf,
+        toff), keys[i], failed[failed_off[i]:failed_off[i+1]]); returns
+        pick u32[n], NO_MEMBER for `false` and for a set that does not exist.
+        cursors: a ShareCursors on the first replica, None = the built-in arrays"""
+        n = len(toff) - 1
+        gbuf = np.ascontiguousarray(gbuf, dtype=np.uint8)
+        goff = np.ascontiguousarray(goff, dtype=np.uint64)
+        tbuf = np.ascontiguousarray(tbuf, dtype=np.uint8)
+        toff = np.ascontiguousarray(toff, dtype=np.uint64)
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.uint32)
+            if len(keys) != n:
+                raise ValueError("keys: one u32 per request")
+        failed = np.ascontiguousarray(failed, dtype=np.uint32)
+        failed_off = np.ascontiguousarray(failed_off, dtype=np.uint64)
+        if len(goff) != n + 1 or len(failed_off) != n + 1:
+            raise ValueError("group and failed offsets: n + 1 entries each")
+        pick = np.zeros(max(n, 1), dtype=np.uint32)
+        rc = self.lib.tm_share_pick_batch(self.h, strategy, cursors.h if cursors is not None else None, _ptr(gbuf),
+                                          _ptr(goff), _ptr(tbuf), _ptr(toff), _ptr(keys),
+                                          _ptr(failed) if len(failed) else None, _ptr(failed_off), n, _ptr(pick))
+        self._check(rc, "tm_share_pick_batch")
+        return pick[:n]
 
     def publish_stream_workspace_bytes(self, n, topic_bytes, caps):
         """caps: (ids, routes, pairs, rr)"""
@@ -776,8 +804,8 @@ class Engine:
 
 
 class ShareCursors:
-    """One publisher process's round-robin cursors on one replica
-    (tm_share_cursors; src/emqx_shared_sub.erl:243-249).  Close it before the
+    """One publisher process's round-robin cursors and sticky entries on one
+    replica (tm_share_cursors; src/emqx_shared_sub.erl:243-249, :211-224).  Close it before the
     engine; closing it afterwards only frees the host handle."""
 
     def __init__(self, engine, replica=0):

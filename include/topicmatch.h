@@ -644,6 +644,7 @@ int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_
 #define TM_NO_MEMBER         0xFFFFFFFFu   /* out_pick: `false`, or not a $share delivery  */
 #define TM_SHARE_KEYED       1u            /* pick = member (pub_key[topic] rem Count)      */
 #define TM_SHARE_ROUND_ROBIN 2u            /* pick = the set's cursor, advanced per publish */
+#define TM_SHARE_STICKY      3u            /* pick = the set's stuck member, drawn when none is */
 
 /* subscribe/3 — :77-79, a dirty_write into a bag: a record already present
  * leaves the bag as it was (first position kept). */
@@ -662,7 +663,12 @@ int tm_share_del_batch(tm_engine* e, const uint8_t* groups, const uint64_t* grou
                        const uint64_t* topic_off, const uint32_t* members, uint32_t n);
 /* cleanup_down/1 — :316-321: every record of the member, whatever the group or
  * topic (through a member -> records index, no table scan).  *removed (may be
- * NULL) = records deleted. */
+ * NULL) = records deleted.  The member is a process that exited: the commit
+ * that publishes the removal also resets every TM_SHARE_STICKY entry equal to
+ * it, in the replicas' built-in arrays and in every open context (is_alive_sub
+ * evaluated eagerly, :330-334) -- also when the member had no record left
+ * (*removed = 0: it unsubscribed everywhere, then exited).  A later
+ * tm_share_add of the same u32 is a new process. */
 int tm_share_member_down(tm_engine* e, uint32_t member, uint32_t* removed);
 /* subscribers/2 — :251-252, in insertion order.  *out_n = members (TM_ENOSPC
  * when it exceeds cap, the first cap still written). */
@@ -698,9 +704,26 @@ uint64_t tm_share_count(tm_engine* e);
  * one --; and a set that loses its last member forgets its cursor, which the
  * reference never erases.
  *
+ * TM_SHARE_STICKY (pub_key as for TM_SHARE_KEYED): pick(sticky, ...) of
+ * :211-224.  One entry {shared_sub_sticky, Group, Topic} per set beside its
+ * cursor, 0xFFFFFFFF = undefined.  A defined entry IS the pick: the stored
+ * member id, not a pool entry -- is_active_sub/2 (:327-334) tests liveness and
+ * FailedSubs, not membership, so a stuck member that unsubscribed from the set
+ * but is alive keeps being picked.  An undefined entry is drawn as `random`
+ * is, member (pub_key[t] rem Count) with the key of the publish that makes
+ * the pick, and stored in every case, [Sub] -> Sub included (a set that grows
+ * later keeps that member).  A batch gives what n one-topic batches give: for
+ * a set whose entry is undefined the first publish of the batch that reaches
+ * it (its lowest slot) draws with its own key and every later publish of the
+ * batch gets that member.  Liveness is evaluated at the commit (see
+ * tm_share_member_down), so defined implies alive and no pick tests it.  The
+ * two deviations of round robin hold unchanged: per set on the built-in array
+ * unless a context is given, and a set that loses its last member forgets its
+ * entry with the commit that frees its index.
+ *
  * Host buffers: TM_ENOSPC as tm_match_dispatch_batch; such a call writes no
- * out_pick and advances no cursor, so its retry picks what a first call
- * would have.  On the engine's first replica. */
+ * out_pick, advances no cursor and stores no sticky entry, so its retry picks
+ * what a first call would have.  On the engine's first replica. */
 int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
@@ -708,8 +731,11 @@ int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint6
                            uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick);
 /* Same with device buffers (d_pub_key too) on hip_stream, by the conventions of
  * tm_match_dispatch_batch_device: a delivery at or past out_cap is dropped,
- * gets no pick and takes no cursor value.  Round robin waits once for the
- * stream (an 8 B read-back sizes the sort). */
+ * gets no pick, takes no cursor value and cannot be the publish that draws a
+ * sticky entry.  Round robin waits once for the stream (an 8 B read-back
+ * sizes the sort).  Sticky waits once for a 4 B word that says whether any
+ * slot found its entry undefined: in the steady state none did and the call
+ * ends there, without a scan or a sort; otherwise it goes on as round robin. */
 int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
                                   uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count, uint64_t* d_out_off,
                                   uint32_t* d_out_to, uint32_t* d_out_target, uint32_t* d_out_ndisp, uint64_t out_cap,
@@ -751,7 +777,7 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
                            tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
                            void* hip_stream);
 
-/* ---- round-robin cursor contexts ---------------------------------------------
+/* ---- publisher contexts: round-robin cursors and sticky entries --------------
  * do_pick_subscriber(Group, Topic, round_robin, _ClientId, Count) keeps its
  * counter in the PUBLISHER's process dictionary, under {shared_sub_round_robin,
  * Group, Topic} (src/emqx_shared_sub.erl:243-249): every publisher process
@@ -767,6 +793,10 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
  * contexts are independent: each one's first use of a set gives Rem 0.  With
  * one context per publisher the first deviation listed at TM_SHARE_ROUND_ROBIN
  * (cursor per set instead of per publisher) is gone.
+ * The context is the publisher's whole dictionary: beside each cursor it holds
+ * the set's {shared_sub_sticky, Group, Topic} entry (:212, :222; a member id,
+ * 0xFFFFFFFF = undefined), kept by tm_commit by the same three rules, plus the
+ * reset of the entries equal to a member reported by tm_share_member_down.
  * TM_EDEVICE on a host-only engine, TM_EINVAL for a replica out of range.
  * Order of closing: close a context before its engine.  tm_close with
  * contexts still open waits for the device, releases their device memory
@@ -799,18 +829,19 @@ void tm_share_cursors_close(tm_share_cursors* c);
  *   caps.routes  the match_routes/1 total = delivery slots (aggre writes each
  *                topic's list at its route offset) = records of d_deliv
  *   caps.pairs   (To, subscriber) pairs = records of d_pairs
- *   caps.rr      delivery slots with Count >= 2 that round robin ranks
+ *   caps.rr      delivery slots with Count >= 2 that round robin ranks, or
+ *                delivery slots whose sticky entry is undefined
  *                (ignored for TM_SHARE_KEYED)
  * each below 2^32 - 2 (TM_ERANGE).  d_hdr[TM_PUBLISH_HDR_WORDS]:
  *   [0..3] {route total, pair total, D, P} as tm_publish_pack_device
- *   [4]    match id total        [5] slots ranked by round robin (0 for keyed)
+ *   [4]    match id total        [5] slots ranked by round robin / drawn by sticky (0 for keyed)
  *   [6]    state: 0 = every stage ran within its capacity, else the first
  *          stage whose total exceeded it: 1 ids, 2 routes, 3 pairs, 4 rr
  *   [7]    0
  * State 0: d_hdr[0..3], d_doff[n+1], d_sub_off[n+1], the D records and the P
  * pairs are bit for bit what the two calls above leave with out_cap =
  * deliv_cap = caps.routes and sub_cap = pair_cap = caps.pairs; the picks
- * follow TM_SHARE_KEYED / TM_SHARE_ROUND_ROBIN as documented at
+ * follow TM_SHARE_KEYED / TM_SHARE_ROUND_ROBIN / TM_SHARE_STICKY as documented at
  * tm_match_publish_batch, with `cursors` as the publisher's dictionary (NULL:
  * the replica's built-in array, the one tm_match_publish_batch_device uses).
  * Round-robin publishes count in topic-index order within the call and in
@@ -818,25 +849,31 @@ void tm_share_cursors_close(tm_share_cursors* c);
  * State != 0: the totals of the stages up to and including the one named are
  * exact (and D whenever the state is 3 or 4), later totals are 0, d_doff,
  * d_sub_off and the records are unspecified, nothing has been written at or
- * past any capacity in outputs or workspace, and NO CURSOR HAS CHANGED: a
+ * past any capacity in outputs or workspace, and NO CURSOR OR STICKY ENTRY HAS CHANGED: a
  * state word in the workspace is set once a stage's total is known, every
- * later kernel tests it first and leaves, and the store of the new cursors is
- * the call's last kernel and runs only in state 0.  The caller sizes a rerun
+ * later kernel tests it first and leaves, and the store of the new cursors
+ * (or sticky entries) is the call's last kernel and runs only in state 0.  The caller sizes a rerun
  * from the header; the rerun picks what a first run would have.
  * The radix sort of the (set index, slot) pairs runs over caps.rr pairs padded
  * with key 0xFFFFFFFF, over the bits the set indices need: the padding's
  * digits are all 255 and the sort is stable, so it stays last.
  * Two calls in flight on different streams must not share a context (nor
- * both pass NULL with round robin): the second would read cursors the first
+ * both pass NULL with round robin or sticky): the second would read state the first
  * has not stored yet.  Calls on one stream may.
  * n == 0: a zero header and d_doff[0] = d_sub_off[0] = 0.
  * TM_EINVAL: a null d_topic_off, d_hdr, d_doff, d_sub_off, caps or
- * d_workspace; a null d_pub_key with TM_SHARE_KEYED (n > 0); caps.routes with
- * a null d_deliv or caps.pairs with a null d_pairs; a strategy that is neither
- * of the two; workspace_bytes below the need (all before anything is
+ * d_workspace; a null d_pub_key with TM_SHARE_KEYED or TM_SHARE_STICKY (n > 0);
+ * caps.routes with a null d_deliv or caps.pairs with a null d_pairs; a strategy
+ * that is none of the three; workspace_bytes below the need (all before anything is
  * enqueued); tm_set_local_node not called; a context of another engine or
  * replica than the one that owns d_topic_off.  TM_EDEVICE on a host-only
  * engine. */
+/* The workspace need is one function of n and the capacities, the same for
+ * every strategy.  It includes (caps.routes + 1) * 4 bytes (rounded up to 256)
+ * for the keys of the slots TM_SHARE_STICKY flags, placed after everything
+ * else: with that strategy's arrival the need grew by as much for
+ * TM_SHARE_KEYED and TM_SHARE_ROUND_ROBIN callers too, who must query the size
+ * (tm_publish_stream_workspace_bytes) rather than keep a figure from before. */
 typedef struct tm_publish_caps { uint64_t ids, routes, pairs, rr; } tm_publish_caps;
 #define TM_PUBLISH_HDR_WORDS 8
 uint64_t tm_publish_stream_workspace_bytes(tm_engine* e, uint32_t n, uint64_t topic_bytes,
@@ -846,6 +883,38 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_topic_bytes, const u
                              tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
                              uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
                              tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream);
+
+/* The retry of dispatch/4 (src/emqx_shared_sub.erl:92-111): after a nack, a
+ * timeout or a 'DOWN' the broker picks again with the failed members removed.
+ * out_pick[i] = pick(Strategy, _, Group_i, Topic_i, FailedSubs_i) of :211-249,
+ * with the cursors and sticky entries where the publish calls keep them: in
+ * `cursors`, NULL = the first replica's built-in arrays.  Host buffers,
+ * synchronous, on the engine's first replica: the tm_dispatch_batch of picks.
+ * Request i: group bytes [group_off[i], group_off[i+1]), topic bytes
+ * [topic_off[i], topic_off[i+1]) (the To of the delivery; the set is found by
+ * its bytes in the committed image), pub_key[i], and the failed members
+ * failed[failed_off[i] .. failed_off[i+1]) (any length, non-members allowed).
+ * The remaining list is the set's members in insertion order without the
+ * failed ones (`--` :229; members of a set never repeat).  TM_NO_MEMBER stands
+ * for `false` and for a set that does not exist.
+ *   TM_SHARE_KEYED        entry (pub_key[i] rem Count') of the remaining list
+ *   TM_SHARE_ROUND_ROBIN  one member left: that one, cursor untouched (:231);
+ *                         else the cursor advances with Count' = the remaining
+ *                         length (:243-249).  pub_key may be NULL.
+ *   TM_SHARE_STICKY       the stuck member unless it is undefined or in the
+ *                         failed list (is_active_sub/2, :327-334); else the
+ *                         keyed pick of the remaining list, stored in every
+ *                         case (`false` as undefined) (:218-223)
+ * Requests count in index order, as n one-request calls would: two requests
+ * for one set in one call see each other's state.
+ * TM_EINVAL: a null array with n > 0 (pub_key only for KEYED and STICKY,
+ * failed only when some list is non-empty), offsets not monotone, an unknown
+ * strategy, a context of another engine or replica.  TM_EDEVICE on a host-only
+ * engine.  emqx_amd/csrc/share.hip tm_share_retry_pick: one wave per request. */
+int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* cursors, const uint8_t* groups,
+                        const uint64_t* group_off, const uint8_t* topics, const uint64_t* topic_off,
+                        const uint32_t* pub_key, const uint32_t* failed, const uint64_t* failed_off, uint32_t n,
+                        uint32_t* out_pick);
 
 /* ---- publish micro-batcher (emqx_amd/csrc/batcher.cpp) -----
  * emqx_broker:publish/1 (src/emqx_broker.erl:148-157) matches one topic per
@@ -900,7 +969,13 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_topic_bytes, const u
  * runs tm_publish_stream_device instead of the two calls above and returns
  * the same records.  An A/B switch like TM_BATCHER_CSR, not a tuning knob: the
  * next change keeps one of the two keyed paths, on the measurements.
- * `sticky` stays with the caller.  A publish batcher takes
+ * TM_BATCHER_STICKY (with TM_BATCHER_PUBLISH and without
+ * TM_BATCHER_ROUND_ROBIN, else TM_EINVAL): the picks are `sticky`
+ * (src/emqx_shared_sub.erl:211-224) with the pub_key of each submit.  As with
+ * round robin a lane is a publisher process with one context, the batch runs
+ * tm_publish_stream_device (caps.rr bounds the slots whose entry is undefined),
+ * and a batch that is rerun has stored no entry.
+ * A publish batcher takes
  * tm_batcher_submit_publish only (tm_batcher_submit: TM_EINVAL, nothing
  * queued), and tm_batcher_submit_publish needs the flag (else TM_EINVAL).
  * done() gets topic's delivery records {to, target, ndisp, pick} in aggre's
@@ -925,6 +1000,7 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_topic_bytes, const u
 #define TM_BATCHER_PUBLISH 16u   /* results are publish/1 up to the sends: deliveries with Count and pick, and the pairs */
 #define TM_BATCHER_ROUND_ROBIN 32u   /* publish mode: round-robin picks, one cursor context per lane */
 #define TM_BATCHER_STREAM 64u   /* publish mode: keyed picks through tm_publish_stream_device (A/B) */
+#define TM_BATCHER_STICKY 128u   /* publish mode: sticky picks, one context per lane */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {

@@ -14,12 +14,24 @@ each call on the caller's stream, 3 warm-ups then the median of 10:
     keyed         tm_match_publish_batch_device, TM_SHARE_KEYED
     round_robin   tm_match_publish_batch_device, TM_SHARE_ROUND_ROBIN (includes its
                   one wait for the stream, so the host clock is reported beside the events)
-keyed - dispatch and round_robin - dispatch are the added milliseconds.
+    sticky        tm_match_publish_batch_device, TM_SHARE_STICKY in the steady state: every
+                  entry defined, so no slot is flagged and nothing is sorted (the same one
+                  wait for the stream as round robin)
+keyed - dispatch, round_robin - dispatch and sticky - dispatch are the added milliseconds.
+The cold sticky batch -- the first of the process on this engine, every entry
+undefined, every group delivery with a set flagged, compacted and sorted -- can
+be taken once only: one sample, timed the same way, after a one-topic sticky
+publish on a throw-away engine has loaded every kernel of the path.
+
+After those, the same batch runs through tm_publish_stream_device (the batcher's
+call for round robin and sticky) with each strategy, interleaved and timed the
+same way on the built-in arrays, so sticky is in its steady state there too.
 
 Before anything is timed, --check topics of the batch are compared with
 tests/shared_ref.py over oracle aggre/1 of O1's ordered match lists: the keyed
 picks, and the round-robin picks of the first call (cursors undefined; the
-picks of a batch's first k topics depend on no later topic).
+picks of a batch's first k topics depend on no later topic), and the sticky
+picks of the cold batch against tests/sticky_ref.py.
 
 Run:  python tools/bench_shared.py [--topics N --check K --out FILE]
       python tools/bench_shared.py --write-design FILE   (no GPU: puts the figures of FILE into DESIGN.md)
@@ -61,6 +73,21 @@ def write_design(path):
             (r["workload"], ms["dispatch"], add["keyed"], add["round_robin"], r["host_clock_ms_median"]["dispatch"],
              r["host_clock_ms_median"]["keyed"], r["host_clock_ms_median"]["round_robin"], r["delivery_slots"],
              r["group_deliveries"], r["rr_ranked"]))
+    if "sticky" in add:
+        cold = r["sticky_cold"]
+        text += (" Sticky in the steady state (every entry defined, nothing flagged) adds %.2f ms (host clock %.2f ms); "
+                 "the cold first batch, one sample, %d slots flagged and sorted (derived, not read from the device: "
+                 "with every entry undefined that is every group delivery with a set), took %.2f ms (host clock %.2f ms), "
+                 "%.2f ms over the dispatch median." %
+                 (add["sticky"], r["host_clock_ms_median"]["sticky"], cold["flagged"], cold["ms"], cold["host_clock_ms"],
+                  cold["ms"] - ms["dispatch"]))
+    if "stream_call" in r:
+        sc = r["stream_call"]
+        text += (" The same batch through `tm_publish_stream_device` (match, routes, aggre, dispatch, picks and pack in "
+                 "one call; built-in arrays, sticky in its steady state with %d slots flagged; caps.rr %d): keyed %.2f ms, "
+                 "round robin %.2f ms (%d slots ranked), sticky %.2f ms." %
+                 (sc["flagged_slots_hdr5"]["sticky"], sc["caps_rr"], sc["ms_median"]["keyed"],
+                  sc["ms_median"]["round_robin"], sc["flagged_slots_hdr5"]["round_robin"], sc["ms_median"]["sticky"]))
     p = os.path.join(ROOT, "DESIGN.md")
     s = open(p).read()
     pat = re.compile(re.escape(MARK[0]) + ".*?" + re.escape(MARK[1]), re.S)
@@ -154,7 +181,36 @@ def main():
 
     def publish(strategy):
         e.match_publish_batch_device(d_b, d_o, n, nbytes, c, o, dto, dtg, dnd, cap, tot, sc, so_, sto, sid, scap, stot,
-                                     strategy, d_k if strategy == Engine.SHARE_KEYED else None, dpk, stream=st)
+                                     strategy, None if strategy == Engine.SHARE_ROUND_ROBIN else d_k, dpk, stream=st)
+
+    # the sticky kernels loaded by a one-topic publish on a throw-away engine, so
+    # that the one cold batch below pays for its work only
+    w = Engine(device=0)
+    w.route_add(b"w", gdest(b"w"))
+    w.dest_target(gdest(b"w"), Engine.TARGET_GROUP, b"w")
+    w.dest_target(NODE, Engine.TARGET_NODE, NODE)
+    w.set_local_node(NODE)
+    kb, ko = pack([b"x"] * 300)                            # 300 more sets: the set indices need a radix pass
+    mb, mo = pack([b"x/%d" % i for i in range(300)])
+    w.share_add_many(kb, ko, mb, mo, np.arange(300, dtype=np.uint32))
+    w.share_add(b"w", b"w", 1001)
+    w.share_add(b"w", b"w", 1002)
+    wb, wo = pack([b"w"])
+    assert int(w.match_publish_batch(wb, wo, Engine.SHARE_STICKY, [1])[9][0]) == 1002
+    w.close()
+
+    def timed(fn):
+        ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        ea.record(st)
+        fn()
+        eb.record(st)
+        torch.cuda.synchronize(dev)
+        return ea.elapsed_time(eb), (time.perf_counter() - t0) * 1e3
+    cold_ms, cold_host = timed(lambda: publish(Engine.SHARE_STICKY))   # the only batch that finds no entry defined
+    cold_off, cold_cnt = o.cpu().numpy(), c.cpu().numpy()
+    cold_pk = dpk[:slots].cpu().numpy().view(np.uint32).copy()
 
     # ---- parity of the first k topics
     check = None
@@ -162,6 +218,7 @@ def main():
         from oracle import O1
         from oracle.pytrie import aggre
         from shared_ref import SharedSub
+        from sticky_ref import StickySub
         k = min(a.check, n)
         names = filters + ([b"#"] if hot_id == nf else [])
         fb2, fo2 = pack(names)
@@ -176,7 +233,9 @@ def main():
         for j, g in enumerate(HOT):
             for m in range(64):
                 ref.subscribe(g, b"#", hot_base + 64 * j + m)
-        want = {"keyed": [], "round_robin": []}
+        sref = StickySub()
+        sref.tab, sref.alive = ref.tab, {m for ms_ in ref.tab.values() for m in ms_}
+        want = {"keyed": [], "round_robin": [], "sticky": []}
         for t in range(k):
             routes = []
             for f in (int(x) for x in oi[int(oo[t]):int(oo[t + 1])]):
@@ -188,14 +247,20 @@ def main():
                     routes += [(b"#", (g, NODE)) for g in HOT]
             dels = aggre(routes)
             for s in want:
+                if s == "sticky":
+                    want[s].append([sref.pick(s, int(keys[t]), x, name) if kind == 1 else None for name, (kind, x) in dels])
+                    continue
                 want[s].append([ref.do_pick(s, int(keys[t]), x, name) if kind == 1 else None
                                 for name, (kind, x) in dels])
         check = {"topics": k}
-        for s, strategy in (("keyed", Engine.SHARE_KEYED), ("round_robin", Engine.SHARE_ROUND_ROBIN)):
-            publish(strategy)
-            torch.cuda.synchronize(dev)
-            off, cnt = o[: k + 1].cpu().numpy(), c[:k].cpu().numpy()
-            pk = dpk[: int(off[k])].cpu().numpy().view(np.uint32)
+        for s, strategy in (("keyed", Engine.SHARE_KEYED), ("round_robin", Engine.SHARE_ROUND_ROBIN), ("sticky", None)):
+            if strategy is None:                           # the cold batch above: it cannot be run again
+                off, cnt, pk = cold_off[: k + 1], cold_cnt[:k], cold_pk
+            else:
+                publish(strategy)
+                torch.cuda.synchronize(dev)
+                off, cnt = o[: k + 1].cpu().numpy(), c[:k].cpu().numpy()
+                pk = dpk[: int(off[k])].cpu().numpy().view(np.uint32)
             for t in range(k):
                 got = [None if int(x) == Engine.NO_MEMBER else int(x) for x in pk[int(off[t]):int(off[t]) + int(cnt[t])]]
                 if got != want[s][t]:
@@ -205,24 +270,42 @@ def main():
 
     # ---- timing
     fns = {"dispatch": lambda: dispatch(scap, sto, sid), "keyed": lambda: publish(Engine.SHARE_KEYED),
-           "round_robin": lambda: publish(Engine.SHARE_ROUND_ROBIN)}
+           "round_robin": lambda: publish(Engine.SHARE_ROUND_ROBIN), "sticky": lambda: publish(Engine.SHARE_STICKY)}
     ms, host = {k_: [] for k_ in fns}, {k_: [] for k_ in fns}
     warmups, runs = 3, 10
     for it in range(warmups + runs):
         for name, fn in fns.items():
-            ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            ea.record(st)
-            fn()
-            eb.record(st)
-            torch.cuda.synchronize(dev)
-            t1 = time.perf_counter()
+            dev_ms, host_ms = timed(fn)
             if it >= warmups:
-                ms[name].append(ea.elapsed_time(eb))
-                host[name].append((t1 - t0) * 1e3)
+                ms[name].append(dev_ms)
+                host[name].append(host_ms)
     med = {k_: float(np.median(v)) for k_, v in ms.items()}
     hmed = {k_: float(np.median(v)) for k_, v in host.items()}
+
+    # ---- the same batch through tm_publish_stream_device (the batcher's call for round robin and sticky), the
+    # three strategies interleaved in the same way; built-in arrays, so sticky is in its steady state.  That call
+    # reads nothing back: with nothing flagged it still scans the flags and sorts caps.rr padding pairs.
+    caps = (cap, cap, scap, int(slots // 8) + 1024)        # match ids <= routes here: every filter has a local route
+    wsb = e.publish_stream_workspace_bytes(n, nbytes, caps)
+    d_ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    d_hdr, d_doff, d_soff = torch.zeros(8, **i64), torch.empty(n + 1, **i64), torch.empty(n + 1, **i64)
+    d_deliv, d_pairs = torch.empty(cap * 4, **i32), torch.empty(scap * 2, **i32)
+
+    def stream(strategy):
+        e.publish_stream_device(d_b, d_o, n, nbytes, strategy, None if strategy == Engine.SHARE_ROUND_ROBIN else d_k,
+                                None, caps, d_ws, wsb, d_hdr, d_doff, d_soff, d_deliv, d_pairs, stream=st)
+    sfns = {"keyed": Engine.SHARE_KEYED, "round_robin": Engine.SHARE_ROUND_ROBIN, "sticky": Engine.SHARE_STICKY}
+    sms, sflag = {k_: [] for k_ in sfns}, {}
+    for it in range(warmups + runs):
+        for name, strategy in sfns.items():
+            dev_ms, _ = timed(lambda: stream(strategy))
+            h = [int(x) for x in d_hdr.cpu().numpy()]
+            if h[6] != 0:
+                raise SystemExit("stream call %s: state %d, header %s" % (name, h[6], h))
+            sflag[name] = h[5]
+            if it >= warmups:
+                sms[name].append(dev_ms)
+    smed = {k_: float(np.median(v)) for k_, v in sms.items()}
     publish(Engine.SHARE_KEYED)
     torch.cuda.synchronize(dev)
     tg_h = dtg[:slots].cpu().numpy()
@@ -235,13 +318,14 @@ def main():
     is_group = live & np.isin(tg_h, list(group_tg))
     out = {"workload": "C%d: %d filters, one local route each, %d with a group route and a member set (mean 4), "
                        "'#' with 2 groups of 64; %d-topic batch" % (a.config, nf, len(shared), a.topics),
-           "method": "HIP events around each call on the caller's stream, 3 warm-ups, median of 10, the three calls "
-                     "interleaved",
+           "method": "HIP events around each call on the caller's stream, 3 warm-ups, median of 10, the four calls "
+                     "interleaved; sticky_cold: the engine's first sticky batch, one sample",
            "ms_median": med, "ms_min_max": {k_: [min(v), max(v)] for k_, v in ms.items()},
            "host_clock_ms_median": hmed,
-           "added_ms": {"keyed": med["keyed"] - med["dispatch"], "round_robin": med["round_robin"] - med["dispatch"]},
-           "added_host_clock_ms": {"keyed": hmed["keyed"] - hmed["dispatch"],
-                                   "round_robin": hmed["round_robin"] - hmed["dispatch"]},
+           "added_ms": {k_: med[k_] - med["dispatch"] for k_ in ("keyed", "round_robin", "sticky")},
+           "added_host_clock_ms": {k_: hmed[k_] - hmed["dispatch"] for k_ in ("keyed", "round_robin", "sticky")},
+           "stream_call": {"ms_median": smed, "ms_min_max": {k_: [min(v), max(v)] for k_, v in sms.items()},
+                           "flagged_slots_hdr5": sflag, "caps_rr": caps[3]},
            "delivery_slots": slots, "group_deliveries": int(is_group.sum()),
            "picks": int((is_group & (pk_h != Engine.NO_MEMBER)).sum()),
            "members": int(e.share_count), "check": check}
@@ -250,6 +334,10 @@ def main():
     to_h = dto[:slots].cpu().numpy().view(np.uint32)
     tname = {int(t): e.target_bytes(int(t))[1] for t in group_tg}
     gi = np.nonzero(is_group)[0]
+    # the cold sticky batch flags every group delivery that has a set = every one with a pick:
+    # derived from the keyed batch's picks, the call does not report its own count
+    out["sticky_cold"] = {"ms": cold_ms, "host_clock_ms": cold_host, "flagged": out["picks"],
+                          "flagged_is": "derived: group deliveries with a pick, every entry being undefined"}
     out["rr_ranked"] = int(sum(1 for j in gi if (tname[int(tg_h[j])], int(to_h[j])) not in one))
     e.close()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

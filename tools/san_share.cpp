@@ -158,6 +158,19 @@ int main() {
         ok(tm_share_add(E, u8(groups[1]), 2, u8(t), (uint32_t)t.size(), rnd(50)), "tm_share_add");
     }
     phase("share refilled");
+    {   // the retry pick's host side: its argument checks, then "no device" on this host-only engine
+        const std::string gg = groups[0] + groups[1], tt = topics[0] + topics[1];
+        const uint64_t goff[3] = {0, 2, 4}, toff[3] = {0, topics[0].size(), tt.size()}, foff[3] = {0, 1, 3};
+        const uint32_t keys[2] = {1, 2}, failed[3] = {1, 2, 3};
+        uint32_t out[2];
+        for (uint32_t strategy = 0; strategy < 5; ++strategy) {
+            const int rc = tm_share_pick_batch(E, strategy, nullptr, u8(gg), goff, u8(tt), toff, keys, failed, foff, 2, out);
+            if (rc != (strategy >= 1 && strategy <= 3 ? TM_EDEVICE : TM_EINVAL)) return 1;
+        }
+        if (tm_share_pick_batch(E, TM_SHARE_STICKY, nullptr, u8(gg), goff, u8(tt), toff, keys, nullptr, foff, 2, out) !=
+            TM_EINVAL)
+            return 1;
+    }
 
     // ---- routes and subscribers ----
     // more topics than the tables' first 16 slots hold several times over
