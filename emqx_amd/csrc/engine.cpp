@@ -460,6 +460,7 @@ struct Image {
     // share image (share.hip), same epoch; cursor: the replica's round-robin
     // cursors (DevState::sh_cursor) as they were when this image was written
     DevBuf d_hsets, d_htx, d_harena, d_hpool, d_hfx;
+    DevBuf d_fwd;      // forward table (forward.hip): target id -> forwardable node, same epoch
     uint32_t* cursor = nullptr;
     uint32_t* sticky = nullptr;   // the replica's sticky entries (DevState::sh_sticky), likewise
     DevBuf d_wheat;    // word id -> heat (option "presort" 2: the tail order's cost estimate)
@@ -477,10 +478,12 @@ struct Image {
     AggreView av{};
     SubView sv{};
     ShareView hv{};
+    ForwardView fv{};
     void release() {
         for (DevBuf* b : {&d_nodes, &d_edges, &d_hedges, &d_dict, &d_arena, &d_woff, &d_inner, &d_leaf, &d_rslots,
                           &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat,
-                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx})
+                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx,
+                          &d_fwd})
             b->release();
         for (hipEvent_t ev : uses) (void)hipEventDestroy(ev);
         uses.clear();
@@ -582,6 +585,10 @@ struct DevState {
     // targets, failed lists and offsets; commit: the sorted downed members
     DevBuf w_hkplane, w_htg, w_hfail, w_hfoff, w_hdown;
     DevBuf w_pscan;   // publish pack (pack.hip): the scan of the topics' delivery counts
+    // forward plan (forward.hip): per-slot flag / publish index and the flag
+    // prefix, the (key, slot) pairs and their sort, the head flags and their
+    // prefixes, and the host-buffer call's planes and results
+    DevBuf w_fflag, w_fpub, w_fpre, w_fscan, w_fpairs, w_fhead, w_fhpre, w_fcounts, w_foff, w_fsscan, w_fin, w_fout;
     // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
     // the image epochs, so a batch continues where the one before it stopped
     // whichever image each was launched on
@@ -636,7 +643,8 @@ struct DevState {
                           &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
                           &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
                           &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor, &sh_sticky, &w_hkplane,
-                          &w_htg, &w_hfail, &w_hfoff, &w_hdown,
+                          &w_htg, &w_hfail, &w_hfoff, &w_hdown, &w_fflag, &w_fpub, &w_fpre, &w_fscan, &w_fpairs,
+                          &w_fhead, &w_fhpre, &w_fcounts, &w_foff, &w_fsscan, &w_fin, &w_fout,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -909,6 +917,10 @@ struct tm_engine {
     std::vector<uint2> dt;                  // dest id -> {target rank, target id | group << 31}
     std::vector<uint32_t> rank_tg;          // target rank -> target id
     bool targets_dirty = true;              // a dest or a dest's target was added: re-rank the targets
+    // forward/3 (forward.hip): target id -> 1 for a node target other than
+    // node(), else 0; rebuilt with the ranks (tm_set_local_node marks them dirty)
+    std::vector<uint32_t> fwd_tg;
+    Track t_fwd;
 
     // ---- subscriber table: the emqx_subscriber duplicate_bag ----
     // (src/emqx_broker_sup.erl:55-67; insert_subscriber/3 src/emqx_broker.erl:398-415,
@@ -2223,9 +2235,20 @@ struct tm_engine {
             const uint32_t tid = dest_target[d];
             dt[d] = make_uint2(trank[tid], tid | (target_names[tid][0] ? 0x80000000u : 0u));
         }
+        fwd_tg.resize(target_names.size());
+        for (uint32_t i = 0; i < fwd_tg.size(); ++i)
+            fwd_tg[i] = (uint8_t)target_names[i][0] == TM_TARGET_NODE && !(local_set && i == local_target) ? 1u : 0u;
         t_dt.cur.all = true;
         t_rank_tg.cur.all = true;
+        t_fwd.cur.all = true;
         targets_dirty = false;
+    }
+    ForwardView make_forward_view(const Image& g) const {
+        ForwardView fv;
+        fv.fwd = g.d_fwd.as<const uint32_t>();
+        fv.n_targets = (uint32_t)fwd_tg.size();
+        fv.n_filters = (uint32_t)fr.meta.size();
+        return fv;
     }
     AggreView make_aggre_view(const Image& g) const {
         AggreView av;
@@ -2496,12 +2519,14 @@ struct tm_engine {
     static const AggreView& aggre_view(const DevState& d) { return d.img[d.bimg].av; }
     static const SubView& sub_view(const DevState& d) { return d.img[d.bimg].sv; }
     static const ShareView& share_view(const DevState& d) { return d.img[d.bimg].hv; }
+    static const ForwardView& forward_view(const DevState& d) { return d.img[d.bimg].fv; }
     void capture_views(Image& g) const {
         g.iv = make_view(g);
         g.rv = make_route_view(g);
         g.av = make_aggre_view(g);
         g.sv = make_sub_view(g);
         g.hv = make_share_view(g);
+        g.fv = make_forward_view(g);
     }
     // the views of image g, from the host tables it was just written from
     ImageView make_view(const Image& g) const {
@@ -2549,6 +2574,7 @@ struct tm_engine {
         f(rank_src, t_rank_src, &Image::d_rank_src, true);
         f(dt, t_dt, &Image::d_dt, true);
         f(rank_tg, t_rank_tg, &Image::d_rank_tg, true);
+        f(fwd_tg, t_fwd, &Image::d_fwd, true);
         f(sx_slots.slots, sx_slots.t, &Image::d_sslots, true);
         f(sx_arena.words, sx_arena.t, &Image::d_sarena, true);
         f(sx_pool.v, sx_pool.t, &Image::d_spool, true);
@@ -3207,6 +3233,80 @@ struct tm_engine {
         HIPCHK(hipMemcpyAsync(sub_total, d.w_xpre.as<uint64_t>() + slots, 8, hipMemcpyDeviceToDevice, st));
         if (strategy) share_pick(d, bytes, off, n, counts, out_off, to, target, slots, strategy, pub_key, pick, st);
         d.note_use(st);   // the dispatch and share kernels read the pinned images after the walk's use
+        d.rw_release(st);
+    }
+
+    // forward/3's plan over a batch's deliveries planes (forward.hip): the
+    // forward deliveries grouped per (target, To).  cap is the planes' capacity
+    // (the flag scan runs over it; the live slots are min(*dtotal, cap)).  One
+    // 8 B read-back, the number of forward deliveries, sizes the sorts, which
+    // cover the bits of the filter ids and of the target ids handed out.
+    void forward_plan(DevState& d, uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,
+                      const uint32_t* tg, uint64_t cap, const uint64_t* dtotal, uint64_t* hdr, void* groups,
+                      uint64_t group_cap, uint32_t* pub, uint64_t pub_cap, hipStream_t st) {
+        if (n == 0 || cap == 0) {
+            HIPCHK(hipMemsetAsync(hdr, 0, TM_FORWARD_HDR_WORDS * 8, st));
+            return;
+        }
+        if (cap >= 0xFFFFFFFEull) throw RangeError("forward: more than 2^32 - 2 delivery slots in one batch");
+        const ForwardView& fv = forward_view(d);
+        d.rw_drain();
+        d.w_fflag.ensure((size_t)cap * 4 + 4);
+        d.w_fpub.ensure((size_t)cap * 4 + 4);
+        d.w_fpre.ensure((size_t)(cap + 1) * 8);
+        d.w_fscan.ensure(scan_tmp_elems((uint32_t)cap) * 8 + 8);
+        uint32_t* flag = d.w_fflag.as<uint32_t>();
+        uint32_t* pubidx = d.w_fpub.as<uint32_t>();
+        uint64_t* P = d.w_fpre.as<uint64_t>();
+        HIPCHK(hipMemsetAsync(flag, 0, (size_t)cap * 4, st));   // the slots the flag pass does not reach
+        HIPCHK(launch_forward_flag(fv, n, acount, aoff, tg, cap, dtotal, flag, pubidx, st));
+        HIPCHK(launch_scan0(flag, (uint32_t)cap, P, P + cap, d.w_fscan.as<uint64_t>(), st));
+        uint64_t m64 = 0;
+        HIPCHK(hipMemcpyAsync(&m64, P + cap, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (m64 == 0) {
+            HIPCHK(hipMemsetAsync(hdr, 0, TM_FORWARD_HDR_WORDS * 8, st));
+            d.note_use(st);
+            d.rw_release(st);
+            return;
+        }
+        const uint32_t m = (uint32_t)m64;
+        uint32_t to_bits = 0, tg_bits = 0;
+        while (to_bits < 32 && ((uint64_t)1 << to_bits) <= fv.n_filters) ++to_bits;   // keys 0 .. n_filters
+        while (tg_bits < 32 && ((uint64_t)1 << tg_bits) < fv.n_targets) ++tg_bits;    // keys below n_targets
+        const uint32_t to_passes = (to_bits + 7) / 8, tg_passes = (tg_bits + 7) / 8, pc = presort_counts(m);
+        d.w_fpairs.ensure((size_t)m * 16);
+        d.w_fhead.ensure((size_t)m * 8);
+        d.w_fhpre.ensure((size_t)(m + 1) * 16);
+        d.w_fcounts.ensure((size_t)pc * 4);
+        d.w_foff.ensure((size_t)(pc + 1) * 8);
+        d.w_fsscan.ensure(std::max(scan_tmp_elems(pc), scan_tmp_elems(m)) * 8 + 8);
+        uint32_t* k0 = d.w_fpairs.as<uint32_t>();
+        uint32_t *v0 = k0 + m, *k1 = v0 + m, *v1 = k1 + m;
+        uint32_t* counts = d.w_fcounts.as<uint32_t>();
+        uint64_t* off = d.w_foff.as<uint64_t>();
+        uint64_t* stmp = d.w_fsscan.as<uint64_t>();
+        HIPCHK(launch_forward_compact(fv, flag, P, to, cap, k0, v0, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, m, to_passes, counts, off, stmp, st));
+        if (to_passes & 1u) {   // an odd number of passes left the pairs in (k1, v1)
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        HIPCHK(launch_forward_retarget(k0, v0, tg, m, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, m, tg_passes, counts, off, stmp, st));
+        if (tg_passes & 1u) {
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        uint32_t* head = d.w_fhead.as<uint32_t>();
+        uint32_t* thead = head + m;
+        uint64_t* H = d.w_fhpre.as<uint64_t>();
+        uint64_t* T = H + m + 1;
+        HIPCHK(launch_forward_heads(k0, v0, to, m, head, thead, st));
+        HIPCHK(launch_scan0(head, m, H, H + m, stmp, st));
+        HIPCHK(launch_scan0(thead, m, T, T + m, stmp, st));
+        HIPCHK(launch_forward_groups(k0, v0, to, pubidx, head, H, T, m, hdr, groups, group_cap, pub, pub_cap, st));
+        d.note_use(st);   // the flag pass read the pinned image's target table
         d.rw_release(st);
     }
 
@@ -4947,6 +5047,78 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
             return rc;
         });
     return rc;
+}
+
+static_assert(sizeof(tm_forward_group) == 16, "forward.hip stores 16 B group records");
+
+int tm_forward_plan_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                           const uint32_t* d_to, const uint32_t* d_target, uint64_t out_cap,
+                           const uint64_t* d_total, uint64_t* d_hdr, tm_forward_group* d_groups,
+                           uint64_t group_cap, uint32_t* d_pub, uint64_t pub_cap, void* hip_stream) {
+    if (!d_hdr || !d_off || !d_total || (n && !d_count) || (out_cap && (!d_to || !d_target)) ||
+        (group_cap && !d_groups) || (pub_cap && !d_pub))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (int rc = local_node_unset(e)) return rc;
+    if (e->devs.empty()) return no_device(e, "forward plan");
+    DevState& d = *e->replica_for(d_off);
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        e->forward_plan(d, n, d_count, d_off, d_to, d_target, out_cap, d_total, d_hdr, d_groups, group_cap, d_pub,
+                        pub_cap, st);
+        return TM_OK;
+    }, [] {});
+}
+
+int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint64_t* off, const uint32_t* to,
+                    const uint32_t* target, uint64_t out_cap, uint64_t total, uint64_t hdr[TM_FORWARD_HDR_WORDS],
+                    tm_forward_group* groups, uint64_t group_cap, uint32_t* pub, uint64_t pub_cap) {
+    if (!hdr || !off || (n && !count) || (out_cap && (!to || !target)) || (group_cap && !groups) || (pub_cap && !pub))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (int rc = local_node_unset(e)) return rc;
+    if (e->devs.empty()) return no_device(e, "forward plan");
+    DevState& d = *e->devs[0];
+    return batch_call(e, {&d}, [&]() -> int {
+        for (uint32_t i = 0; i < n; ++i)
+            if (off[i + 1] < off[i]) throw ArgError("delivery offsets not monotone");
+        std::memset(hdr, 0, TM_FORWARD_HDR_WORDS * 8);
+        const uint64_t c = std::min(total, out_cap);   // the live slots: what the planes hold
+        if (n == 0 || c == 0) return TM_OK;
+        if (c >= 0xFFFFFFFEull) throw RangeError("forward: more than 2^32 - 2 delivery slots in one batch");
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        d.rw_drain();
+        // [off][total][count][to][target] and [hdr][groups][pub]; no plan has more groups or entries than slots
+        const uint64_t gc = std::min(group_cap, c), pc = std::min(pub_cap, c);
+        const size_t o_total = (size_t)(n + 1) * 8, o_count = o_total + 8, o_to = o_count + (size_t)n * 4,
+                     o_tg = o_to + (size_t)c * 4;
+        d.w_fin.ensure(o_tg + (size_t)c * 4);
+        d.w_fout.ensure(TM_FORWARD_HDR_WORDS * 8 + (size_t)gc * 16 + (size_t)pc * 4 + 16);
+        uint8_t* in = d.w_fin.as<uint8_t>();
+        uint8_t* out = d.w_fout.as<uint8_t>();
+        HIPCHK(hipMemcpyAsync(in, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_total, &c, 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_count, count, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_to, to, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_tg, target, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        uint64_t* d_hdr = reinterpret_cast<uint64_t*>(out);
+        tm_forward_group* d_groups = reinterpret_cast<tm_forward_group*>(out + TM_FORWARD_HDR_WORDS * 8);
+        uint32_t* d_pub = reinterpret_cast<uint32_t*>(out + TM_FORWARD_HDR_WORDS * 8 + (size_t)gc * 16);
+        e->forward_plan(d, n, reinterpret_cast<const uint32_t*>(in + o_count), reinterpret_cast<const uint64_t*>(in),
+                        reinterpret_cast<const uint32_t*>(in + o_to), reinterpret_cast<const uint32_t*>(in + o_tg), c,
+                        reinterpret_cast<const uint64_t*>(in + o_total), d_hdr, d_groups, gc, d_pub, pc, s);
+        HIPCHK(hipMemcpyAsync(hdr, d_hdr, TM_FORWARD_HDR_WORDS * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t M = hdr[0], G = hdr[1];
+        const uint64_t gn = std::min(G, gc), pn = std::min(M, pc);
+        if (gn) HIPCHK(hipMemcpyAsync(groups, d_groups, (size_t)gn * 16, hipMemcpyDeviceToHost, s));
+        if (pn) HIPCHK(hipMemcpyAsync(pub, d_pub, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+        d.rw_release(s);
+        HIPCHK(hipStreamSynchronize(s));
+        return (M > pub_cap || G > group_cap) ? TM_ENOSPC : TM_OK;
+    }, [] {});
 }
 
 int tm_share_cursors_open(tm_engine* e, uint32_t replica, tm_share_cursors** out) {

@@ -258,6 +258,19 @@ struct ShareView {
     uint32_t              n_sets;    // set indices handed out so far (cursor entries in use)
 };
 
+// ---- forward table (emqx_broker:forward/3, src/emqx_broker.erl:185-186, 209-216) ----
+// The sending half of route/2's {To, Node} clause (forward.hip) tells a remote
+// node's delivery from the local node's and from a $share group's by its
+// target id alone: fwd[target] = 1 for a TM_TARGET_NODE target other than
+// node(), else 0.  One u32 per target id, rebuilt when the targets are ranked.
+// Target ids are never freed, so a deliveries plane of an older epoch always
+// indexes inside the table of the current one.
+struct ForwardView {
+    const uint32_t* fwd;        // n_targets: target id -> forwardable node
+    uint32_t        n_targets;
+    uint32_t        n_filters;  // filter ids are below it (the To key's width)
+};
+
 // ---- hashing (identical on host and device) ---------------------------------
 #if defined(__HIPCC__)
 #define TM_HD __host__ __device__ __forceinline__

@@ -250,6 +250,36 @@ hipError_t launch_share_retry_pick(const ShareView& hv, uint32_t strategy, const
                                    uint32_t n, const uint32_t* rcnt, const uint32_t* rseg, const uint32_t* pub_key,
                                    const uint32_t* failed, const uint64_t* failed_off, uint32_t* pick, hipStream_t st);
 
+// emqx_broker:forward/3's sending half (forward.hip): the remote-node
+// deliveries of a batch regrouped per (target, To), over the same deliveries
+// CSR and slot geometry as launch_dispatch_count.  slots = the deliveries'
+// capacity (at most 2^32 - 2), the live slots are min(*dtotal, slots).
+//   launch_forward_flag      per slot flag (live, node target, not node(); the caller zeroes
+//                            flag[0, slots) first) and pubidx = the slot's topic
+//   launch_scan0(flag, slots, P, P + slots, ...)   P[slots] = M, the forward deliveries
+//   launch_forward_compact   keys / vals[P[slot]] = (To key, slot) of the flagged slots
+//   launch_sort_pairs        stable by To key (bits of ForwardView::n_filters)
+//   launch_forward_retarget  keys[p] = tg[vals[p]]
+//   launch_sort_pairs        stable by target (bits of ForwardView::n_targets - 1)
+//   launch_forward_heads     head / thead[p]: (target, To) / target differs from pair p - 1's
+//   launch_scan0 x 2         H, T (m + 1 u64 each): group index of every pair, G, targets
+//   launch_forward_groups    hdr[4] = {m, G, targets, 0}; groups[g] = {target, To, first,
+//                            count} (16 B records, g < group_cap); pub[p] = pubidx of pair p
+//                            (p < pub_cap)
+hipError_t launch_forward_flag(const ForwardView& fv, uint32_t n, const uint32_t* acount, const uint64_t* aoff,
+                               const uint32_t* tg, uint64_t slots, const uint64_t* dtotal, uint32_t* flag,
+                               uint32_t* pubidx, hipStream_t st);
+hipError_t launch_forward_compact(const ForwardView& fv, const uint32_t* flag, const uint64_t* P, const uint32_t* to,
+                                  uint64_t slots, uint32_t* keys, uint32_t* vals, hipStream_t st);
+hipError_t launch_forward_retarget(uint32_t* keys, const uint32_t* vals, const uint32_t* tg, uint32_t m,
+                                   hipStream_t st);
+hipError_t launch_forward_heads(const uint32_t* keys, const uint32_t* vals, const uint32_t* to, uint32_t m,
+                                uint32_t* head, uint32_t* thead, hipStream_t st);
+hipError_t launch_forward_groups(const uint32_t* keys, const uint32_t* vals, const uint32_t* to,
+                                 const uint32_t* pubidx, const uint32_t* head, const uint64_t* H, const uint64_t* T,
+                                 uint32_t m, uint64_t* hdr, void* groups, uint64_t group_cap, uint32_t* pub,
+                                 uint64_t pub_cap, hipStream_t st);
+
 // A publish batch's results as dense records (pack.hip) over what
 // tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:
 // scan_tmp_elems(n)), deliv[doff[t] + k] = {to, tg, ndisp, pick} of slot

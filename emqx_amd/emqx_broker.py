@@ -13,6 +13,9 @@ expansion, aggre and the subscriber fan-out, dispatch.hip).
     publish_shared_many(Topics, ...)   the same with route/2's $share clause :187-189: the member
                                        emqx_shared_sub:dispatch/3 picks for every {To, Group} delivery
     dispatch_many(Tos)                 dispatch/2 :218-238 as a remote node's forward/3 calls it
+    publish_forward_many(Topics)       publish_many plus route/2's {To, Node} clause :185-186: the
+                                       batch's forward/3 calls :209-216 as one bundle per remote node
+    dispatch_forwarded(Groups, Topics) the receiving node's side of such a bundle: one dispatch_many
 
 A subscriber is a u32 chosen by the caller (the NIF keeps id <-> {SubPid,
 SubId}); groups are byte strings.  The counterpart of emqx_router.py.
@@ -128,6 +131,47 @@ class Broker:
             pairs = [(name_of(int(sto[k]), topic), int(sid[k])) for k in range(a, a + int(scount[t]))]
             res.append(Published(dels, pairs) if pick is None else SharedPublished(dels, pairs, picks))
         return res
+
+    # route/2's {To, Node} clause and forward/3 — :185-186, :209-216
+    def publish_forward_many(self, topics):
+        """publish_many plus the batch's forwards, one bundle per remote node ->
+        ([Published], forwards); forwards = [(node bytes, [(To bytes | None,
+        [publish index, ...]), ...])] ordered as the plan is (tm_forward_plan:
+        target id, then To, then publish index).  To None = each of the named
+        publishes' own topic.  A bundle's second field is what the node's
+        Broker.dispatch_forwarded takes."""
+        topics = list(topics)
+        buf, off = pack(topics)
+        out = self.engine.match_dispatch_batch(buf, off)
+        _hdr, groups, pub = self.engine.forward_plan(out[0], out[1], out[2], out[3])
+        ids = [int(g[1]) for g in groups if int(g[1]) != Engine.TOPIC_ROUTE]
+        names = dict(zip(ids, self.engine.filters_bytes(ids))) if ids else {}
+        forwards = []
+        last = None
+        for node, to, first, count in groups.tolist():
+            if node != last:
+                forwards.append((self.engine.target_bytes(node)[1], []))
+                last = node
+            forwards[-1][1].append((None if to == Engine.TOPIC_ROUTE else names[to],
+                                    [int(x) for x in pub[first:first + count]]))
+        return self._published(topics, out, None), forwards
+
+    def dispatch_forwarded(self, groups, topics):
+        """the receiving end of forward/3 (the RPC replaced by a call): groups =
+        one bundle of publish_forward_many, topics = that batch's topics (a
+        forwarded message carries its own) -> [(publish index, To, Count,
+        [Sub])] in bundle order, from one dispatch_many call"""
+        tos, rows = [], []
+        for to, pubs in groups:
+            if to is None:
+                for p in pubs:
+                    rows.append((p, len(tos)))
+                    tos.append(topics[p])
+            else:
+                rows.extend((p, len(tos)) for p in pubs)
+                tos.append(to)
+        res = self.dispatch_many(tos) if tos else []
+        return [(p, tos[i], res[i][0], list(res[i][1])) for p, i in rows]
 
     # dispatch/2 — :218-238
     def dispatch_many(self, tos):

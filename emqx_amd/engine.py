@@ -577,6 +577,59 @@ class Engine:
             self._check(rc, "tm_dispatch_batch")
             return nd[:n], soff, sid[: int(needed.value)]
 
+    # -- emqx_broker:forward/3, the sending half (forward.hip) ----------------------
+    FORWARD_HDR_WORDS = 4
+
+    def forward_plan(self, counts, offs, to, target, total=None, out_cap=None, group_cap=None, pub_cap=None):
+        """tm_forward_plan over the host planes match_dispatch_batch /
+        match_publish_batch returned -> (hdr u64[4] = {M, G, targets, 0},
+        groups u32[G, 4] = rows {node target, To, first, count}, pub u32[M]):
+        the batch's remote-node deliveries grouped per (target, To).  total:
+        the route total (default len(to)); out_cap: the planes' capacity
+        (default len(to)).  group_cap / pub_cap None: retried at the sizes the
+        header reports; given: one call (TopicMatchError TM_ENOSPC when short,
+        with .hdr)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        to = np.ascontiguousarray(to, dtype=np.uint32)
+        target = np.ascontiguousarray(target, dtype=np.uint32)
+        n = len(offs) - 1
+        total = len(to) if total is None else total
+        out_cap = len(to) if out_cap is None else out_cap
+        gc = 1 << 12 if group_cap is None else group_cap
+        pc = 1 << 14 if pub_cap is None else pub_cap
+        hdr = np.zeros(self.FORWARD_HDR_WORDS, dtype=np.uint64)
+        while True:
+            groups = np.zeros((max(gc, 1), 4), dtype=np.uint32)
+            pub = np.zeros(max(pc, 1), dtype=np.uint32)
+            rc = self.lib.tm_forward_plan(self.h, n, _ptr(counts), _ptr(offs), _ptr(to), _ptr(target), out_cap, total,
+                                          _ptr(hdr), _ptr(groups), gc, _ptr(pub), pc)
+            if rc == L.TM_ENOSPC and (group_cap is None or int(hdr[1]) <= gc) and \
+                    (pub_cap is None or int(hdr[0]) <= pc):
+                gc, pc = max(gc, int(hdr[1])), max(pc, int(hdr[0]))
+                continue
+            if rc == L.TM_ENOSPC:
+                e = L.TopicMatchError(rc, "tm_forward_plan: needs %d groups, %d entries" % (hdr[1], hdr[0]))
+                e.hdr = hdr.copy()
+                raise e
+            self._check(rc, "tm_forward_plan")
+            return hdr, groups[: int(hdr[1])], pub[: int(hdr[0])]
+
+    def forward_plan_device(self, n, d_counts, d_offs, d_to, d_target, out_cap, d_total, d_hdr, d_groups, group_cap,
+                            d_pub, pub_cap, stream=None):
+        """tm_forward_plan_device over device pointers (tensors or ints; None =
+        NULL): the plan of the planes a *_batch_device publish call left"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_forward_plan_device(self.h, n, p(d_counts), p(d_offs), p(d_to), p(d_target), out_cap,
+                                             p(d_total), p(d_hdr), p(d_groups), group_cap, p(d_pub), pub_cap, st)
+        return self._check(rc, "tm_forward_plan_device")
+
     # -- emqx_shared_sub: the $share member table and the pick (share.hip) ---------
     NO_MEMBER = 0xFFFFFFFF            # pick: `false`, or not a $share delivery
     SHARE_KEYED, SHARE_ROUND_ROBIN, SHARE_STICKY = 1, 2, 3

@@ -777,6 +777,57 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
                            tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
                            void* hip_stream);
 
+/* ---- forward/3: a batch's remote-node deliveries, one bundle per node ---------
+ * (emqx_amd/csrc/forward.hip)  The second clause of route/2
+ * (src/emqx_broker.erl:185-186) hands a {To, Node} delivery of another node to
+ * forward/3 (:209-216), which makes one emqx_rpc:call(Node, emqx_broker,
+ * dispatch, [To, Delivery]) per delivery.  Over a batch of publishes one
+ * bundle per node carries the same calls; these two entries regroup the
+ * deliveries CSR of a batch into that shape, as a post-pass over what
+ * tm_match_dispatch_batch[_device] / tm_match_publish_batch[_device] left.
+ *
+ * A FORWARD DELIVERY is a live slot (not a hole of its topic's span, below
+ * out_cap and below the route total) whose target is of kind TM_TARGET_NODE
+ * (an undeclared dest is a node named by its bytes) and is not the target
+ * of tm_set_local_node.  $share groups and node() are never in the plan.
+ * The plan is the batch's forward deliveries as (target id, To, publish index)
+ * sorted by target id, then To (a filter id; TM_ROUTE_TOPIC last), then publish
+ * index (the topic's index in the batch), all ascending:
+ *   pub[M]     the publish indices in that order
+ *   groups[G]  one record per distinct (target, To) in that order: its
+ *              publishes are pub[first .. first + count).  These are the
+ *              {route, Node, To} of :186.  A node's groups are contiguous; the
+ *              caller cuts them where `node` changes.  to == TM_ROUTE_TOPIC:
+ *              each entry's To is that publish's own topic
+ *   hdr[4]     {M, G, distinct targets, 0}
+ * Within a (node, To) pair the publishes keep batch order.  Nothing is written
+ * at or past group_cap records or pub_cap entries, and hdr is exact even when
+ * the plan does not fit, so a second call can be sized from it.
+ *
+ * Device form: device pointers, ordered on hip_stream, on the replica that owns
+ * d_off; it pins the current epoch (run it before a commit frees the filter ids
+ * of the planes).  It reads M back once (one 8 B copy, one host wait) to size
+ * its sorts.  out_cap is the capacity of d_to / d_target: the scans run over
+ * it, so pass what the planes hold, below 2^32 - 2 (TM_ERANGE).  TM_EINVAL: a
+ * null d_hdr, d_off or d_total, a null d_count with n, a null plane or result
+ * array with its capacity, or tm_set_local_node not called yet; TM_EDEVICE on a
+ * host-only engine.  n == 0 or no forward delivery: a zero header. */
+#define TM_FORWARD_HDR_WORDS 4
+typedef struct tm_forward_group { uint32_t node, to, first, count; } tm_forward_group;   /* 16 B */
+int tm_forward_plan_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                           const uint32_t* d_to, const uint32_t* d_target, uint64_t out_cap,
+                           const uint64_t* d_total, uint64_t* d_hdr, tm_forward_group* d_groups,
+                           uint64_t group_cap, uint32_t* d_pub, uint64_t pub_cap, void* hip_stream);
+/* The same over host planes, those tm_match_dispatch_batch /
+ * tm_match_publish_batch returned (total = their *out_needed; the planes hold
+ * min(total, out_cap) slots): uploads them, runs the same passes on the
+ * engine's first replica and copies the plan back.  Synchronous.  TM_ENOSPC
+ * when M > pub_cap or G > group_cap, hdr exact. */
+int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint64_t* off,
+                    const uint32_t* to, const uint32_t* target, uint64_t out_cap, uint64_t total,
+                    uint64_t hdr[TM_FORWARD_HDR_WORDS], tm_forward_group* groups, uint64_t group_cap,
+                    uint32_t* pub, uint64_t pub_cap);
+
 /* ---- publisher contexts: round-robin cursors and sticky entries --------------
  * do_pick_subscriber(Group, Topic, round_robin, _ClientId, Count) keeps its
  * counter in the PUBLISHER's process dictionary, under {shared_sub_round_robin,
