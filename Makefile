@@ -96,3 +96,14 @@ san_batcher: $(LIBOUT)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_batcher_main.o $(BUILD)/san_engine.o $(BUILD)/san_batcher_lib.o $(SAN_BATCHER_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_batcher
 	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_batcher
 .PHONY: san_batcher
+
+# the per-node filters of the host mirror (option "nfilter": relayout with
+# extension slots, churn, id reuse, the option switched) under
+# AddressSanitizer + UBSan on a host-only engine (tools/san_nfilter.cpp); the
+# kernels linked as built and never run.
+san_nfilter: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c tools/san_nfilter.cpp -o $(BUILD)/san_nfilter_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_nfilter_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_nfilter
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_nfilter
+.PHONY: san_nfilter

@@ -398,6 +398,8 @@ constexpr EdgeSlot empty_slot() {
 }
 constexpr EdgeSlot kEmptySlot = empty_slot();
 
+constexpr size_t NF_TAIL = 128;   // bytes past the node arrays a filter-word address may reach (image.h)
+
 struct NodeAux {
     uint32_t parent;      // parent node id (root: NODE_NONE)
     uint32_t word;        // word by which the parent reaches it (id, WORD_PLUS, WORD_HASH)
@@ -1152,7 +1154,7 @@ struct tm_engine {
         e.parent = parent;
         e.word = word;
         e.child = child;
-        e.plus = SLOT_RECORD ? c.plus : child_sum(child);
+        e.plus = SLOT_RECORD ? c.plus : child_sum(child) | node_cls(child) << SLOT_CLS_SHIFT;
 #if TM_SLOT_RECORD
         e.hash_filter = c.hash_filter;
         e.lw = c.lw;
@@ -1164,6 +1166,39 @@ struct tm_engine {
     // the summary a child's edge slot carries (image.h EdgeSlot): its own
     // S(c), so the walk drops a table child whose subtree cannot match
     uint32_t child_sum(uint32_t x) const { return summaries ? aux[x].sum : SUM_ALL; }
+
+    // ---- per-node filters in the node's own line (option "nfilter", image.h):
+    // relayout gives a WIDE node with >= NF_MIN literal children an id that
+    // is a multiple of NF_GROUP and the ids after it as extension slots,
+    // whose inner halves hold its filter words.  Extension slots (and the
+    // few ids left over by the alignment) are not nodes: aux[].parent is
+    // NODE_NONE as for a free id, but they are never in free_nodes, never
+    // counted in live_nodes and never handed out; they go away at the next
+    // relayout.  A literal child added to a filtered node sets its bits, a
+    // removed one leaves them (a superset: false positives only); a node
+    // created since the last relayout, or on a reused id, has no filter.
+    // The class rides in the references to the node: its parent's '+' field
+    // and its edge slot.
+    int nfilter = 1;                  // option "nfilter" (1: on; changing it relayouts)
+    enum : uint8_t { NK_PLAIN = 0, NK_HEAD = 1, NK_EXT = 2 };
+    std::vector<uint8_t> nkind;       // per id since the last relayout (ids created later: NK_PLAIN)
+    uint32_t node_cls(uint32_t x) const { return x < nkind.size() && nkind[x] == NK_HEAD ? 1u : 0u; }
+    bool is_ext(uint32_t x) const { return x < nkind.size() && nkind[x] == NK_EXT; }
+    static uint32_t& nf_field(Node& x, uint32_t k) { return (&x.plus)[k]; }   // plus, hash_filter, lw, lc
+    void nf_add(uint32_t v, uint32_t w) {
+        if (!node_cls(v) || w >= WORD_MAX) return;
+        const uint32_t h = nf_hash(w), k = nf_slot(h), b = nf_bits(h);
+        const uint32_t x = v + 1 + k / 4;
+        uint32_t& f = nf_field(nodes[x], k % 4);
+        if ((f & b) != b) {
+            f |= b;
+            t_nodes.cur.mark(x);
+        }
+    }
+    bool nf_has(uint32_t v, uint32_t w) const {
+        const uint32_t h = nf_hash(w), k = nf_slot(h), b = nf_bits(h);
+        return (nf_field(const_cast<Node&>(nodes[v + 1 + k / 4]), k % 4) & b) == b;
+    }
     void refresh_slot_sum(uint32_t x) {
         if (SLOT_RECORD) return;   // such slots carry the child's record instead
         const uint32_t p = aux[x].parent, w = aux[x].word;
@@ -1172,7 +1207,7 @@ struct tm_engine {
         const size_t s = edge_find_slot(p, w);
         if (s == SIZE_MAX) return;
         EdgeSlot& e = tab(p).slots[s];
-        const uint32_t v = child_sum(x);
+        const uint32_t v = child_sum(x) | node_cls(x) << SLOT_CLS_SHIFT;
         if (e.plus != v) {
             e.plus = v;
             tab(p).t.cur.mark(s);
@@ -1236,6 +1271,7 @@ struct tm_engine {
         }
         nodes[id] = empty_node();
         aux[id] = NodeAux{parent, word, 0, 0, (uint16_t)SUM_NONE, (uint16_t)SUM_NONE};
+        if (id < nkind.size()) nkind[id] = NK_PLAIN;   // (a reused id: no filter until the next relayout)
         if (word < WORD_MAX) heat_bump(word, +1);
         t_nodes.cur.mark(id);
         ++live_nodes;
@@ -1286,9 +1322,11 @@ struct tm_engine {
             y.lw = 0;
             y.lc = 0;
             bloom_add(y, w0);
+            nf_add(v, w0);
         }
         edge_insert(v, w, c);
         bloom_add(nodes[v], w);
+        nf_add(v, w);
     }
     void lit_remove(uint32_t v, uint32_t w) {
         Node& x = nodes[v];
@@ -1340,6 +1378,7 @@ struct tm_engine {
         if (w < WORD_MAX) heat_bump(w, -1);
         nodes[c] = empty_node();
         aux[c] = NodeAux{NODE_NONE, 0, 0, 0, (uint16_t)SUM_NONE, (uint16_t)SUM_NONE};
+        if (c < nkind.size()) nkind[c] = NK_PLAIN;   // (a filtered node's extension slots stay dead ids)
         t_nodes.cur.mark(c);
         free_nodes.push_back(c);
         --live_nodes;
@@ -2438,19 +2477,68 @@ struct tm_engine {
                 pa.sum = (uint16_t)sum_union(pa.sum, sum_hash0(SUM_NONE));
         }
         if (layout_order & 4) heat_sort(order, newid, new_hot_limit);
+        // ids with holes (option "nfilter", image.h): `order` is final; a
+        // filtered node takes the next id that is a multiple of NF_GROUP and
+        // the ids after it as its extension slots.  It waits for that id
+        // while the nodes after it in the order fill the ids up to it, so
+        // only the end of the hot range and of the array leave ids unused.
+        std::vector<uint8_t> kind;
+        uint32_t next_id = 0, padded_hot_limit = 0;
+        {
+            auto filtered = [&](uint32_t v) {
+                return nfilter && !SLOT_RECORD && (nodes[v].plus & WIDE) && aux[v].lit_count >= NF_MIN;
+            };
+            auto set_kind = [&](uint32_t id, uint8_t k) {
+                if (kind.size() <= id) kind.resize((size_t)id + 1, NK_PLAIN);
+                kind[id] = k;
+            };
+            std::vector<uint32_t> waiting;
+            size_t head = 0;
+            auto place_head = [&](uint32_t v) {
+                newid[v] = next_id;
+                set_kind(next_id, NK_HEAD);
+                for (uint32_t k = 1; k < NF_GROUP; ++k) set_kind(next_id + k, NK_EXT);
+                next_id += NF_GROUP;
+            };
+            auto flush = [&]() {
+                while (head < waiting.size()) {
+                    while (next_id % NF_GROUP) set_kind(next_id++, NK_EXT);
+                    place_head(waiting[head++]);
+                }
+            };
+            for (size_t i = 0; i < order.size(); ++i) {
+                if (i == new_hot_limit) {   // the hot range ends: nothing waits across it
+                    flush();
+                    padded_hot_limit = next_id;
+                }
+                const uint32_t v = order[i];
+                if (filtered(v)) waiting.push_back(v);
+                else newid[v] = next_id++;
+                while (next_id % NF_GROUP == 0 && head < waiting.size()) place_head(waiting[head++]);
+            }
+            flush();
+            if (new_hot_limit >= order.size()) padded_hot_limit = next_id;
+            if ((uint64_t)next_id >= NODE_NONE) throw RangeError("trie exceeds 2^29-1 node ids");
+            kind.resize(next_id, NK_PLAIN);
+        }
+        new_hot_limit = padded_hot_limit;
         auto remap = [&](uint32_t id) { return id == NODE_NONE ? NODE_NONE : newid[id]; };
-        std::vector<Node> nn(order.size());
-        std::vector<NodeAux> na(order.size());
+        Node dead = empty_node();   // extension slots: no filter bits yet, nothing a stray visit could follow
+        dead.plus = dead.hash_filter = dead.lw = dead.lc = 0;
+        std::vector<Node> nn(next_id, dead);
+        std::vector<NodeAux> na(next_id, NodeAux{NODE_NONE, 0, 0, 0, (uint16_t)SUM_NONE, (uint16_t)SUM_NONE});
         for (size_t i = 0; i < order.size(); ++i) {
             Node x = nodes[order[i]];
-            x.plus = (x.plus & WIDE) | remap(x.plus & NODE_MASK);
+            const uint32_t pc = remap(x.plus & NODE_MASK);
+            x.plus = (x.plus & WIDE) | pc;
+            if (pc != NODE_NONE && kind[pc] == NK_HEAD) x.plus |= 1u << CLS_SHIFT;
             x.hash = remap(x.hash);
             if (x.plus & WIDE) x.lw = x.lc = 0;   // Bloom rebuilt exactly below
             else if (x.lw != WORD_NONE) x.lc = remap(x.lc);
-            nn[i] = x;
+            nn[newid[order[i]]] = x;
             NodeAux a = aux[order[i]];
             a.parent = remap(a.parent);
-            na[i] = a;
+            na[newid[order[i]]] = a;
         }
         // edge tables with the new ids: parents below the new hot limit in `hot`
         std::vector<EdgeSlot> old;
@@ -2472,6 +2560,9 @@ struct tm_engine {
             if (e.word != WORD_HASH) bloom_add(nn[newid[e.parent]], e.word);
         nodes.swap(nn);
         aux.swap(na);   // before the edges are placed: slot_for reads the children's new summaries
+        nkind.swap(kind);   // likewise: slot_for puts each child's class in its slot
+        for (const EdgeSlot& e : old)   // the filters, exactly, from the literal edges
+            if (e.word != WORD_HASH) nf_add(newid[e.parent], e.word);
         hot_limit = new_hot_limit;
         size_t nhot = 0;
         for (const EdgeSlot& e : old) nhot += newid[e.parent] < hot_limit;
@@ -2487,7 +2578,8 @@ struct tm_engine {
         }
         for (FilterRec& f : filters)
             if (f.node != NODE_NONE) f.node = newid[f.node];
-        for (uint32_t v = 0; v < nodes.size(); ++v) nodes[v].hash_filter = hf_value(v);
+        for (uint32_t v = 0; v < nodes.size(); ++v)
+            if (!is_ext(v)) nodes[v].hash_filter = hf_value(v);   // (an extension slot's field holds filter bits)
         if (SLOT_RECORD)   // the slots carry their children's records: those of the final hash_filter values
             for (EdgeTable* t : {&cold, &hot})
                 for (EdgeSlot& e : t->slots)
@@ -2552,6 +2644,7 @@ struct tm_engine {
         im.fshape = shape_keys ? g.d_fshape.as<const uint64_t>() : nullptr;
         im.word_heat = g.d_wheat.as<const uint8_t>();
         im.n_words = g.heat_words;
+        im.root_cls = node_cls(ROOT);
         return im;
     }
 
@@ -2597,7 +2690,8 @@ struct tm_engine {
     void upload_table(DevState& d, Image& g, DevBuf& buf, const std::vector<T>& host, const Dirty& dirty,
                       const Dirty& prev) {
         static_assert(sizeof(T) % 4 == 0, "tables are scattered in 32-bit words");
-        const bool re = buf.ensure_async(std::max<size_t>(host.size(), 1) * sizeof(T), d.ustream);
+        // (NF_TAIL: the node table's tail padding, see split_image)
+        const bool re = buf.ensure_async(std::max<size_t>(host.size(), 1) * sizeof(T) + NF_TAIL, d.ustream);
         // g holds commit g.epoch; this one makes epoch + 1
         const bool two = g.written && g.epoch + 1 == epoch;        // g missed exactly the previous commit
         const bool stale = !g.written || g.epoch + 1 < epoch;      // missed more (double_buffer switched on)
@@ -2737,7 +2831,9 @@ struct tm_engine {
 
     // option "split": de-interleave the uploaded records into inner / leaf arrays
     void split_image(DevState& d, Image& g) {
-        g.d_inner.ensure_async(nodes.size() * 16, d.ustream);
+        // (tail padding: a filter word's address, up to three ids past its node, is in bounds whatever
+        // class bits a reference carries)
+        g.d_inner.ensure_async(nodes.size() * 16 + NF_TAIL, d.ustream);
         g.d_leaf.ensure_async(nodes.size() * 16, d.ustream);
         HIPCHK(launch_split_nodes(g.d_nodes.p, nodes.size(), g.d_inner.p, g.d_leaf.p, d.ustream));
         g.split_stale = false;
@@ -5448,6 +5544,108 @@ int tm_match_small_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* 
 // range-local word-hash order, 2 the tail order, 0 arrival order ...)
 extern "C" int tm_debug_last_order(tm_engine* e) { return e ? e->last_order.load() : TM_EINVAL; }
 
+// diagnostics (not part of include/topicmatch.h): host-side consistency of
+// the per-node filters (option "nfilter", image.h): every literal child of a
+// filtered node passes its filter (no false negative); every reference the
+// walk takes a class from (edge slot, '+' field) carries its target's class;
+// a filtered node's id is a multiple of NF_GROUP and its extension slots
+// exist; no extension slot is live, free-listed or referenced; live_nodes
+// counts the nodes alone.  TM_OK, or TM_EINVAL naming the first defect
+// (stderr).
+extern "C" int tm_debug_check_filters(tm_engine* e) {
+    if (!e) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        auto fail = [](const std::string& m) {
+            std::fprintf(stderr, "tm_debug_check_filters: %s\n", m.c_str());
+            return TM_EINVAL;
+        };
+        const size_t N = e->nodes.size();
+        if (e->nkind.size() > N) return fail("kinds past the node array");
+        auto ref_ok = [&](uint32_t id) { return id < N && !e->is_ext(id) && (id == ROOT || e->aux[id].parent != NODE_NONE); };
+        size_t live = 0;
+        for (size_t v = 0; v < N; ++v) {
+            const bool is_node = v == ROOT || e->aux[v].parent != NODE_NONE;
+            if (e->is_ext((uint32_t)v)) {
+                if (is_node) return fail("extension slot " + std::to_string(v) + " is a live node");
+                continue;
+            }
+            if (!is_node) {
+                if (e->node_cls((uint32_t)v)) return fail("free id " + std::to_string(v) + " keeps a filter class");
+                continue;
+            }
+            ++live;
+            const Node& x = e->nodes[v];
+            if (e->node_cls((uint32_t)v)) {
+                if (v % NF_GROUP) return fail("filtered node " + std::to_string(v) + ": id not a multiple of the group");
+                for (uint32_t k = 1; k < NF_GROUP; ++k)
+                    if (v + k >= N || !e->is_ext((uint32_t)(v + k)))
+                        return fail("filtered node " + std::to_string(v) + ": extension slot missing");
+            }
+            const uint32_t pc = x.plus & NODE_MASK;
+            if (pc != NODE_NONE) {
+                if (!ref_ok(pc)) return fail("node " + std::to_string(v) + ": '+' child is no node");
+                if (((x.plus & CLS_MASK) >> CLS_SHIFT) != e->node_cls(pc))
+                    return fail("node " + std::to_string(v) + ": '+' child class bits");
+            } else if (x.plus & CLS_MASK) {
+                return fail("node " + std::to_string(v) + ": class bits without a '+' child");
+            }
+            if (x.hash != NODE_NONE && !ref_ok(x.hash)) return fail("node " + std::to_string(v) + ": '#' child is no node");
+            if (!(x.plus & WIDE) && x.lw != WORD_NONE && !ref_ok(x.lc))
+                return fail("node " + std::to_string(v) + ": inline child is no node");
+            if (e->aux[v].parent != NODE_NONE && !ref_ok(e->aux[v].parent))
+                return fail("node " + std::to_string(v) + ": parent is no node");
+        }
+        if (live != e->live_nodes) return fail("live_nodes " + std::to_string(e->live_nodes) + " != nodes " + std::to_string(live));
+        for (uint32_t f : e->free_nodes)
+            if (f >= N || e->is_ext(f)) return fail("extension slot " + std::to_string(f) + " in the free list");
+        for (const FilterRec& f : e->filters)
+            if (f.node != NODE_NONE && !ref_ok(f.node)) return fail("a filter ends at id " + std::to_string(f.node) + ": no node");
+        for (const auto* t : {&e->cold, &e->hot})
+            for (const EdgeSlot& s : t->slots) {
+                if (s.parent == EDGE_EMPTY) continue;
+                if (!ref_ok(s.parent) || !ref_ok(s.child))
+                    return fail("slot (" + std::to_string(s.parent) + ", " + std::to_string(s.child) + "): not nodes");
+                if (!SLOT_RECORD && ((s.plus >> SLOT_CLS_SHIFT) & 3u) != e->node_cls(s.child))
+                    return fail("slot of child " + std::to_string(s.child) + ": class bits");
+                if (s.word == WORD_HASH || !e->node_cls(s.parent)) continue;
+                if (!e->nf_has(s.parent, s.word))
+                    return fail("node " + std::to_string(s.parent) + ": word " + std::to_string(s.word) +
+                                " missing from its filter");
+            }
+        if (!e->nfilter && !e->force_relayout)   // (switched off: the filtered nodes go at the next relayout)
+            for (size_t v = 0; v < e->nkind.size(); ++v)
+                if (e->nkind[v] != tm_engine::NK_PLAIN && (v == ROOT || e->aux[v].parent != NODE_NONE))
+                    return fail("nfilter off, yet id " + std::to_string(v) + " is filtered");
+        return TM_OK;
+    });
+}
+
+// diagnostics: does word `w` (bytes) pass the in-node Bloom / the Bloom and
+// the filter of the trie node named `topic` (as tm_lookup; empty: the root)?  out[0] = the node's literal
+// children, out[1] = 1 when the node is filtered, out[2] = passes the Bloom,
+// out[3] = passes Bloom and filter.  TM_ENOENT: no such node or word.
+extern "C" int tm_debug_filter_pass(tm_engine* e, const uint8_t* topic, uint32_t tlen, const uint8_t* word,
+                                    uint32_t wlen, uint32_t* out) {
+    if (!e || !out || (tlen && !topic) || (wlen && !word)) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        uint32_t v = ROOT;   // (an empty `topic`: the root)
+        if (tlen) {
+            if (!e->split_words(topic, tlen, false)) return TM_ENOENT;
+            v = e->walk(e->tmp_words);
+            if (v == NODE_NONE) return TM_ENOENT;
+        }
+        const uint32_t w = e->word_id(word, wlen, false);
+        if (w >= WORD_MAX) return TM_ENOENT;
+        const Node& x = e->nodes[v];
+        out[0] = e->aux[v].lit_count;
+        out[1] = e->node_cls(v);
+        const uint64_t b = word_bloom(w), mask = ((uint64_t)x.lc << 32) | x.lw;
+        out[2] = (x.plus & WIDE) && (mask & b) == b;
+        out[3] = out[2] && (!e->node_cls(v) || e->nf_has(v, w));
+        return TM_OK;
+    });
+}
+
 // diagnostics (not part of include/topicmatch.h): the phases of the last
 // per-lane queue walk on replica 0, per XCD x (kernels.h QWS_CLOCK):
 // out[4x..4x+3] = ms from the walk's first wave start to XCD x's first wave
@@ -5775,6 +5973,15 @@ int tm_set_option(tm_engine* e, const char* name, int64_t value) {
         if (!std::strcmp(name, "light_tail")) {   // per mille of each range walked last by presort 6
             if (value < 0 || value > 500) return TM_EINVAL;
             e->light_tail = (uint32_t)value;
+            return TM_OK;
+        }
+        if (!std::strcmp(name, "nfilter")) {   // per-node filters in the node's own line (image.h NF_MIN)
+            if (value < 0 || value > 1) return TM_EINVAL;
+            if ((int)value != e->nfilter) {
+                e->nfilter = (int)value;
+                e->force_relayout = true;   // filtered nodes and their extension slots are laid out by relayout
+                e->dev_dirty = true;
+            }
             return TM_OK;
         }
         if (!std::strcmp(name, "relayout")) {   // 1: relayout at the next commit (layout A/Bs)

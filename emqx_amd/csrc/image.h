@@ -131,6 +131,7 @@ struct ImageView {
     const uint64_t* fshape;            // filter id -> order key (filter_shape), or null (option "shape_keys" off)
     const uint8_t*  word_heat;         // word id -> floor(log2(1 + nodes it labels)) (presort mode 2)
     uint32_t        n_words;
+    uint32_t        root_cls;          // option "nfilter": the root's filter class (0: none)
 };
 
 
@@ -365,6 +366,38 @@ TM_HD uint64_t word_bloom(uint32_t w) {
     const uint32_t h = w * 0x9E3779B1u;
     return (1ull << (h >> 26)) | (1ull << ((h >> 20) & 63u));
 }
+
+// Per-node filters inside the node's own cache line (option "nfilter").  A
+// WIDE node's 64-bit Bloom passes nearly every word once it has more than
+// ~16 children, and each such pass for a word that is not a child is an
+// edge-table probe of a random cold line: the largest class of the walk's L2
+// misses.  A WIDE node with >= NF_MIN literal children at relayout gets an
+// id that is a multiple of 4, and the three ids after it are its extension
+// slots: not nodes, their inner halves {plus, hash_filter, lw, lc} hold 12
+// filter words of 32 bits (384 bits).  With the split half arrays
+// (node_shift 4) the four inner halves are one 64 B line, so the filter word
+// is in the line the visit loads anyway and can never cost a fabric read of
+// its own.  A child word sets 2 bits of one of the 12 words.  The class (1:
+// the node has the extension slots) rides in every reference the walk
+// follows to the node -- bits 29-30 of the parent's '+' field, bits 16-17 of
+// the edge slot's summary word, bits 29-30 of an unkeyed walk's path entry
+// and cursor, ImageView::root_cls -- so the walk issues the filter load
+// beside the node's own half (no extra dependent round), and an absent word
+// that the Bloom lets through costs no probe.  Bits are only set between
+// relayouts (a superset: false positives only), which rebuild them exactly.
+// A node reached through an inline literal edge (lc) is visited without its
+// filter.
+constexpr uint32_t NF_MIN = 16;                 // literal children of a filtered node, at least
+constexpr uint32_t NF_WORDS = 12;               // filter words per node (three extension slots)
+constexpr uint32_t NF_GROUP = 4;                // ids per filtered node (its id is a multiple)
+constexpr uint32_t CLS_SHIFT = 29;              // class in node references (plus field, path entries)
+constexpr uint32_t CLS_MASK = 3u << CLS_SHIFT;
+constexpr uint32_t SLOT_CLS_SHIFT = 16;         // class in EdgeSlot::plus (above the 15-bit summary)
+// word w's filter word k (0..11) of node v lives in field k % 4 of the inner
+// half of id v + 1 + k / 4; its two bits of that word
+TM_HD uint32_t nf_hash(uint32_t w) { return w * 0x85EBCA77u; }
+TM_HD uint32_t nf_slot(uint32_t h) { return (uint32_t)(((uint64_t)h * NF_WORDS) >> 32); }
+TM_HD uint32_t nf_bits(uint32_t h) { return (1u << ((h >> 22) & 31u)) | (1u << ((h >> 17) & 31u)); }
 
 // home slot of key (parent, word): a 32-bit mix (three 32-bit multiplies)
 // for tables of up to 2^32 slots, the 64-bit one beyond

@@ -1208,6 +1208,13 @@ int  tm_rewrite_match_batch_device(tm_rewrite* r, const uint8_t* d_topics, const
  *   "block_load" blocks kept at load <= 1/value (2..16, default 4)
  *   "block_gc" garbage block slots before a compaction (default 2^20)
  *   "relayout" 1 = relayout the image at the next commit
+ *   "nfilter"  1 = a node with 16 or more literal children at relayout gets
+ *              a 384-bit filter of its children's words in the three node
+ *              slots after it (its id is a multiple of 4: with split halves
+ *              the node's own 64 B line), and the per-lane walk skips the
+ *              edge-table probe of a word the filter rejects (default);
+ *              0 = no filtered nodes, dense ids; changing it forces a
+ *              relayout.  Results are the same either way.
  *   "hot_levels" depths laid out level by level first at relayout (0..16,
  *              default 4; 0 = DFS preorder throughout); forces a relayout
  *   "presort"  1 = walk each batch in the order of a key of its first words

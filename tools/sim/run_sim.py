@@ -26,7 +26,8 @@ from emqx_amd import Engine  # noqa: E402
 from emqx_amd import workload as W  # noqa: E402
 
 KINDS = ["inner", "leaf", "cold", "hot", "pair"]
-MODES = {"cur": 0, "slotrec": 1, "pair": 2, "spec": 4, "blocks": 8, "fix": 64, "nofp": 128, "gf": 256, "gfptr": 512}
+MODES = {"cur": 0, "slotrec": 1, "pair": 2, "spec": 4, "blocks": 8, "fix": 64, "nofp": 128, "gf": 256, "gfptr": 512,
+         "nf": 1024, "nfs": 2048}
 
 
 class View(ctypes.Structure):
@@ -40,7 +41,7 @@ class SimOut(ctypes.Structure):
                 ("topics", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("matches", ctypes.c_uint64),
                 ("rounds", ctypes.c_uint64), ("probes_ok", ctypes.c_uint64), ("probes_fail", ctypes.c_uint64),
                 ("table_visits", ctypes.c_uint64), ("plus_now", ctypes.c_uint64), ("plus_pop", ctypes.c_uint64),
-                ("lit_inline", ctypes.c_uint64), ("reach_req", ctypes.c_uint64 * 5), ("reach_l2m", ctypes.c_uint64 * 5),
+                ("lit_inline", ctypes.c_uint64), ("probes_saved", ctypes.c_uint64), ("reach_req", ctypes.c_uint64 * 5), ("reach_l2m", ctypes.c_uint64 * 5),
                 ("wave_time", ctypes.c_double), ("wave_rounds", ctypes.c_double),
                 ("waves", ctypes.c_uint64)]
 
@@ -90,6 +91,7 @@ def report(name, o, extra=None):
     d["l2_hit"] = round(1 - sum(o.l2m) / max(1, sum(o.l1m)), 3)
     d["probes_ok"] = round(o.probes_ok / t, 2)
     d["probes_fail"] = round(o.probes_fail / t, 2)
+    d["probes_saved"] = round(o.probes_saved / t, 2)
     d["table_visits"] = round(o.table_visits / t, 2)
     d["plus_now"] = round(o.plus_now / t, 2)
     d["plus_pop"] = round(o.plus_pop / t, 2)
@@ -176,6 +178,10 @@ def main():
                 occ = int(part[3:])
             elif part.startswith("gfmin"):   # gf: least literal children of a filtered node
                 mode |= int(part[5:]) << 16
+            elif part.startswith("nfmin"):   # nfs: least literal children of a filtered node
+                mode |= int(part[5:]) << 16
+            elif part in ("u64", "k3", "cls2"):   # nfs: u64 blocks, 3 bits per word, the 256 B class from 128 children
+                mode |= {"u64": 1, "k3": 2, "cls2": 4}[part] << 24
             elif part.startswith("gfbits"):   # gf: log2 words of the global filter (0: sized to ~8 % density)
                 mode |= int(part[6:]) << 24
             elif part.startswith("div"):   # per-node block load: size >= div x edges

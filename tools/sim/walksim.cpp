@@ -97,6 +97,14 @@ enum Mode : int {
                      // array at a hash of the node id, sized by a 2-bit class the reference to the node
                      // carries, so the filter word is loaded beside the node's half (same round); an
                      // absent word that passes the in-node Bloom but not the region costs no probe    // upper bound of a perfect per-node filter: a Bloom pass for an absent word costs no probe
+    M_NF = 1024,     // the in-line filters of the image itself (option "nfilter", image.h): a filtered node's
+                     // filter word is in the inner half of one of the three ids after it (with the split halves the
+                     // node's own 64 B line), loaded in the node's round whenever the reference carried the class
+    M_NFS = 2048,    // in-line filters synthesised over an image without them, to choose their parameters: least
+                     // children (mode bits 16-23), u64 blocks (bit 24), 3 bits per word (bit 25), a second class
+                     // for nodes with >= 128 children (bit 26: a 256 B group, 60 words, the filter word in one of
+                     // the three lines after the node's).  Class 1's filter load is modelled at the node's own
+                     // address (same line by construction; the ids the extension slots take are not modelled)
     M_FIX = 64,      // a fixed 64 B block per node id (no pointer: address = v * 64): up to 8 literal children
                      // as 8 B {word, child} in 4 quads, home quad by word hash, quads probed in order (one
                      // round each); nodes with more children: the shared table (with M_BLOCKS: their own
@@ -233,15 +241,87 @@ struct GFilt {
     }
 };
 
+// M_NFS: synthetic in-line filters (built from the shared edge tables)
+struct NFilt {
+    uint32_t min_children = 16;
+    bool u64 = false, three = false, cls2 = false;
+    std::vector<uint8_t> cls;        // per node: 0, 1 (12 words) or 2 (60 words)
+    std::vector<uint32_t> off;       // per filtered node: first word in `bits`
+    std::vector<uint32_t> bits;
+    static uint32_t nwords(uint32_t c) { return c == 2 ? 60u : 12u; }
+    // word w in a filter of nw u32 words: the first u32 of its block and the block's bit mask
+    void place(uint32_t w, uint32_t nw, uint32_t& word, uint64_t& mask) const {
+        const uint32_t h = w * 0x85EBCA77u, g = w * 0xC2B2AE35u;
+        if (u64) {
+            word = 2 * (uint32_t)(((uint64_t)h * (nw / 2)) >> 32);
+            mask = (1ull << (g >> 26)) | (1ull << ((g >> 20) & 63u));
+            if (three) mask |= 1ull << ((g >> 14) & 63u);
+        } else {
+            word = (uint32_t)(((uint64_t)h * nw) >> 32);
+            mask = (1ull << (g >> 27)) | (1ull << ((g >> 22) & 31u));
+            if (three) mask |= 1ull << ((g >> 17) & 31u);
+        }
+    }
+    uint64_t get(uint32_t node, uint32_t word) const {
+        const uint32_t* b = &bits[off[node] + word];
+        return u64 ? ((uint64_t)b[1] << 32) | b[0] : b[0];
+    }
+    void build(const View& v, uint32_t mn, uint32_t flags) {
+        min_children = mn;
+        u64 = flags & 1;
+        three = flags & 2;
+        cls2 = flags & 4;
+        const uint64_t n = v.n_nodes;
+        std::vector<uint32_t> cnt(n, 0);
+        auto each = [&](auto f) {
+            for (const EdgeSlot* t : {v.cold, v.hot}) {
+                const uint64_t ns = t == v.cold ? v.cold_slots : v.hot_slots;
+                for (uint64_t s = 0; s < ns; ++s)
+                    if (t[s].parent != EDGE_EMPTY && t[s].word != WORD_HASH) f(t[s]);
+            }
+        };
+        each([&](const EdgeSlot& e) { ++cnt[e.parent]; });
+        cls.assign(n, 0);
+        off.assign(n, 0);
+        uint32_t cur = 0;
+        for (uint64_t x = 0; x < n; ++x) {
+            if (cnt[x] < mn) continue;
+            cls[x] = cls2 && cnt[x] >= 128 ? 2 : 1;
+            off[x] = cur;
+            cur += nwords(cls[x]);
+        }
+        bits.assign(cur + 2, 0);
+        each([&](const EdgeSlot& e) {
+            if (!cls[e.parent]) return;
+            uint32_t word;
+            uint64_t mask;
+            place(e.word, nwords(cls[e.parent]), word, mask);
+            bits[off[e.parent] + word] |= (uint32_t)mask;
+            if (u64) bits[off[e.parent] + word + 1] |= (uint32_t)(mask >> 32);
+        });
+    }
+};
+
 struct Walker {
     const View& v;
     const GFilt* gf = nullptr;
+    const NFilt* nf = nullptr;
+    mutable uint32_t cur_cls = 0;      // M_NF: the class the reference to the node being visited carried
+    mutable uint8_t cur_reach = 0;     // how it was reached (a node reached through an inline edge takes no filter)
     int mode = 0;
     const Blocks* blk = nullptr;
     mutable uint64_t probes_ok = 0, probes_fail = 0, table_visits = 0, plus_now = 0, plus_pop = 0, lit_inline = 0;
     mutable uint64_t wide_hist[48] = {0};   // WIDE lookups by log2(children): lookups, bloom passes, hits
     explicit Walker(const View& vw, int m) : v(vw), mode(m) {}
 
+    mutable uint64_t probes_saved = 0;   // in-line filters: Bloom passes the filter stopped
+    void place_nfs(uint32_t node, uint32_t w, uint32_t& word, uint64_t& fm) const {
+        nf->place(w, NFilt::nwords(nf->cls[node]), word, fm);
+    }
+    // the root's class (ImageView::root_cls): it is filtered iff id 1 is one of its extension slots
+    uint32_t root_cls() const {
+        return (mode & M_NF) && v.n_nodes > 1 && aux(1)[0] == NODE_NONE && aux(ROOT)[3] >= NF_MIN ? 1u : 0u;
+    }
     const uint32_t* aux(uint32_t id) const {
         return reinterpret_cast<const uint32_t*>(v.aux + (uint64_t)id * v.aux_stride);
     }
@@ -353,9 +433,28 @@ struct Walker {
                 if (h.child != NODE_NONE) ++wide_hist[32 + bk];
                 return h;
             }
+            // in-line filters: the load is issued with the node's half (round 0), whatever the Bloom says
+            bool nf_ok = true;
+            if ((mode & M_NF) && cur_cls) {
+                const uint32_t h = nf_hash(w), k = nf_slot(h), fb = nf_bits(h);
+                const uint32_t id = node + 1 + k / 4;
+                acc.push_back(Acc{id, K_INNER, 0, cur_reach});
+                nf_ok = ((&v.nodes[id].plus)[k % 4] & fb) == fb;
+            } else if ((mode & M_NFS) && nf->cls[node] && cur_reach != R_LIT_INLINE) {
+                uint32_t word;
+                uint64_t fm;
+                place_nfs(node, w, word, fm);
+                if (nf->cls[node] == 2) acc.push_back(Acc{node * 4 + 1 + word / 16, K_PAIR, 0});   // a neighbouring line
+                else acc.push_back(Acc{node, K_INNER, 0, cur_reach});
+                nf_ok = (nf->get(node, word) & fm) == fm;
+            }
             const uint64_t b = word_bloom(w);
             const uint64_t mask = ((uint64_t)lc << 32) | lw;
             if ((mask & b) != b) return Hit{NODE_NONE, 0, false};
+            if (!nf_ok) {
+                ++probes_saved;
+                return Hit{NODE_NONE, 0, false};
+            }
             if (gf && gf->cls[node] && w < WORD_MAX) {   // the filter word came with the node's half (round 0)
                 const uint64_t i = gf->base(node) + GFilt::wpos(w, gf->rwords(node));
                 if (gf->packed) {   // after the node's half: a round of its own
@@ -401,16 +500,21 @@ struct Walker {
               uint64_t& matches) const {
         uint32_t path[64];
         uint64_t pend = 0;
-        uint32_t cv, cr;
+        uint32_t cv, cr, ccls = 0;   // ccls: the class the reference to cv carried (kernels.hip Cursor::v bits 29-30)
         if (!dollar) {
             cv = ROOT;
             cr = 0;
+            ccls = root_cls();
         } else {
             steps.push_back((uint32_t)acc.size());
             acc.push_back(Acc{ROOT, K_INNER, 0});
             uint32_t rd = 1;
             const Node& q = v.nodes[ROOT];
-            cv = lit(ROOT, q.plus, q.lw, q.lc, W[0], acc, rd).child;
+            cur_cls = 0;   // walk_begin consults no filter
+            cur_reach = R_ROOT;
+            const Hit g0 = lit(ROOT, q.plus, q.lw, q.lc, W[0], acc, rd);
+            cv = g0.child;
+            ccls = (q.plus & WIDE) ? (g0.plus >> SLOT_CLS_SHIFT) & 3u : 0u;
             cr = 1;
             if (cv == NODE_NONE) return;
         }
@@ -450,14 +554,17 @@ struct Walker {
                     plus_ok = sum_useful(hf & SUM_ALL, k);
                     lit_ok = w < WORD_MAX ? sum_useful((hf >> 15) & SUM_ALL, k) : w == WORD_PLUS ? plus_ok : true;
                 }
+                cur_cls = ccls;
+                cur_reach = reach;
                 Hit g = lit_ok ? lit(node, x.plus, x.lw, x.lc, w, acc, rd) : Hit{NODE_NONE, 0, false};
                 if (g.child != NODE_NONE && !(mode & M_SLOTREC) && !sum_useful(g.plus & SUM_ALL, n - r - 1))
                     g.child = NODE_NONE;
                 const uint32_t pc = plus_ok ? (x.plus & NODE_MASK) : NODE_NONE;
                 if (g.child != NODE_NONE) {
-                    path[r] = pc;
+                    path[r] = pc | (pc != NODE_NONE ? (x.plus & CLS_MASK) : 0u);
                     pend = pc != NODE_NONE ? (pend | (1ull << r)) : (pend & ~(1ull << r));
                     cv = g.child;
+                    ccls = (x.plus & WIDE) ? (g.plus >> SLOT_CLS_SHIFT) & 3u : 0u;
                     cr = r + 1;
                     have = g.delivered;
                     reach = (x.plus & WIDE) ? R_LIT_TABLE : R_LIT_INLINE;
@@ -466,6 +573,7 @@ struct Walker {
                 } else if (pc != NODE_NONE) {
                     pend &= ~(1ull << r);
                     cv = pc;
+                    ccls = (x.plus & CLS_MASK) >> CLS_SHIFT;
                     cr = r + 1;
                     ++plus_now;
                     reach = R_PLUS_NOW;
@@ -477,7 +585,8 @@ struct Walker {
                 if (!m) break;
                 const uint32_t k = 63u - (uint32_t)__builtin_clzll(m);
                 pend &= ~(1ull << k);
-                cv = path[k];
+                cv = path[k] & NODE_MASK;
+                ccls = (path[k] & CLS_MASK) >> CLS_SHIFT;
                 cr = k + 1;
                 ++plus_pop;
                 reach = R_PLUS_POP;
@@ -494,7 +603,7 @@ extern "C" {
 struct SimOut {
     uint64_t req[K_NKIND], l1m[K_NKIND], l2m[K_NKIND];
     uint64_t topics, steps, matches, rounds;
-    uint64_t probes_ok, probes_fail, table_visits, plus_now, plus_pop, lit_inline;
+    uint64_t probes_ok, probes_fail, table_visits, plus_now, plus_pop, lit_inline, probes_saved;
     uint64_t reach_req[R_NREACH], reach_l2m[R_NREACH];   // node loads by how the node was reached
     double wave_time;        // mean over waves of the summed per-round max latency (cycles)
     double wave_rounds;      // mean over waves of the dependent rounds executed
@@ -516,6 +625,12 @@ int sim_run(const void* view, const uint32_t* levels, const uint32_t* words, con
                     (uint32_t)((mode >> 24) & 0x3F), (mode & M_GFPTR) != 0);
         wk.gf = &gfilt;
     }
+    NFilt nfilt;
+    if (mode & M_NFS) {
+        nfilt.build(vw, (uint32_t)((mode >> 16) & 0xFF) ? (uint32_t)((mode >> 16) & 0xFF) : 16u,
+                    (uint32_t)((mode >> 24) & 0x3F));
+        wk.nf = &nfilt;
+    }
     if (mode & (M_BLOCKS | M_FIX)) {
         blocks.build(vw, (uint32_t)((mode >> 8) & 0xFF) ? (uint32_t)((mode >> 8) & 0xFF) : 2u);
         wk.blk = &blocks;
@@ -535,7 +650,8 @@ int sim_run(const void* view, const uint32_t* levels, const uint32_t* words, con
         switch (a.kind) {
             case K_INNER: return 0 * R + i * 16;
             case K_PAIR: return (mode & M_FIX)  ? 4 * R + (uint64_t)a.idx * 16
-                                : (mode & M_GF) ? 5 * R + (uint64_t)a.idx * 4 : 0 * R + i * 16;
+                                : (mode & M_GF) ? 5 * R + (uint64_t)a.idx * 4
+                                : (mode & M_NFS) ? 5 * R + (uint64_t)a.idx * 64 : 0 * R + i * 16;
             case K_LEAF: return 1 * R + i * 16;
             case K_COLD: return 2 * R + i * sb + hi * 16;
             default: return 3 * R + i * sb + hi * 16;
@@ -627,6 +743,7 @@ int sim_run(const void* view, const uint32_t* levels, const uint32_t* words, con
     out->plus_now = wk.plus_now;
     out->plus_pop = wk.plus_pop;
     out->lit_inline = wk.lit_inline;
+    out->probes_saved = wk.probes_saved;
     return 0;
 }
 
