@@ -16,10 +16,10 @@ $(BUILD):
 	mkdir -p $(BUILD)
 
 # every kernel file: one rule (device_bytes.h is the shared device header)
-$(BUILD)/%.o: emqx_amd/csrc/%.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h emqx_amd/csrc/device_bytes.h include/topicmatch.h | $(BUILD)
+$(BUILD)/%.o: emqx_amd/csrc/%.hip emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h emqx_amd/csrc/device_bytes.h emqx_amd/csrc/deliver.h include/topicmatch.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/engine.o: emqx_amd/csrc/engine.cpp emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h include/topicmatch.h | $(BUILD)
+$(BUILD)/engine.o: emqx_amd/csrc/engine.cpp emqx_amd/csrc/kernels.h emqx_amd/csrc/image.h emqx_amd/csrc/deliver.h include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O3 -fPIC -std=c++17 -Wall $(TMDEFS) -c $< -o $@
 
 # A/B builds of compile-time variants: make variant TAG=x TMDEFS="-D..." ->
@@ -107,3 +107,14 @@ san_nfilter: $(LIBOUT)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_nfilter_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_nfilter
 	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_nfilter
 .PHONY: san_nfilter
+
+# the subscription-option host calls (tm_sub_add_opts, tm_sub_set_opts, the
+# option pool through growth, in-place rewrites, deletes and compaction, the
+# *_opts calls' argument checks) under AddressSanitizer + UBSan on a host-only
+# engine (tools/san_subopts.cpp); the kernels linked as built and never run.
+san_subopts: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c tools/san_subopts.cpp -o $(BUILD)/san_subopts_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_subopts_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_subopts
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_subopts
+.PHONY: san_subopts

@@ -90,6 +90,23 @@ class TmRouteResult(ctypes.Structure):
                 ("d_counts", ctypes.c_void_p), ("d_offs", ctypes.c_void_p), ("d_ids", ctypes.c_void_p)]
 
 
+TM_SUBOPT_NONE = 3
+TM_SUBOPT_NL = 4
+TM_SUBOPT_RAP = 8
+TM_SUBOPT_SUBID_SHIFT = 4
+TM_MSG_RETAIN = 4
+TM_MSG_RETAINED = 8
+TM_DELIVER_DROP = 8
+TM_DELIVER_UPGRADE_QOS = 1
+TM_NO_SUBSCRIBER = 0xFFFFFFFF
+
+
+class TmDeliver(ctypes.Structure):
+    """tm_deliver: host pointers in the host forms, device pointers in the device forms."""
+    _fields_ = [("pub_flags", ctypes.c_void_p), ("pub_from", ctypes.c_void_p), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("sub_deliver", ctypes.c_void_p)]
+
+
 TM_ROUTE_ALL = 0xFFFFFFFF
 TM_COMM_ID_BYTES = 128
 TM_BATCHER_ROUTES = 1
@@ -271,6 +288,35 @@ SIGNATURES = [
     ("tm_dispatch_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.c_void_p]),
+    ("tm_sub_add_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]),
+    ("tm_sub_add_opts_batch", ctypes.c_int, [ctypes.c_void_p] * 8 + [ctypes.c_uint32]),
+    ("tm_sub_set_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)]),
+    ("tm_sub_get_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
+    ("tm_deliver_word", ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32]),
+    # the *_opts calls: the plain call's arguments plus one const tm_deliver* (TmDeliver, by reference),
+    # in the device forms before the stream
+    ("tm_match_dispatch_batch_opts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5 +
+     [ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_match_dispatch_batch_opts_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64] + [ctypes.c_void_p] * 5 +
+     [ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
+    ("tm_dispatch_batch_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_match_publish_batch_opts", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5 +
+     [ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_match_publish_batch_opts_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64] + [ctypes.c_void_p] * 5 +
+     [ctypes.c_uint64] + [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p]),
     ("tm_share_add", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
                                     ctypes.c_uint32, ctypes.c_uint32]),
     ("tm_share_del", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,

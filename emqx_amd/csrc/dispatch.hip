@@ -31,11 +31,20 @@
 //           Every pair is written by exactly one lane with a coalesced 4 B
 //           store; a bag of 250,000 subscribers is ~250 waves' work, not one
 //           lane's.  No atomics.
+//
+// With subscription options (the *_opts calls) the count pass also stores each
+// slot's topic index and the emit also writes, beside sub_id[p], the delivery
+// word of emqx_session:handle_dispatch/3 + run_dispatch_steps/3
+// (src/emqx_session.erl:667-684, 797-819; deliver.h) from the option word at
+// the pair's pool index.  Both are kernels of their own (tm_dispatch_count_pub,
+// tm_dispatch_emit_opts): the calls without options launch the plain ones,
+// which carry no branch for it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "image.h"
 #include "kernels.h"
 #include "device_bytes.h"
+#include "deliver.h"
 
 namespace tmx {
 
@@ -51,13 +60,17 @@ __device__ __forceinline__ uint4 sub_exact_lookup(const SubView& sv, const uint8
 }
 
 // pass 1 over blocks of 256 topics (their delivery spans are one contiguous
-// slot range, read coalesced): per slot ndisp, plain count and segment
-__global__ void __launch_bounds__(DBLOCK)
-tm_dispatch_count(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
-                  const uint32_t* __restrict__ acount, const uint64_t* __restrict__ aoff,
-                  const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg, uint64_t slots,
-                  uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg,
-                  const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate) {
+// slot range, read coalesced): per slot ndisp, plain count and segment.  PUB:
+// also the slot's topic (its publish index) into ppub, which the delivery-word
+// emit reads per slot; the plain instantiation has no such store.
+template <bool PUB>
+__device__ __forceinline__ void
+dispatch_count_body(const SubView& sv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
+                    const uint32_t* __restrict__ acount, const uint64_t* __restrict__ aoff,
+                    const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg, uint64_t slots,
+                    uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg,
+                    const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate,
+                    uint32_t* __restrict__ ppub) {
     __shared__ uint64_t lds_inc[DBLOCK];   // inclusive prefix of the block's spans
     __shared__ uint64_t lds_scan[DBLOCK / 64];
     if (gate && *gate) return;   // an earlier stage of a stream-ordered publish overflowed (wave-uniform)
@@ -107,7 +120,27 @@ tm_dispatch_count(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t*
         ndisp[g] = nd;
         pcnt[g] = pc;
         pseg[g] = ps;
+        if constexpr (PUB) ppub[g] = tl;
     }
+}
+
+__global__ void __launch_bounds__(DBLOCK)
+tm_dispatch_count(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
+                  const uint32_t* __restrict__ acount, const uint64_t* __restrict__ aoff,
+                  const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg, uint64_t slots,
+                  uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg,
+                  const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate) {
+    dispatch_count_body<false>(sv, bytes, off, n, acount, aoff, to, tg, slots, ndisp, pcnt, pseg, dtotal, gate, nullptr);
+}
+
+__global__ void __launch_bounds__(DBLOCK)
+tm_dispatch_count_pub(SubView sv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
+                      const uint32_t* __restrict__ acount, const uint64_t* __restrict__ aoff,
+                      const uint32_t* __restrict__ to, const uint32_t* __restrict__ tg, uint64_t slots,
+                      uint32_t* __restrict__ ndisp, uint32_t* __restrict__ pcnt, uint32_t* __restrict__ pseg,
+                      const uint64_t* __restrict__ dtotal, const uint64_t* __restrict__ gate,
+                      uint32_t* __restrict__ ppub) {
+    dispatch_count_body<true>(sv, bytes, off, n, acount, aoff, to, tg, slots, ndisp, pcnt, pseg, dtotal, gate, ppub);
 }
 
 // dispatch/2 called by To bytes (a remote node's forward/3): slot i = To i
@@ -141,10 +174,28 @@ tm_dispatch_offsets(const uint64_t* __restrict__ P, uint64_t slots, const uint64
 // pass 3: pair p of the batch is subscriber (p - P[s]) of slot s's segment,
 // s the slot with P[s] <= p < P[s+1].  Every value that steers the loops
 // (chunk, cur, j, the window's end) is the same in all 64 lanes.
-__global__ void __launch_bounds__(DBLOCK)
-tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
-                 const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to, uint32_t* __restrict__ sub_to,
-                 uint32_t* __restrict__ sub_id, uint64_t cap, const uint64_t* __restrict__ gate) {
+//
+// OPT (the delivery word, deliver.h): the pair's option word sits at its pool
+// index in the parallel pool `opt`; the publish word and the publisher of a
+// slot's topic are loaded once per slot of the window (topic = ppub[slot], or
+// the slot itself when ppub is null: tm_dispatch_batch_opts, slot i = entry i)
+// and reach the pair's lane by the shuffles that carry `to`.  One more
+// coalesced 4 B load and one more coalesced 4 B store per pair.
+struct DeliverArgs {
+    const uint32_t* opt;         // parallel to pool
+    const uint32_t* ppub;        // per slot: publish index (null: the slot index)
+    const uint32_t* pub_flags;   // per publish
+    const uint32_t* pub_from;    // per publish (null: no publisher is a subscriber)
+    uint32_t flags;
+    uint32_t* sub_deliver;       // parallel to sub_id
+};
+
+template <bool OPT>
+__device__ __forceinline__ void
+dispatch_emit_body(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
+                   const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to, uint32_t* __restrict__ sub_to,
+                   uint32_t* __restrict__ sub_id, uint64_t cap, const uint64_t* __restrict__ gate,
+                   const DeliverArgs& dv) {
     if (gate && *gate) return;
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * DBLOCK + threadIdx.x) >> 6;
@@ -170,6 +221,14 @@ tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__
                 const uint64_t b = P[jj + 1 < slots ? jj + 1 : slots];     // its end
                 const uint32_t sg = jj < slots ? pseg[jj] : 0u;
                 const uint32_t tv = (to && jj < slots) ? to[jj] : 0u;
+                uint32_t pfv = 0u, frv = NO_SUBSCRIBER;   // only a slot with pairs reads its publish
+                if constexpr (OPT) {
+                    if (jj < slots && b > a) {
+                        const uint32_t pb = dv.ppub ? dv.ppub[jj] : (uint32_t)jj;
+                        pfv = dv.pub_flags[pb];
+                        if (dv.pub_from) frv = dv.pub_from[pb];
+                    }
+                }
                 const uint64_t wraw = __shfl(b, 63, 64);
                 const uint64_t wend = wraw < p1 ? wraw : p1;
                 for (uint64_t q = cur; q < wend; q += 64) {
@@ -182,9 +241,22 @@ tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__
                     const uint64_t as = __shfl(a, (int)s, 64);
                     const uint32_t ss = __shfl(sg, (int)s, 64);
                     const uint32_t ts = __shfl(tv, (int)s, 64);
-                    if (p < wend) {
-                        sub_id[p] = pool[ss + (uint32_t)(p - as)];
-                        if (sub_to) sub_to[p] = ts;
+                    if constexpr (OPT) {
+                        const uint32_t pfs = __shfl(pfv, (int)s, 64);
+                        const uint32_t frs = __shfl(frv, (int)s, 64);
+                        if (p < wend) {
+                            const uint32_t ix = ss + (uint32_t)(p - as);
+                            const uint32_t sub = pool[ix];
+                            const uint32_t ow = dv.opt[ix];
+                            sub_id[p] = sub;
+                            if (sub_to) sub_to[p] = ts;
+                            dv.sub_deliver[p] = deliver_word(ow, pfs, frs != NO_SUBSCRIBER && sub == frs, dv.flags);
+                        }
+                    } else {
+                        if (p < wend) {
+                            sub_id[p] = pool[ss + (uint32_t)(p - as)];
+                            if (sub_to) sub_to[p] = ts;
+                        }
                     }
                 }
                 const bool moved = wend > cur;
@@ -195,13 +267,32 @@ tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__
     }
 }
 
+__global__ void __launch_bounds__(DBLOCK)
+tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
+                 const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to, uint32_t* __restrict__ sub_to,
+                 uint32_t* __restrict__ sub_id, uint64_t cap, const uint64_t* __restrict__ gate) {
+    dispatch_emit_body<false>(pool, P, slots, pseg, to, sub_to, sub_id, cap, gate, DeliverArgs{});
+}
+
+__global__ void __launch_bounds__(DBLOCK)
+tm_dispatch_emit_opts(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
+                      const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to,
+                      uint32_t* __restrict__ sub_to, uint32_t* __restrict__ sub_id, uint64_t cap, DeliverArgs dv) {
+    dispatch_emit_body<true>(pool, P, slots, pseg, to, sub_to, sub_id, cap, nullptr, dv);
+}
+
 static inline uint32_t ddiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 hipError_t launch_dispatch_count(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                  const uint32_t* acount, const uint64_t* aoff, const uint32_t* to, const uint32_t* tg,
                                  uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st,
-                                 const uint64_t* dtotal, const uint64_t* gate) {
+                                 const uint64_t* dtotal, const uint64_t* gate, uint32_t* ppub) {
     if (n == 0 || slots == 0) return hipSuccess;
+    if (ppub) {
+        hipLaunchKernelGGL(tm_dispatch_count_pub, dim3(ddiv_up(n, DBLOCK)), dim3(DBLOCK), 0, st, sv, bytes, off, n,
+                           acount, aoff, to, tg, slots, ndisp, pcnt, pseg, dtotal, gate, ppub);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(tm_dispatch_count, dim3(ddiv_up(n, DBLOCK)), dim3(DBLOCK), 0, st, sv, bytes, off, n, acount,
                        aoff, to, tg, slots, ndisp, pcnt, pseg, dtotal, gate);
     return hipGetLastError();
@@ -233,6 +324,21 @@ hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t s
     if (blocks > 2048u) blocks = 2048u;
     hipLaunchKernelGGL(tm_dispatch_emit, dim3(blocks), dim3(DBLOCK), 0, st, sv.pool, P, slots, pseg, to, sub_to, sub_id,
                        cap, gate);
+    return hipGetLastError();
+}
+
+hipError_t launch_dispatch_emit_opts(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
+                                     const uint32_t* to, const uint32_t* ppub, const uint32_t* pub_flags,
+                                     const uint32_t* pub_from, uint32_t flags, uint32_t* sub_to, uint32_t* sub_id,
+                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st) {
+    const uint64_t bound = pairs_bound < cap ? pairs_bound : cap;
+    if (slots == 0 || bound == 0) return hipSuccess;
+    if (!sv.opt || !pub_flags || !sub_deliver) return hipErrorInvalidValue;
+    uint32_t blocks = ddiv_up(bound, (uint64_t)DCHUNK * (DBLOCK / 64));   // as launch_dispatch_emit
+    if (blocks > 2048u) blocks = 2048u;
+    const DeliverArgs dv{sv.opt, ppub, pub_flags, pub_from, flags, sub_deliver};
+    hipLaunchKernelGGL(tm_dispatch_emit_opts, dim3(blocks), dim3(DBLOCK), 0, st, sv.pool, P, slots, pseg, to, sub_to,
+                       sub_id, cap, dv);
     return hipGetLastError();
 }
 

@@ -44,6 +44,7 @@
 #include "../../include/topicmatch.h"
 #include "image.h"
 #include "kernels.h"
+#include "deliver.h"
 
 using namespace tmx;
 
@@ -459,6 +460,7 @@ struct Image {
     DevBuf d_fshape;   // option "shape_keys": filter id -> order key
     // subscriber image (dispatch.hip), same epoch as the trie and the routes
     DevBuf d_sslots, d_sarena, d_spool, d_fs_meta;
+    DevBuf d_sopt;     // emqx_suboption words, parallel to d_spool
     // share image (share.hip), same epoch; cursor: the replica's round-robin
     // cursors (DevState::sh_cursor) as they were when this image was written
     DevBuf d_hsets, d_htx, d_harena, d_hpool, d_hfx;
@@ -484,7 +486,7 @@ struct Image {
     void release() {
         for (DevBuf* b : {&d_nodes, &d_edges, &d_hedges, &d_dict, &d_arena, &d_woff, &d_inner, &d_leaf, &d_rslots,
                           &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat,
-                          &d_sslots, &d_sarena, &d_spool, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx,
+                          &d_sslots, &d_sarena, &d_spool, &d_sopt, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx,
                           &d_fwd})
             b->release();
         for (hipEvent_t ev : uses) (void)hipEventDestroy(ev);
@@ -578,6 +580,7 @@ struct DevState {
     // dispatch (dispatch.hip): per-slot plain counts, segments and prefix, and
     // the host-buffer call's deliveries / pairs before they go back
     DevBuf w_xpcnt, w_xpseg, w_xpre, w_xscan, w_xto, w_xscount, w_xsoff, w_xsub;
+    DevBuf w_xppub, w_xdpub;   // delivery words: per slot its publish, the host forms' pub_flags / pub_from
     // shared-subscription pick (share.hip): per-slot Count / segment / set index
     // / flag and the flag prefix, the (set index, slot) pairs and their sort,
     // the runs' new cursors, and the host-buffer call's keys and picks
@@ -643,7 +646,7 @@ struct DevState {
         for (DevBuf* b : {&stage_dev, &w_rexact, &w_rscan, &w_rids, &w_rcounts, &w_roff, &w_dsrc, &w_dcount, &w_akey,
                           &w_alarge, &w_mpre, &w_mscan, &w_bytes, &w_off, &w_counts, &w_outoff, &w_ids, &w_total,
                           &w_xpcnt, &w_xpseg, &w_xpre, &w_xscan, &w_xto, &w_xscount, &w_xsoff, &w_xsub,
-                          &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
+                          &w_xppub, &w_xdpub, &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
                           &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor, &sh_sticky, &w_hkplane,
                           &w_htg, &w_hfail, &w_hfoff, &w_hdown, &w_fflag, &w_fpub, &w_fpre, &w_fscan, &w_fpairs,
                           &w_fhead, &w_fhpre, &w_fcounts, &w_foff, &w_fsscan, &w_fin, &w_fout,
@@ -935,6 +938,9 @@ struct tm_engine {
         std::vector<std::pair<uint32_t, uint32_t>> bag;   // (sub, group | NO_GROUP), insertion order
         // the plain subscribers once the bag passes BAG_INDEX_MIN entries (scanned below that)
         std::unique_ptr<std::unordered_set<uint32_t>> index;
+        // emqx_suboption's entries of this topic: sub -> option word, one per
+        // (topic, sub) whatever the entry's group (do_subscribe/4 :410)
+        std::unordered_map<uint32_t, uint32_t> opts;
         uint32_t n_plain = 0;
         const std::string* key = nullptr;     // the sub_bag key (node-stable)
         uint32_t slot = SLOT_NONE;            // exact-table slot (sx_slots)
@@ -957,6 +963,12 @@ struct tm_engine {
     MirrorTable<SubSlot, SubRec> sx_slots;
     TopicArena sx_arena;
     SegPool sx_pool;
+    // emqx_suboption on the device: sx_opt[i] is the option word of the plain
+    // subscriber at sx_pool.v[i] (SUBOPT_NONE without an entry).  It shares
+    // the segments' {off, cap} and moves wherever they move.
+    std::vector<uint32_t> sx_opt;
+    Track t_opt;
+    uint64_t sx_compactions = 0, sx_seg_moves = 0;   // diagnostics (tm_debug_sub_pool_stats)
     FilterLink<uint4, SubRec> fs{make_uint4(0, 0, 0, 0)};
     bool local_set = false;        // tm_set_local_node: the target that is node()
     uint32_t local_target = 0;
@@ -1785,10 +1797,19 @@ struct tm_engine {
     // insert_subscriber/3 (:398-415): the membership test is on the bare
     // Subscriber (:399-405), so only a plain entry suppresses an add, whatever
     // the group; a repeated shared add duplicates the entry (duplicate_bag)
-    void sub_add(const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+    // opts (tm_sub_add_opts): do_subscribe/4 :407-410, the option entry is
+    // written whether or not the bag took the entry
+    void sub_add(const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen,
+                 const uint32_t* opts = nullptr) {
         std::string key(reinterpret_cast<const char*>(t), tlen);
         auto it = sub_bag.find(key);
-        if (it != sub_bag.end() && it->second.has_plain(sub)) return;
+        if (it != sub_bag.end() && it->second.has_plain(sub)) {
+            if (opts) {
+                it->second.opts[sub] = *opts;
+                opt_word_sync(it->second, sub);
+            }
+            return;
+        }
         const uint32_t gid = g ? intern_group(g, glen) : NO_GROUP;
         if (it == sub_bag.end()) {
             it = sub_bag.emplace(std::move(key), SubRec{}).first;
@@ -1801,6 +1822,7 @@ struct tm_engine {
             if (tm_topic_wildcard(t, tlen)) link_filter(r, filter_of(t, tlen));
         }
         SubRec& r = it->second;
+        if (opts) r.opts[sub] = *opts;   // before the append: the new plain entry's word
         r.bag.emplace_back(sub, gid);
         if (gid == NO_GROUP) {
             ++r.n_plain;
@@ -1814,9 +1836,19 @@ struct tm_engine {
     }
     // ets:delete_object(?SUBSCRIBER, {Topic, shared(Group, Sub)}) (:447-448):
     // every equal object goes, an absent one is a no-op; returns the entries left
+    // with ets:delete(?SUBOPTION, {Topic, Subscriber}) (:415): the option entry
+    // goes whatever the group and whether or not an object went
     uint32_t sub_del(const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
         auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
         if (it == sub_bag.end()) return 0;
+        const bool had = it->second.opts.erase(sub) != 0;
+        const uint32_t left = sub_del_object(it, sub, g, glen);
+        // a plain entry that stays lost its word (one that went: sseg_rewrite)
+        if (had && left && it->second.has_plain(sub)) opt_word_sync(it->second, sub);
+        return left;
+    }
+    uint32_t sub_del_object(std::unordered_map<std::string, SubRec>::iterator it, uint32_t sub, const uint8_t* g,
+                            uint32_t glen) {
         SubRec& r = it->second;
         uint32_t gid = NO_GROUP;
         if (g) {
@@ -1849,6 +1881,20 @@ struct tm_engine {
         maybe_compact_subs();
         return 0;
     }
+    // set_subopts/3 (:285-291): false without an entry
+    bool sub_set_opts(const uint8_t* t, uint32_t tlen, uint32_t sub, uint32_t mask, uint32_t value) {
+        auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
+        if (it == sub_bag.end()) return false;
+        SubRec& r = it->second;
+        auto oi = r.opts.find(sub);
+        if (oi == r.opts.end()) return false;
+        const uint32_t w = (oi->second & ~mask) | (value & mask);
+        if ((w & SUBOPT_QOS_MASK) == SUBOPT_NONE) throw ArgError("subscription option qos 3");
+        if (w == oi->second) return true;
+        oi->second = w;
+        if (r.has_plain(sub)) opt_word_sync(r, sub);
+        return true;
+    }
     const SubRec* subscribers(const uint8_t* t, uint32_t tlen) const {
         auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
         return it == sub_bag.end() ? nullptr : &it->second;
@@ -1868,29 +1914,69 @@ struct tm_engine {
         if (r.fid != FILTER_NONE) fs.set(r.fid, make_uint4(r.off, r.n_plain, n_all, 0u));
     }
     // the plain subscribers of r into its segment, from the bag
+    static uint32_t opt_word(const SubRec& r, uint32_t sub) {
+        if (r.opts.empty()) return SUBOPT_NONE;
+        auto it = r.opts.find(sub);
+        return it == r.opts.end() ? SUBOPT_NONE : it->second;
+    }
+    // the plain subscribers of r and their option words into its segment, from
+    // the bag and the option map
     void sseg_rewrite(SubRec& r) {
-        sx_pool.fit(r.off, r.cap, r.n_plain, "subscriber pool past 2^32 entries");
+        if (sx_pool.fit(r.off, r.cap, r.n_plain, "subscriber pool past 2^32 entries")) ++sx_seg_moves;
+        sx_opt.resize(sx_pool.v.size(), SUBOPT_NONE);
         size_t k = r.off;
         for (const auto& x : r.bag)
-            if (x.second == NO_GROUP) sx_pool.v[k++] = x.first;
+            if (x.second == NO_GROUP) {
+                sx_pool.v[k] = x.first;
+                sx_opt[k++] = opt_word(r, x.first);
+            }
         sx_pool.t.mark_range(r.off, k);
+        t_opt.mark_range(r.off, k);
         sx_sync(r);
     }
     void sseg_append(SubRec& r, uint32_t sub) {   // sub is r's last plain entry
         if (r.n_plain > r.cap) return sseg_rewrite(r);
-        sx_pool.set(r.off + r.n_plain - 1, sub);
+        const size_t i = r.off + r.n_plain - 1;
+        sx_pool.set(i, sub);
+        sx_opt[i] = opt_word(r, sub);
+        t_opt.cur.mark(i);
         sx_sync(r);
+    }
+    // the one word of r's plain entry `sub`, in place (a scan of the segment:
+    // a plain subscriber is in its bag once)
+    void opt_word_sync(const SubRec& r, uint32_t sub) {
+        const uint32_t* seg = sx_pool.v.data() + r.off;
+        const uint32_t* at = std::find(seg, seg + r.n_plain, sub);
+        if (at == seg + r.n_plain) return;
+        const size_t i = r.off + (size_t)(at - seg);
+        const uint32_t w = opt_word(r, sub);
+        if (sx_opt[i] == w) return;
+        sx_opt[i] = w;
+        t_opt.cur.mark(i);
+        dev_dirty = true;
     }
     // option "route_gc" sets the threshold of all three images
     void maybe_compact_subs() {
+        std::vector<uint32_t> nopt;   // the option words follow their segments
+        bool pool_gc = false;
         compact(sx_pool, sx_arena, route_gc_min, [&](auto seg, auto top) {
             for (auto& kv : sub_bag) {
                 SubRec& r = kv.second;
-                seg(r.off, r.cap);
+                const uint32_t from = r.off;
+                if (seg(r.off, r.cap)) {
+                    pool_gc = true;
+                    nopt.insert(nopt.end(), sx_opt.begin() + from, sx_opt.begin() + from + r.cap);
+                }
                 top(r.arena, r.words);
                 sx_sync(r);
             }
         });
+        if (pool_gc || sx_opt.size() != sx_pool.v.size()) {   // (a pool of garbage only: rewritten empty)
+            sx_opt.swap(nopt);
+            sx_opt.resize(sx_pool.v.size(), SUBOPT_NONE);
+            ++sx_compactions;
+            t_opt.cur.all = true;
+        }
     }
     SubView make_sub_view(const Image& g) const {
         SubView sv;
@@ -1901,6 +1987,7 @@ struct tm_engine {
         sv.sx_slot_mask = sx_slots.slots.size() - 1;
         sv.sx_arena = g.d_sarena.as<const uint8_t>();
         sv.pool = g.d_spool.as<const uint32_t>();
+        sv.opt = g.d_sopt.as<const uint32_t>();
         return sv;
     }
 
@@ -2671,6 +2758,7 @@ struct tm_engine {
         f(sx_slots.slots, sx_slots.t, &Image::d_sslots, true);
         f(sx_arena.words, sx_arena.t, &Image::d_sarena, true);
         f(sx_pool.v, sx_pool.t, &Image::d_spool, true);
+        f(sx_opt, t_opt, &Image::d_sopt, true);
         f(fs.meta, fs.t, &Image::d_fs_meta, true);
         f(sh_sets.slots, sh_sets.t, &Image::d_hsets, true);
         f(sh_tx.slots, sh_tx.t, &Image::d_htx, true);
@@ -3229,20 +3317,31 @@ struct tm_engine {
     // total, the deliveries' capacity)
     void dispatch_count(DevState& d, const uint8_t* bytes, const uint64_t* off, uint32_t n, const uint32_t* acount,
                         const uint64_t* aoff, const uint32_t* to, const uint32_t* tg, uint64_t slots, uint32_t* ndisp,
-                        uint32_t* sub_count, uint64_t* sub_off, hipStream_t st) {
+                        uint32_t* sub_count, uint64_t* sub_off, hipStream_t st, bool pub = false) {
         if (slots >= 0xFFFFFFFEull) throw RangeError("dispatch: more than 2^32 - 2 delivery slots in one batch");
+        if (pub) d.w_xppub.ensure((size_t)slots * 4 + 4);   // the delivery-word emit's per-slot publish index
         d.w_xpcnt.ensure((size_t)slots * 4 + 4);
         d.w_xpseg.ensure((size_t)slots * 4 + 4);
         d.w_xpre.ensure((size_t)(slots + 1) * 8);
         d.w_xscan.ensure(scan_tmp_elems((uint32_t)slots) * 8 + 8);
         uint64_t* P = d.w_xpre.as<uint64_t>();
         HIPCHK(launch_dispatch_count(sub_view(d), bytes, off, n, acount, aoff, to, tg, slots, ndisp,
-                                     d.w_xpcnt.as<uint32_t>(), d.w_xpseg.as<uint32_t>(), st));
+                                     d.w_xpcnt.as<uint32_t>(), d.w_xpseg.as<uint32_t>(), st, nullptr, nullptr,
+                                     pub ? d.w_xppub.as<uint32_t>() : nullptr));
         HIPCHK(launch_scan0(d.w_xpcnt.as<uint32_t>(), (uint32_t)slots, P, P + slots, d.w_xscan.as<uint64_t>(), st));
         HIPCHK(launch_dispatch_offsets(P, slots, aoff, n, sub_count, sub_off, st));
     }
+    // dv (device pointers): the delivery-word emit, after a dispatch_count
+    // with pub set (by_slot: slot i is publish i, after launch_dispatch_lookup)
     void dispatch_emit(DevState& d, uint64_t slots, const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
-                       uint64_t pairs_bound, hipStream_t st) {
+                       uint64_t pairs_bound, hipStream_t st, const tm_deliver* dv = nullptr, bool by_slot = false) {
+        if (dv) {
+            HIPCHK(launch_dispatch_emit_opts(sub_view(d), d.w_xpre.as<uint64_t>(), slots, d.w_xpseg.as<uint32_t>(), to,
+                                             by_slot ? nullptr : d.w_xppub.as<uint32_t>(), dv->pub_flags,
+                                             dv->pub_from, dv->flags, sub_to, sub_id, dv->sub_deliver, cap,
+                                             pairs_bound, st));
+            return;
+        }
         HIPCHK(launch_dispatch_emit(sub_view(d), d.w_xpre.as<uint64_t>(), slots, d.w_xpseg.as<uint32_t>(), to, sub_to,
                                     sub_id, cap, pairs_bound, st));
     }
@@ -3319,13 +3418,13 @@ struct tm_engine {
                       uint32_t* counts, uint64_t* out_off, uint32_t* to, uint32_t* target, uint32_t* ndisp, uint64_t cap,
                       uint64_t* total, uint32_t* sub_count, uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id,
                       uint64_t sub_cap, uint64_t* sub_total, hipStream_t st, uint32_t strategy = 0,
-                      const uint32_t* pub_key = nullptr, uint32_t* pick = nullptr) {
+                      const uint32_t* pub_key = nullptr, uint32_t* pick = nullptr, const tm_deliver* dv = nullptr) {
         uint64_t rcap = 0, rtotal = 0;
         deliveries_routes(d, bytes, off, n, nbytes, out_off, total, st, rcap, &rtotal);
         aggre_out(d, n, out_off, rcap, counts, to, target, cap, st);
         const uint64_t slots = std::min(rtotal, cap);
-        dispatch_count(d, bytes, off, n, counts, out_off, to, target, slots, ndisp, sub_count, sub_off, st);
-        dispatch_emit(d, slots, to, sub_to, sub_id, sub_cap, sub_cap, st);
+        dispatch_count(d, bytes, off, n, counts, out_off, to, target, slots, ndisp, sub_count, sub_off, st, dv != nullptr);
+        dispatch_emit(d, slots, to, sub_to, sub_id, sub_cap, sub_cap, st, dv);
         HIPCHK(hipMemcpyAsync(sub_total, d.w_xpre.as<uint64_t>() + slots, 8, hipMemcpyDeviceToDevice, st));
         if (strategy) share_pick(d, bytes, off, n, counts, out_off, to, target, slots, strategy, pub_key, pick, st);
         d.note_use(st);   // the dispatch and share kernels read the pinned images after the walk's use
@@ -4745,6 +4844,59 @@ int tm_sub_del_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_
                      });
 }
 
+// ---- subscription options (emqx_suboption) -----------------------------------
+static_assert(TM_SUBOPT_NONE == SUBOPT_NONE && TM_SUBOPT_NL == SUBOPT_NL && TM_SUBOPT_RAP == SUBOPT_RAP &&
+                  TM_MSG_RETAIN == MSG_RETAIN && TM_MSG_RETAINED == MSG_RETAINED && TM_DELIVER_DROP == DELIVER_DROP &&
+                  TM_DELIVER_UPGRADE_QOS == DELIVER_UPGRADE_QOS && TM_NO_SUBSCRIBER == NO_SUBSCRIBER,
+              "deliver.h packs the words include/topicmatch.h documents");
+
+int tm_sub_add_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group,
+                    uint32_t glen, uint32_t opts) {
+    if ((!topic && tlen) || sub == 0xFFFFFFFFu || (opts & 3u) == TM_SUBOPT_NONE) return TM_EINVAL;
+    return guarded(e, [&] {
+        e->sub_add(topic, tlen, sub, group, glen, &opts);
+        return TM_OK;
+    });
+}
+
+int tm_sub_add_opts_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                          const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared,
+                          const uint32_t* opts, uint32_t n) {
+    if (n && !opts) return TM_EINVAL;
+    uint32_t i = 0;   // sub_batch applies the entries in order, one call each
+    return sub_batch(e, topics, topic_off, subs, groups, group_off, shared, n,
+                     [&](const uint8_t* t, uint32_t tlen, uint32_t sub, const uint8_t* g, uint32_t glen) {
+                         const uint32_t w = opts[i++];
+                         if ((w & 3u) == TM_SUBOPT_NONE) throw ArgError("subscription option qos 3");
+                         e->sub_add(t, tlen, sub, g, glen, &w);
+                     });
+}
+
+int tm_sub_set_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, uint32_t mask, uint32_t value,
+                    int* found) {
+    if ((!topic && tlen) || sub == 0xFFFFFFFFu) return TM_EINVAL;
+    return guarded(e, [&] {
+        const bool f = e->sub_set_opts(topic, tlen, sub, mask, value);
+        if (found) *found = f ? 1 : 0;
+        return TM_OK;
+    });
+}
+
+int tm_sub_get_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, uint32_t* opts, int* found) {
+    if ((!topic && tlen) || sub == 0xFFFFFFFFu || !opts) return TM_EINVAL;
+    return guarded(e, [&] {
+        const tm_engine::SubRec* r = e->subscribers(topic, tlen);
+        const uint32_t w = r ? tm_engine::opt_word(*r, sub) : (uint32_t)TM_SUBOPT_NONE;
+        *opts = w;
+        if (found) *found = w != TM_SUBOPT_NONE;
+        return TM_OK;
+    });
+}
+
+uint32_t tm_deliver_word(uint32_t opts, uint32_t pub_flags, int same_client, uint32_t flags) {
+    return deliver_word(opts, pub_flags, same_client != 0, flags);
+}
+
 int tm_subscribers(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t* out_sub, uint32_t* out_group,
                    uint32_t cap, uint32_t* out_n) {
     if ((!topic && tlen) || !out_n) return TM_EINVAL;
@@ -4798,13 +4950,19 @@ int local_node_unset(tm_engine* e) {
 }
 }  // namespace
 
-int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
-                                   uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
-                                   uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
-                                   uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
-                                   uint64_t sub_cap, uint64_t* d_sub_total, void* hip_stream) {
+// a device form's descriptor: the arrays it cannot do without
+static bool deliver_args_bad(const tm_deliver* dv, uint32_t n, uint64_t sub_cap) {
+    return dv && ((n && !dv->pub_flags) || (sub_cap && !dv->sub_deliver) || (dv->flags & ~TM_DELIVER_UPGRADE_QOS));
+}
+
+static int dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                 uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                 uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                 uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                 uint64_t sub_cap, uint64_t* d_sub_total, void* hip_stream, const tm_deliver* dv) {
     if (!d_off || !d_out_off || !d_total || !d_sub_off || !d_sub_total || (n && (!d_count || !d_sub_count)) ||
-        (out_cap && (!d_to || !d_target || !d_ndisp)) || (sub_cap && (!d_sub_to || !d_sub_id)))
+        (out_cap && (!d_to || !d_target || !d_ndisp)) || (sub_cap && (!d_sub_to || !d_sub_id)) ||
+        deliver_args_bad(dv, n, sub_cap))
         return TM_EINVAL;
     if (!e) return TM_EINVAL;
     if (e->devs.empty()) return no_device(e, "dispatch");
@@ -4821,9 +4979,32 @@ int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const u
             return TM_OK;
         }
         e->run_dispatch(d, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
-                        d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, st);
+                        d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, st, 0, nullptr,
+                        nullptr, dv);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
+}
+
+int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                   uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                   uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                   uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                   uint64_t sub_cap, uint64_t* d_sub_total, void* hip_stream) {
+    return dispatch_batch_device(e, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp,
+                                 out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total,
+                                 hip_stream, nullptr);
+}
+
+int tm_match_dispatch_batch_opts_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                        uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                        uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                        uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to,
+                                        uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total,
+                                        const tm_deliver* deliver, void* hip_stream) {
+    if (!deliver) return TM_EINVAL;
+    return dispatch_batch_device(e, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp,
+                                 out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total,
+                                 hip_stream, deliver);
 }
 
 // tm_match_dispatch_batch (strategy 0: no pick pass, out_pick unused) and
@@ -4834,14 +5015,38 @@ inline bool share_strategy_ok(uint32_t s) {
     return s == TM_SHARE_KEYED || s == TM_SHARE_ROUND_ROBIN || s == TM_SHARE_STICKY;
 }
 inline bool share_strategy_keyed(uint32_t s) { return s == TM_SHARE_KEYED || s == TM_SHARE_STICKY; }
+// a host form's descriptor: the arrays it cannot do without, and no PubQoS 3
+int deliver_args_host(const tm_deliver* dv, uint32_t n, uint64_t sub_cap) {
+    if (!dv) return TM_OK;
+    if (deliver_args_bad(dv, n, sub_cap)) return TM_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((dv->pub_flags[i] & 3u) == 3u) return TM_EINVAL;
+    return TM_OK;
+}
+// the host descriptor's per-publish arrays into replica workspace: the device
+// descriptor the emit takes, its words going to `words`
+tm_deliver deliver_upload(DevState& d, const tm_deliver& dv, uint32_t n, uint32_t* words, hipStream_t s) {
+    d.w_xdpub.ensure((size_t)n * 8 + 8);
+    uint32_t* pf = d.w_xdpub.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(pf, dv.pub_flags, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (dv.pub_from) HIPCHK(hipMemcpyAsync(pf + n, dv.pub_from, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    tm_deliver o{};
+    o.pub_flags = pf;
+    o.pub_from = dv.pub_from ? pf + n : nullptr;
+    o.flags = dv.flags;
+    o.sub_deliver = words;
+    return o;
+}
 int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
                            uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
                            uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
                            uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
-                           uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick) {
+                           uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick,
+                           const tm_deliver* dv = nullptr) {
     if (!topic_off || !out_off || !sub_off || (n && (!out_count || !sub_count)) ||
         (out_cap && (!out_to || !out_target || !out_ndisp || (strategy && !out_pick))) || (sub_cap && (!sub_to || !sub_id)))
         return TM_EINVAL;
+    if (int rc = deliver_args_host(dv, n, sub_cap)) return rc;
     if (strategy && !share_strategy_ok(strategy)) return TM_EINVAL;
     if (share_strategy_keyed(strategy) && n && !pub_key) return TM_EINVAL;
     if (!e) return TM_EINVAL;
@@ -4883,13 +5088,15 @@ int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topi
         uint32_t* to = d.w_xto.as<uint32_t>();
         e->aggre_out(d, n, d.w_outoff.as<uint64_t>(), rcap, d.w_counts.as<uint32_t>(), to, to + plane, rtotal, s);
         e->dispatch_count(d, b, o, n, d.w_counts.as<uint32_t>(), d.w_outoff.as<uint64_t>(), to, to + plane, rtotal,
-                          to + 2 * plane, d.w_xscount.as<uint32_t>(), d.w_xsoff.as<uint64_t>(), s);
+                          to + 2 * plane, d.w_xscount.as<uint32_t>(), d.w_xsoff.as<uint64_t>(), s, dv != nullptr);
         HIPCHK(hipMemcpyAsync(&pairs, d.w_xpre.as<uint64_t>() + rtotal, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const uint64_t splane = std::max<uint64_t>(pairs, 1);
-        d.w_xsub.ensure(splane * 8);
+        d.w_xsub.ensure(splane * (dv ? 12 : 8));   // a third plane for the delivery words
         uint32_t* sp = d.w_xsub.as<uint32_t>();
-        e->dispatch_emit(d, rtotal, to, sp, sp + splane, pairs, pairs, s);
+        tm_deliver ddv{};
+        if (dv) ddv = deliver_upload(d, *dv, n, sp + 2 * splane, s);
+        e->dispatch_emit(d, rtotal, to, sp, sp + splane, pairs, pairs, s, dv ? &ddv : nullptr);
         // the picks only when everything fits: a call that returns TM_ENOSPC
         // has advanced no cursor, so its retry picks what a first call would
         const bool fits = rtotal <= out_cap && pairs <= sub_cap;
@@ -4920,6 +5127,7 @@ int host_dispatch(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topi
         if (pc) {
             HIPCHK(hipMemcpyAsync(sub_to, sp, pc * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(sub_id, sp + splane, pc * 4, hipMemcpyDeviceToHost, s));
+            if (dv) HIPCHK(hipMemcpyAsync(dv->sub_deliver, sp + 2 * splane, pc * 4, hipMemcpyDeviceToHost, s));
         }
         HIPCHK(hipStreamSynchronize(s));
         if (out_needed) *out_needed = rtotal;
@@ -4939,9 +5147,22 @@ int tm_match_dispatch_batch(tm_engine* e, const uint8_t* topic_bytes, const uint
                          out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, 0, nullptr, nullptr);
 }
 
-int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
-                      uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed) {
+int tm_match_dispatch_batch_opts(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                                 uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                                 uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                                 uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                                 uint64_t* sub_needed, const tm_deliver* deliver) {
+    if (!deliver) return TM_EINVAL;
+    return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
+                         out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, 0, nullptr, nullptr,
+                         deliver);
+}
+
+static int dispatch_batch_host(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n,
+                               uint32_t* ndisp, uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed,
+                               const tm_deliver* dv) {
     if (!to_off || !sub_off || (n && !ndisp) || (cap && !sub_id)) return TM_EINVAL;
+    if (int rc = deliver_args_host(dv, n, cap)) return rc;
     if (!e) return TM_EINVAL;
     if (e->devs.empty()) return no_device(e, "dispatch");
     if (int rc = local_node_unset(e)) return rc;
@@ -4977,16 +5198,32 @@ int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_
         HIPCHK(hipStreamSynchronize(s));
         const uint64_t pairs = sub_off[n];
         const uint64_t splane = std::max<uint64_t>(pairs, 1);
-        d.w_xsub.ensure(splane * 4);
-        e->dispatch_emit(d, n, nullptr, nullptr, d.w_xsub.as<uint32_t>(), pairs, pairs, s);
+        d.w_xsub.ensure(splane * (dv ? 8 : 4));
+        uint32_t* sp = d.w_xsub.as<uint32_t>();
+        tm_deliver ddv{};
+        if (dv) ddv = deliver_upload(d, *dv, n, sp + splane, s);
+        e->dispatch_emit(d, n, nullptr, nullptr, sp, pairs, pairs, s, dv ? &ddv : nullptr, true);
         d.note_use(s);
         d.rw_release(s);
         const uint64_t pc = std::min(pairs, cap);
-        if (pc) HIPCHK(hipMemcpyAsync(sub_id, d.w_xsub.p, pc * 4, hipMemcpyDeviceToHost, s));
+        if (pc) HIPCHK(hipMemcpyAsync(sub_id, sp, pc * 4, hipMemcpyDeviceToHost, s));
+        if (pc && dv) HIPCHK(hipMemcpyAsync(dv->sub_deliver, sp + splane, pc * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (needed) *needed = pairs;
         return pairs > cap ? TM_ENOSPC : TM_OK;
     }, [&] {});
+}
+
+int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
+                      uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed) {
+    return dispatch_batch_host(e, to_bytes, to_off, n, ndisp, sub_off, sub_id, cap, needed, nullptr);
+}
+
+int tm_dispatch_batch_opts(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
+                           uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed,
+                           const tm_deliver* deliver) {
+    if (!deliver) return TM_EINVAL;
+    return dispatch_batch_host(e, to_bytes, to_off, n, ndisp, sub_off, sub_id, cap, needed, deliver);
 }
 
 // ---- shared subscriptions (emqx_shared_sub) ----------------------------------
@@ -5071,14 +5308,15 @@ uint64_t tm_share_count(tm_engine* e) {
     return e->sh_total;
 }
 
-int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
-                                  uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
-                                  uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
-                                  uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
-                                  uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
-                                  const uint32_t* d_pub_key, uint32_t* d_pick, void* hip_stream) {
+static int publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy, const uint32_t* d_pub_key,
+                                uint32_t* d_pick, void* hip_stream, const tm_deliver* dv) {
     if (!d_off || !d_out_off || !d_total || !d_sub_off || !d_sub_total || (n && (!d_count || !d_sub_count)) ||
-        (out_cap && (!d_to || !d_target || !d_ndisp || !d_pick)) || (sub_cap && (!d_sub_to || !d_sub_id)))
+        (out_cap && (!d_to || !d_target || !d_ndisp || !d_pick)) || (sub_cap && (!d_sub_to || !d_sub_id)) ||
+        deliver_args_bad(dv, n, sub_cap))
         return TM_EINVAL;
     if (!share_strategy_ok(strategy)) return TM_EINVAL;
     if (share_strategy_keyed(strategy) && n && !d_pub_key) return TM_EINVAL;
@@ -5098,9 +5336,33 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const ui
         }
         e->run_dispatch(d, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
                         d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, st, strategy,
-                        d_pub_key, d_pick);
+                        d_pub_key, d_pick, dv);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
+}
+
+int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                  uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                  uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                  uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id,
+                                  uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
+                                  const uint32_t* d_pub_key, uint32_t* d_pick, void* hip_stream) {
+    return publish_batch_device(e, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
+                                d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, strategy,
+                                d_pub_key, d_pick, hip_stream, nullptr);
+}
+
+int tm_match_publish_batch_opts_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                       uint64_t topic_bytes, uint32_t* d_count, uint64_t* d_out_off, uint32_t* d_to,
+                                       uint32_t* d_target, uint32_t* d_ndisp, uint64_t out_cap, uint64_t* d_total,
+                                       uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to,
+                                       uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
+                                       const uint32_t* d_pub_key, uint32_t* d_pick, const tm_deliver* deliver,
+                                       void* hip_stream) {
+    if (!deliver) return TM_EINVAL;
+    return publish_batch_device(e, d_bytes, d_off, n, topic_bytes, d_count, d_out_off, d_to, d_target, d_ndisp, out_cap,
+                                d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, strategy,
+                                d_pub_key, d_pick, hip_stream, deliver);
 }
 
 static_assert(sizeof(tm_delivery) == 16 && sizeof(tm_pair) == 8, "pack.hip stores 16 B and 8 B records");
@@ -5419,6 +5681,18 @@ int tm_match_publish_batch(tm_engine* e, const uint8_t* topic_bytes, const uint6
     return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
                          out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, strategy, pub_key,
                          out_pick);
+}
+
+int tm_match_publish_batch_opts(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                                uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                                uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                                uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                                uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick,
+                                const tm_deliver* deliver) {
+    if (!share_strategy_ok(strategy) || !deliver) return TM_EINVAL;
+    return host_dispatch(e, topic_bytes, topic_off, n, out_count, out_off, out_to, out_target, out_ndisp, out_cap,
+                         out_needed, sub_count, sub_off, sub_to, sub_id, sub_cap, sub_needed, strategy, pub_key,
+                         out_pick, deliver);
 }
 
 int tm_match_batch_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
@@ -5829,6 +6103,19 @@ extern "C" int tm_debug_check_subs(tm_engine* e) {
             if (r.cap < r.n_plain || (uint64_t)r.off + r.cap > e->sx_pool.v.size() ||
                 !std::equal(plain.begin(), plain.end(), e->sx_pool.v.begin() + r.off))
                 return fail("segment of " + kv.first);
+            // the option words of the segment against the option map, and no
+            // entry without a bag object of its subscriber (do_unsubscribe/3)
+            if ((uint64_t)r.off + r.cap > e->sx_opt.size()) return fail("option segment of " + kv.first);
+            for (size_t k = 0; k < plain.size(); ++k)
+                if (e->sx_opt[r.off + k] != tm_engine::opt_word(r, plain[k])) return fail("option word of " + kv.first);
+            if (!r.opts.empty()) {
+                std::unordered_set<uint32_t> held;
+                for (const auto& b : r.bag) held.insert(b.first);
+                for (const auto& o : r.opts) {
+                    if ((o.second & SUBOPT_QOS_MASK) == SUBOPT_NONE) return fail("option qos of " + kv.first);
+                    if (!held.count(o.first)) return fail("option entry without a subscriber of " + kv.first);
+                }
+            }
             const bool wild = tm_topic_wildcard(t, len);
             const uint32_t fid = wild ? e->filter_of(t, len) : FILTER_NONE;
             if (r.fid != fid) return fail("filter link of " + kv.first);
@@ -5842,9 +6129,27 @@ extern "C" int tm_debug_check_subs(tm_engine* e) {
         }
         if (total != e->sub_total) return fail("subscriber total");
         check_accounting(e->sx_pool, e->sx_arena, live_cap, live_words, fail);
+        if (e->sx_opt.size() != e->sx_pool.v.size()) return fail("option pool size");
         for (size_t f = 0; f < e->fs.meta.size(); ++f)
             if ((e->fs.meta[f].y || e->fs.meta[f].z) && (!e->fs.rec[f] || e->fs.rec[f]->fid != f))
                 return fail("stale fs_meta");
+        return TM_OK;
+    });
+}
+
+// diagnostics (not part of include/topicmatch.h): the subscriber pool's
+// size, its garbage, the compactions and segment moves so far and the
+// largest segment capacity (tests assert that their churn reached both paths)
+extern "C" int tm_debug_sub_pool_stats(tm_engine* e, uint64_t* out5) {
+    if (!out5) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        uint64_t cap = 0;
+        for (auto& kv : e->sub_bag) cap = std::max<uint64_t>(cap, kv.second.cap);
+        out5[0] = e->sx_pool.v.size();
+        out5[1] = e->sx_pool.garbage;
+        out5[2] = e->sx_compactions;
+        out5[3] = e->sx_seg_moves;
+        out5[4] = cap;
         return TM_OK;
     });
 }

@@ -208,6 +208,10 @@ struct SubView {
     uint64_t        sx_slot_mask;
     const uint8_t*  sx_arena;
     const uint32_t* pool;           // the plain pool
+    // emqx_suboption (src/emqx_broker.erl:407-415), parallel to pool: opt[i] is
+    // the option word (deliver.h) of the subscriber at pool[i] for its
+    // segment's topic, SUBOPT_NONE without an entry
+    const uint32_t* opt;
 };
 
 // ---- share image (emqx_shared_subscription bag, src/emqx_shared_sub.erl:49-62) ----

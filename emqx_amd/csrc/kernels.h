@@ -178,7 +178,8 @@ hipError_t launch_stream_finish(const uint64_t* ctl, const uint64_t* doff, uint3
 hipError_t launch_dispatch_count(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                  const uint32_t* acount, const uint64_t* aoff, const uint32_t* to, const uint32_t* tg,
                                  uint64_t slots, uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st,
-                                 const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr);
+                                 const uint64_t* dtotal = nullptr, const uint64_t* gate = nullptr,
+                                 uint32_t* ppub = nullptr);
 hipError_t launch_dispatch_lookup(const SubView& sv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                                   uint32_t* ndisp, uint32_t* pcnt, uint32_t* pseg, hipStream_t st);
 hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint64_t* aoff, uint32_t n,
@@ -187,6 +188,17 @@ hipError_t launch_dispatch_offsets(const uint64_t* P, uint64_t slots, const uint
 hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                 const uint32_t* to, uint32_t* sub_to, uint32_t* sub_id, uint64_t cap,
                                 uint64_t pairs_bound, hipStream_t st, const uint64_t* gate = nullptr);
+// The delivery word of every pair (deliver.h; emqx_session:handle_dispatch/3):
+// launch_dispatch_count with ppub != null is a second kernel that also stores
+// each slot's topic index (slots entries); launch_dispatch_emit_opts is a
+// second emit kernel that reads sv.opt beside sv.pool and writes
+// sub_deliver[p] beside sub_id[p].  ppub == null: slot i belongs to publish i
+// (launch_dispatch_lookup's geometry).  pub_flags / pub_from: n device words
+// each (pub_from may be null).  Calls without options launch neither.
+hipError_t launch_dispatch_emit_opts(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
+                                     const uint32_t* to, const uint32_t* ppub, const uint32_t* pub_flags,
+                                     const uint32_t* pub_from, uint32_t flags, uint32_t* sub_to, uint32_t* sub_id,
+                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st);
 
 // emqx_shared_sub:dispatch/3 member pick (share.hip) over the same deliveries
 // CSR and slot geometry as launch_dispatch_count.

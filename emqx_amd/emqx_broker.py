@@ -5,11 +5,15 @@ subscribers/1) and publish/1 runs on the GPU end to end (trie walk, route
 expansion, aggre and the subscriber fan-out, dispatch.hip).
 
     subscribe(Topic, Sub[, Group])     handle_cast #subscribe :332-345: insert_subscriber/3
-                                       :398-405, then emqx_router:add_route(Topic, dest(Group))
+                                       :398-405, then emqx_router:add_route(Topic, dest(Group));
+                                       with opts: do_subscribe/4 :407-410, the emqx_suboption entry
+    get_subopts / set_subopts          :279-291 over the entries the engine keeps (qos, nl, rap, subid)
     unsubscribe(Topic, Sub[, Group])   handle_cast #unsubscribe :347-358: delete_object :414,
                                        then del_route when ets:member(?SUBSCRIBER, Topic) is false
     subscribers(Topic)                 :245-247 -> [Sub | {share, Group, Sub}] in bag order
-    publish_many(Topics)               publish/1 :148-157 per topic: route(aggre(match_routes(T)))
+    publish_many(Topics[, Msgs])       publish/1 :148-157 per topic: route(aggre(match_routes(T)));
+                                       with msgs, every pair with the outcome of the session's
+                                       handle_dispatch/3 (src/emqx_session.erl:667-684, 797-819)
     publish_shared_many(Topics, ...)   the same with route/2's $share clause :187-189: the member
                                        emqx_shared_sub:dispatch/3 picks for every {To, Group} delivery
     dispatch_many(Tos)                 dispatch/2 :218-238 as a remote node's forward/3 calls it
@@ -44,6 +48,33 @@ class SharedPublished(Published):
         return self
 
 
+def pack_subopts(opts) -> int:
+    """{qos, nl, rap, subid} (missing keys: ?DEFAULT_SUBOPTS, no subid) -> the engine's option word"""
+    qos, subid = int(opts.get("qos", 0)), opts.get("subid")
+    if qos not in (0, 1, 2) or not (subid is None or 1 <= int(subid) < (1 << 28)):
+        raise ValueError("subopts: qos 0..2, subid 1..2^28-1")
+    return (qos | (Engine.SUBOPT_NL if opts.get("nl") else 0) | (Engine.SUBOPT_RAP if opts.get("rap") else 0)
+            | (int(subid or 0) << 4))
+
+
+def unpack_subopts(word: int):
+    return {"qos": word & 3, "nl": (word >> 2) & 1, "rap": (word >> 3) & 1, "subid": (word >> 4) or None}
+
+
+def pack_msgs(msgs):
+    """[(qos, retain, retained, from_sub | None)] -> (pub_flags, pub_from)"""
+    pf = [int(q) | (Engine.MSG_RETAIN if r else 0) | (Engine.MSG_RETAINED if rd else 0) for q, r, rd, _ in msgs]
+    fr = [Engine.NO_SUBSCRIBER if f is None else int(f) for _, _, _, f in msgs]
+    return pf, fr
+
+
+def unpack_deliver(word: int):
+    """a delivery word -> None (dropped by no-local) or (qos, retain, subid | None)"""
+    if word & Engine.DELIVER_DROP:
+        return None
+    return (word & 3, (word >> 2) & 1, (word >> 4) or None)
+
+
 class Broker:
     def __init__(self, engine: Engine, router: Router):
         self.engine = engine
@@ -56,8 +87,15 @@ class Broker:
         return self.router.node if group is None else (group, self.router.node)
 
     # handle_cast({From, #subscribe{}}) — :332-345
-    def subscribe(self, topic: bytes, sub: int, group=None):
-        self.engine.sub_add(topic, sub, None if group is None else _key(group))
+    # opts {qos, nl, rap, subid}: do_subscribe/4 :407-410 (the emqx_suboption
+    # entry, written even when the bag already held the plain entry); None:
+    # insert_subscriber/3 alone, no entry
+    def subscribe(self, topic: bytes, sub: int, group=None, opts=None):
+        g = None if group is None else _key(group)
+        if opts is None:
+            self.engine.sub_add(topic, sub, g)
+        else:
+            self.engine.sub_add_opts(topic, sub, pack_subopts(opts), g)
         self.shared.subscribe(group, topic, sub)          # :394
         self.router.add_route(topic, self._dest(group))
         return "ok"
@@ -69,6 +107,34 @@ class Broker:
         if left == 0:                      # ets:member(?SUBSCRIBER, Topic) -> false
             self.router.del_route(topic, self._dest(group))
         return "ok"
+
+    # get_subopts/2 — :279-283 ([] -> None)
+    def get_subopts(self, topic: bytes, sub: int):
+        w = self.engine.sub_get_opts(topic, sub)
+        return None if w is None else unpack_subopts(w)
+
+    # set_subopts/3 — :285-291: maps:merge over the keys given; False without an entry
+    def set_subopts(self, topic: bytes, sub: int, opts) -> bool:
+        mask = value = 0
+        if "qos" in opts:
+            mask, value = mask | 3, value | pack_subopts({"qos": opts["qos"]})
+        if "nl" in opts:
+            mask, value = mask | Engine.SUBOPT_NL, value | (Engine.SUBOPT_NL if opts["nl"] else 0)
+        if "rap" in opts:
+            mask, value = mask | Engine.SUBOPT_RAP, value | (Engine.SUBOPT_RAP if opts["rap"] else 0)
+        if "subid" in opts:
+            mask, value = mask | 0xFFFFFFF0, value | (pack_subopts({"subid": opts["subid"]}) & 0xFFFFFFF0)
+        return self.engine.sub_set_opts(topic, sub, mask, value)
+
+    @staticmethod
+    def _deliver(msgs, n, upgrade_qos):
+        if msgs is None:
+            return None
+        msgs = list(msgs)
+        if len(msgs) != n:
+            raise ValueError("msgs: one (qos, retain, retained, from_sub) per entry")
+        pf, fr = pack_msgs(msgs)
+        return pf, fr, Engine.DELIVER_UPGRADE_QOS if upgrade_qos else 0
 
     # subscribers/1 — :245-247
     def subscribers(self, topic: bytes):
@@ -87,24 +153,32 @@ class Broker:
     def publish(self, topic: bytes):
         return self.publish_many([topic])[0]
 
-    def publish_many(self, topics):
+    def publish_many(self, topics, msgs=None, upgrade_qos=False):
         """one device batch for all topics -> [Published(deliveries, pairs)]:
-        deliveries in aggre's order, pairs = [(To, Sub)] in dispatch order"""
+        deliveries in aggre's order, pairs = [(To, Sub)] in dispatch order.
+        msgs[i] = (qos, retain, retained, from_sub | None) of publish i: pairs =
+        [(To, Sub, None | (qos, retain, subid | None))], None = dropped by
+        no-local; upgrade_qos: the sessions' zone setting, for the whole batch"""
         topics = list(topics)
         buf, off = pack(topics)
-        return self._published(topics, self.engine.match_dispatch_batch(buf, off), None)
+        dv = self._deliver(msgs, len(topics), upgrade_qos)
+        out = self.engine.match_dispatch_batch(buf, off, deliver=dv)
+        return self._published(topics, out[:9], None, out[9] if dv else None)
 
-    def publish_shared_many(self, topics, strategy=None, keys=None):
+    def publish_shared_many(self, topics, strategy=None, keys=None, msgs=None, upgrade_qos=False):
         """publish_many with the $share clause: Published.picks = [(To, Group,
         member | None)] per $share delivery.  strategy: "round_robin", or
         "hash" / "random" / "keyed" / "sticky" with keys = one u32 per topic
-        (erlang:phash2(ClientId), or a uniform draw); default: self.shared.strategy"""
+        (erlang:phash2(ClientId), or a uniform draw); default: self.shared.strategy.
+        msgs / upgrade_qos: as publish_many (the picks carry no option word)"""
         topics = list(topics)
         buf, off = pack(topics)
-        out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys)
-        return self._published(topics, out[:9], out[9])
+        dv = self._deliver(msgs, len(topics), upgrade_qos)
+        out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys,
+                                              deliver=dv)
+        return self._published(topics, out[:9], out[9], out[10] if dv else None)
 
-    def _published(self, topics, out, pick):
+    def _published(self, topics, out, pick, words=None):
         counts, offs, to, tg, nd, scount, soff, sto, sid = out
         names, tnames, res = {}, {}, []
 
@@ -129,6 +203,8 @@ class Broker:
                     picks.append((dels[-1].to, tnames[g][1], None if m == Engine.NO_MEMBER else m))
             a = int(soff[t])
             pairs = [(name_of(int(sto[k]), topic), int(sid[k])) for k in range(a, a + int(scount[t]))]
+            if words is not None:
+                pairs = [pr + (unpack_deliver(int(words[a + k])),) for k, pr in enumerate(pairs)]
             res.append(Published(dels, pairs) if pick is None else SharedPublished(dels, pairs, picks))
         return res
 
@@ -174,10 +250,18 @@ class Broker:
         return [(p, tos[i], res[i][0], list(res[i][1])) for p, i in rows]
 
     # dispatch/2 — :218-238
-    def dispatch_many(self, tos):
+    def dispatch_many(self, tos, msgs=None, upgrade_qos=False):
         """[(Count, [Sub])] per To (given by its bytes): Count counts shared
-        entries too, the list holds the plain subscribers in bag order"""
+        entries too, the list holds the plain subscribers in bag order.
+        msgs[i] = the message forwarded with To i, as publish_many's (a To may
+        be listed once per message): the lists hold (Sub, None | (qos, retain,
+        subid | None))"""
         tos = list(tos)
         buf, off = pack(tos)
-        nd, soff, sid = self.engine.dispatch_batch(buf, off)
-        return [(int(nd[i]), [int(x) for x in sid[int(soff[i]):int(soff[i + 1])]]) for i in range(len(tos))]
+        dv = self._deliver(msgs, len(tos), upgrade_qos)
+        if dv is None:
+            nd, soff, sid = self.engine.dispatch_batch(buf, off)
+            return [(int(nd[i]), [int(x) for x in sid[int(soff[i]):int(soff[i + 1])]]) for i in range(len(tos))]
+        nd, soff, sid, words = self.engine.dispatch_batch(buf, off, deliver=dv)
+        return [(int(nd[i]), [(int(sid[k]), unpack_deliver(int(words[k])))
+                              for k in range(int(soff[i]), int(soff[i + 1]))]) for i in range(len(tos))]

@@ -471,6 +471,67 @@ class Engine:
     def sub_del_many(self, tbuf, toff, subs, gbuf=None, goff=None, shared=None):
         return self._sub_many(self.lib.tm_sub_del_batch, "tm_sub_del_batch", tbuf, toff, subs, gbuf, goff, shared)
 
+    # -- emqx_suboption: one option word per (topic, subscriber) ------------------
+    SUBOPT_NONE = L.TM_SUBOPT_NONE
+    SUBOPT_NL = L.TM_SUBOPT_NL
+    SUBOPT_RAP = L.TM_SUBOPT_RAP
+    MSG_RETAIN = L.TM_MSG_RETAIN
+    MSG_RETAINED = L.TM_MSG_RETAINED
+    DELIVER_DROP = L.TM_DELIVER_DROP
+    DELIVER_UPGRADE_QOS = L.TM_DELIVER_UPGRADE_QOS
+    NO_SUBSCRIBER = L.TM_NO_SUBSCRIBER
+
+    def sub_add_opts(self, topic: bytes, sub: int, opts: int, group=None):
+        """do_subscribe/4: sub_add, then the option word of (topic, sub) is written
+        (also when a plain entry suppressed the add)"""
+        return self._check(self.lib.tm_sub_add_opts(self.h, topic, len(topic), sub, group, len(group) if group else 0,
+                                                    opts), "tm_sub_add_opts")
+
+    def sub_add_opts_many(self, tbuf, toff, subs, opts, gbuf=None, goff=None, shared=None):
+        """sub_add_many with opts[i] for entry i"""
+        opts = np.ascontiguousarray(opts, dtype=np.uint32)
+        if len(opts) != len(toff) - 1:
+            raise ValueError("opts: one u32 per entry")
+
+        def fn(h, t, to, sb, g, go, sh, n):
+            return self.lib.tm_sub_add_opts_batch(h, t, to, sb, g, go, sh, _ptr(opts), n)
+        return self._sub_many(fn, "tm_sub_add_opts_batch", tbuf, toff, subs, gbuf, goff, shared)
+
+    def sub_set_opts(self, topic: bytes, sub: int, mask: int, value: int) -> bool:
+        """set_subopts/3: (old & ~mask) | (value & mask); False without an entry"""
+        found = ctypes.c_int()
+        self._check(self.lib.tm_sub_set_opts(self.h, topic, len(topic), sub, mask, value, ctypes.byref(found)),
+                    "tm_sub_set_opts")
+        return bool(found.value)
+
+    def sub_get_opts(self, topic: bytes, sub: int):
+        """get_subopts/2: the option word, None without an entry"""
+        w, found = ctypes.c_uint32(), ctypes.c_int()
+        self._check(self.lib.tm_sub_get_opts(self.h, topic, len(topic), sub, ctypes.byref(w), ctypes.byref(found)),
+                    "tm_sub_get_opts")
+        return int(w.value) if found.value else None
+
+    def deliver_word(self, opts: int, pub_flags: int, same_client: bool, flags: int = 0) -> int:
+        """tm_deliver_word: handle_dispatch/3 + run_dispatch_steps/3 for one pair"""
+        return int(self.lib.tm_deliver_word(opts, pub_flags, 1 if same_client else 0, flags))
+
+    @staticmethod
+    def _host_deliver(deliver, n):
+        """deliver=(pub_flags, pub_from | None, flags) -> (pub_flags, pub_from, flags) as u32 arrays"""
+        pf, fr, fl = deliver
+        pf = np.ascontiguousarray(pf, dtype=np.uint32)
+        if len(pf) != n:
+            raise ValueError("deliver: one pub_flags word per publish")
+        if fr is not None:
+            fr = np.ascontiguousarray(fr, dtype=np.uint32)
+            if len(fr) != n:
+                raise ValueError("deliver: one pub_from word per publish")
+        return pf, fr, int(fl)
+
+    @staticmethod
+    def _deliver_struct(pf, fr, fl, out):
+        return L.TmDeliver(pf, fr, fl, 0, out)
+
     def subscribers(self, topic: bytes):
         """subscribers/1: [(sub, group id or NO_GROUP)] in bag order"""
         n = ctypes.c_uint32()
@@ -506,15 +567,27 @@ class Engine:
         self.lib.tm_debug_check_subs.argtypes = [ctypes.c_void_p]
         return self._check(self.lib.tm_debug_check_subs(self.h), "tm_debug_check_subs")
 
-    def match_dispatch_batch(self, buf, off, out_cap=None, sub_cap=None):
+    def debug_sub_pool_stats(self):
+        """(pool entries, garbage, compactions, segment moves, largest segment
+        capacity) of the subscriber pool (diagnostic, tm_debug_sub_pool_stats)"""
+        out = (ctypes.c_uint64 * 5)()
+        self.lib.tm_debug_sub_pool_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.lib.tm_debug_sub_pool_stats(self.h, out), "tm_debug_sub_pool_stats")
+        return tuple(int(x) for x in out)
+
+    def match_dispatch_batch(self, buf, off, out_cap=None, sub_cap=None, deliver=None):
         """Host batch -> (counts u32[n], offsets u64[n+1], to, target, ndisp
         (one per delivery slot), sub_count u32[n], sub_off u64[n+1], sub_to,
         sub_id): publish/1's deliveries with the local dispatch.  out_cap /
         sub_cap None: retried at the needed sizes; given: one call
-        (TopicMatchError TM_ENOSPC when either is short)."""
+        (TopicMatchError TM_ENOSPC when either is short).
+        deliver=(pub_flags u32[n], pub_from u32[n] | None, flags): the tuple
+        gains sub_deliver, the delivery word of every pair."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         n = len(off) - 1
+        if deliver is not None:
+            pf, fr, fl = self._host_deliver(deliver, n)
         counts = np.zeros(max(n, 1), dtype=np.uint32)
         offs = np.zeros(n + 1, dtype=np.uint64)
         scount = np.zeros(max(n, 1), dtype=np.uint32)
@@ -525,9 +598,18 @@ class Engine:
             to, tg, nd = (np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(3))
             sto, sid = (np.zeros(max(scap, 1), dtype=np.uint32) for _ in range(2))
             needed, sneeded = ctypes.c_uint64(), ctypes.c_uint64()
-            rc = self.lib.tm_match_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs), _ptr(to),
-                                                  _ptr(tg), _ptr(nd), cap, ctypes.byref(needed), _ptr(scount),
-                                                  _ptr(soff), _ptr(sto), _ptr(sid), scap, ctypes.byref(sneeded))
+            if deliver is not None:
+                sdv = np.zeros(max(scap, 1), dtype=np.uint32)
+                dv = self._deliver_struct(_ptr(pf), _ptr(fr), fl, _ptr(sdv))
+                rc = self.lib.tm_match_dispatch_batch_opts(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs),
+                                                           _ptr(to), _ptr(tg), _ptr(nd), cap, ctypes.byref(needed),
+                                                           _ptr(scount), _ptr(soff), _ptr(sto), _ptr(sid), scap,
+                                                           ctypes.byref(sneeded), ctypes.byref(dv))
+            else:
+                rc = self.lib.tm_match_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs),
+                                                      _ptr(to), _ptr(tg), _ptr(nd), cap, ctypes.byref(needed),
+                                                      _ptr(scount), _ptr(soff), _ptr(sto), _ptr(sid), scap,
+                                                      ctypes.byref(sneeded))
             if rc == L.TM_ENOSPC and (out_cap is None or needed.value <= cap) and \
                     (sub_cap is None or sneeded.value <= scap):
                 cap = max(cap, int(needed.value))
@@ -540,11 +622,14 @@ class Engine:
                 raise e
             self._check(rc, "tm_match_dispatch_batch")
             k, sk = int(needed.value), int(sneeded.value)
-            return counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk]
+            res = (counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk])
+            return res if deliver is None else res + (sdv[:sk],)
 
     def match_dispatch_batch_device(self, d_bytes, d_off, n, topic_bytes, d_counts, d_offs, d_to, d_target, d_ndisp,
                                     out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap,
-                                    d_sub_total, stream=None):
+                                    d_sub_total, stream=None, deliver=None):
+        """deliver=(d_pub_flags, d_pub_from | None, flags, d_sub_deliver): device
+        arrays; d_sub_deliver is written parallel to d_sub_id"""
         def p(x):
             if x is None:
                 return None
@@ -552,30 +637,48 @@ class Engine:
         st = None
         if stream is not None:
             st = ctypes.c_void_p(L.stream_handle(stream))
+        if deliver is not None:
+            dv = self._deliver_struct(p(deliver[0]), p(deliver[1]), int(deliver[2]), p(deliver[3]))
+            rc = self.lib.tm_match_dispatch_batch_opts_device(
+                self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts), p(d_offs), p(d_to), p(d_target),
+                p(d_ndisp), out_cap, p(d_total), p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,
+                p(d_sub_total), ctypes.byref(dv), st)
+            return self._check(rc, "tm_match_dispatch_batch_opts_device")
         rc = self.lib.tm_match_dispatch_batch_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts),
                                                      p(d_offs), p(d_to), p(d_target), p(d_ndisp), out_cap, p(d_total),
                                                      p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,
                                                      p(d_sub_total), st)
         return self._check(rc, "tm_match_dispatch_batch_device")
 
-    def dispatch_batch(self, buf, off, cap=None):
-        """dispatch/2 by To bytes -> (ndisp u32[n], sub_off u64[n+1], sub_id)"""
+    def dispatch_batch(self, buf, off, cap=None, deliver=None):
+        """dispatch/2 by To bytes -> (ndisp u32[n], sub_off u64[n+1], sub_id);
+        deliver=(pub_flags, pub_from | None, flags), entry i = (To i, message
+        i): plus sub_deliver"""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         n = len(off) - 1
+        if deliver is not None:
+            pf, fr, fl = self._host_deliver(deliver, n)
         nd = np.zeros(max(n, 1), dtype=np.uint32)
         soff = np.zeros(n + 1, dtype=np.uint64)
         c = 1 << 16 if cap is None else cap
         while True:
             sid = np.zeros(max(c, 1), dtype=np.uint32)
             needed = ctypes.c_uint64()
-            rc = self.lib.tm_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(nd), _ptr(soff), _ptr(sid), c,
-                                            ctypes.byref(needed))
+            if deliver is not None:
+                sdv = np.zeros(max(c, 1), dtype=np.uint32)
+                dv = self._deliver_struct(_ptr(pf), _ptr(fr), fl, _ptr(sdv))
+                rc = self.lib.tm_dispatch_batch_opts(self.h, _ptr(buf), _ptr(off), n, _ptr(nd), _ptr(soff), _ptr(sid),
+                                                     c, ctypes.byref(needed), ctypes.byref(dv))
+            else:
+                rc = self.lib.tm_dispatch_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(nd), _ptr(soff), _ptr(sid), c,
+                                                ctypes.byref(needed))
             if rc == L.TM_ENOSPC and cap is None:
                 c = int(needed.value)
                 continue
             self._check(rc, "tm_dispatch_batch")
-            return nd[:n], soff, sid[: int(needed.value)]
+            res = (nd[:n], soff, sid[: int(needed.value)])
+            return res if deliver is None else res + (sdv[: int(needed.value)],)
 
     # -- emqx_broker:forward/3, the sending half (forward.hip) ----------------------
     FORWARD_HDR_WORDS = 4
@@ -692,15 +795,18 @@ class Engine:
         self.lib.tm_debug_check_shares.argtypes = [ctypes.c_void_p]
         return self._check(self.lib.tm_debug_check_shares(self.h), "tm_debug_check_shares")
 
-    def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None):
+    def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None, deliver=None):
         """match_dispatch_batch's tuple plus pick u32 (one per delivery slot):
         the member picked for a $share delivery, NO_MEMBER otherwise.
         strategy SHARE_KEYED and SHARE_STICKY take keys (u32[n]);
         SHARE_ROUND_ROBIN none.  A short out_cap / sub_cap: as
-        match_dispatch_batch (no cursor moves, no sticky entry is stored)."""
+        match_dispatch_batch (no cursor moves, no sticky entry is stored).
+        deliver: as match_dispatch_batch, sub_deliver goes last."""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         n = len(off) - 1
+        if deliver is not None:
+            pf, fr, fl = self._host_deliver(deliver, n)
         if keys is not None:
             keys = np.ascontiguousarray(keys, dtype=np.uint32)
             if len(keys) != n:
@@ -715,10 +821,19 @@ class Engine:
             to, tg, nd, pick = (np.zeros(max(cap, 1), dtype=np.uint32) for _ in range(4))
             sto, sid = (np.zeros(max(scap, 1), dtype=np.uint32) for _ in range(2))
             needed, sneeded = ctypes.c_uint64(), ctypes.c_uint64()
-            rc = self.lib.tm_match_publish_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs), _ptr(to),
-                                                 _ptr(tg), _ptr(nd), cap, ctypes.byref(needed), _ptr(scount),
-                                                 _ptr(soff), _ptr(sto), _ptr(sid), scap, ctypes.byref(sneeded),
-                                                 strategy, _ptr(keys), _ptr(pick))
+            if deliver is not None:
+                sdv = np.zeros(max(scap, 1), dtype=np.uint32)
+                dv = self._deliver_struct(_ptr(pf), _ptr(fr), fl, _ptr(sdv))
+                rc = self.lib.tm_match_publish_batch_opts(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs),
+                                                          _ptr(to), _ptr(tg), _ptr(nd), cap, ctypes.byref(needed),
+                                                          _ptr(scount), _ptr(soff), _ptr(sto), _ptr(sid), scap,
+                                                          ctypes.byref(sneeded), strategy, _ptr(keys), _ptr(pick),
+                                                          ctypes.byref(dv))
+            else:
+                rc = self.lib.tm_match_publish_batch(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs),
+                                                     _ptr(to), _ptr(tg), _ptr(nd), cap, ctypes.byref(needed),
+                                                     _ptr(scount), _ptr(soff), _ptr(sto), _ptr(sid), scap,
+                                                     ctypes.byref(sneeded), strategy, _ptr(keys), _ptr(pick))
             if rc == L.TM_ENOSPC and (out_cap is None or needed.value <= cap) and \
                     (sub_cap is None or sneeded.value <= scap):
                 cap = max(cap, int(needed.value))
@@ -731,11 +846,13 @@ class Engine:
                 raise e
             self._check(rc, "tm_match_publish_batch")
             k, sk = int(needed.value), int(sneeded.value)
-            return counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk], pick[:k]
+            res = (counts[:n], offs, to[:k], tg[:k], nd[:k], scount[:n], soff, sto[:sk], sid[:sk], pick[:k])
+            return res if deliver is None else res + (sdv[:sk],)
 
     def match_publish_batch_device(self, d_bytes, d_off, n, topic_bytes, d_counts, d_offs, d_to, d_target, d_ndisp,
                                    out_cap, d_total, d_sub_count, d_sub_off, d_sub_to, d_sub_id, sub_cap,
-                                   d_sub_total, strategy, d_keys, d_pick, stream=None):
+                                   d_sub_total, strategy, d_keys, d_pick, stream=None, deliver=None):
+        """deliver: as match_dispatch_batch_device"""
         def p(x):
             if x is None:
                 return None
@@ -743,6 +860,13 @@ class Engine:
         st = None
         if stream is not None:
             st = ctypes.c_void_p(L.stream_handle(stream))
+        if deliver is not None:
+            dv = self._deliver_struct(p(deliver[0]), p(deliver[1]), int(deliver[2]), p(deliver[3]))
+            rc = self.lib.tm_match_publish_batch_opts_device(
+                self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts), p(d_offs), p(d_to), p(d_target),
+                p(d_ndisp), out_cap, p(d_total), p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,
+                p(d_sub_total), strategy, p(d_keys), p(d_pick), ctypes.byref(dv), st)
+            return self._check(rc, "tm_match_publish_batch_opts_device")
         rc = self.lib.tm_match_publish_batch_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, p(d_counts),
                                                     p(d_offs), p(d_to), p(d_target), p(d_ndisp), out_cap, p(d_total),
                                                     p(d_sub_count), p(d_sub_off), p(d_sub_to), p(d_sub_id), sub_cap,

@@ -623,6 +623,125 @@ int tm_match_dispatch_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, c
 int tm_dispatch_batch(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
                       uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed);
 
+/* ---- subscription options: emqx_suboption and the per-pair delivery word -------
+ * (emqx_amd/csrc/deliver.h, dispatch.hip)  The broker's third table,
+ * emqx_suboption (src/emqx_broker.erl:45), is keyed {Topic, Subscriber} and
+ * written by the do_subscribe/4 / do_unsubscribe/3 (:407-415) that write the
+ * emqx_subscriber bag.  The first thing a session does with a dispatched
+ * (To, subscriber) pair is emqx_session:handle_dispatch/3
+ * (src/emqx_session.erl:667-684): it looks To up in the subscription's
+ * options and runs run_dispatch_steps/3 (:797-819).  The engine keeps one
+ * option entry per (topic, subscriber) -- shared by the plain entry and every
+ * shared entry of that subscriber -- and returns the outcome of those steps
+ * per pair.
+ *
+ * An option entry is a packed u32 (?DEFAULT_SUBOPTS, include/emqx_mqtt.hrl:201-206):
+ *   bits 0-1   qos 0..2 (3 never appears in a stored entry)
+ *   bit  2     nl   TM_SUBOPT_NL
+ *   bit  3     rap  TM_SUBOPT_RAP
+ *   bits 4-31  subid, the MQTT Subscription Identifier 1..2^28-1 (0 = none, :675)
+ * TM_SUBOPT_NONE (a qos field of 3) means "no option entry": the `error`
+ * clause of handle_dispatch/3 (:679-680).  rh, rc and share are NOT stored:
+ * dispatch never reads them; the full option map stays with the caller. */
+#define TM_SUBOPT_NONE   3u
+#define TM_SUBOPT_NL     4u
+#define TM_SUBOPT_RAP    8u
+#define TM_SUBOPT_SUBID_SHIFT 4
+
+/* do_subscribe/4 (:407-410) without the emqx_subscription table: the bag
+ * effect is exactly tm_sub_add's, then the option entry of (topic, sub) is
+ * written -- also when a plain entry suppressed the bag add (:410 runs
+ * unconditionally and overwrites).  TM_EINVAL when (opts & 3) == 3.
+ * tm_sub_add / tm_sub_add_batch stay insert_subscriber/3 alone: they write no
+ * option entry, and a pair without one is delivered unchanged (:679-680). */
+int tm_sub_add_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, const uint8_t* group,
+                    uint32_t glen, uint32_t opts);
+/* laid out as tm_sub_add_batch, entry i with opts[i] */
+int tm_sub_add_opts_batch(tm_engine* e, const uint8_t* topics, const uint64_t* topic_off, const uint32_t* subs,
+                          const uint8_t* groups, const uint64_t* group_off, const uint8_t* shared,
+                          const uint32_t* opts, uint32_t n);
+/* tm_sub_del / tm_sub_del_batch additionally erase the option entry of
+ * (topic, sub) -- ets:delete(emqx_suboption, {Topic, Subscriber}), :415 --
+ * whatever the group and whether or not an object went; their return values
+ * and bag effects are as documented above. */
+
+/* set_subopts/3 (:285-291): maps:merge(Old, Opts) is (old & ~mask) | (value &
+ * mask).  Without an entry *found = 0 and nothing changes ([] -> false), else
+ * *found = 1 (found may be NULL).  A result whose qos field is 3 returns
+ * TM_EINVAL and changes nothing. */
+int tm_sub_set_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, uint32_t mask, uint32_t value,
+                    int* found);
+/* get_subopts/2 (:279-283): *opts = the entry, or TM_SUBOPT_NONE with *found =
+ * 0 when there is none (found may be NULL). */
+int tm_sub_get_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t sub, uint32_t* opts, int* found);
+
+/* The delivery word.  Per publish t of a batch:
+ *   pub_flags[t]  bits 0-1 PubQoS, TM_MSG_RETAIN the message's retain flag,
+ *                 TM_MSG_RETAINED headers.retained =:= true
+ *   pub_from[t]   the subscriber id of the publishing client's own session, or
+ *                 TM_NO_SUBSCRIBER (a NULL array: none for every publish)
+ * and one call flag, TM_DELIVER_UPGRADE_QOS (the reference reads upgrade_qos
+ * per session from its zone, :803, :810; a call takes it for the whole batch).
+ * sub_deliver[p] is parallel to sub_id[p], under the same sub_cap drop rule:
+ *   bits 0-1 delivered QoS, bit 2 retain flag, bit 3 TM_DELIVER_DROP (dropped by
+ *   no-local: the word is then exactly 8), bits 4-31 subid
+ * A dropped pair stays in the pair arrays; every other output is element for
+ * element what the call without options returns.  $share picks get no word
+ * (the caller looks a picked member's options up itself).
+ *
+ * The struct lives on the host; its pointers are host pointers in the host
+ * forms and device pointers in the *_device forms.  `reserved` must be 0. */
+#define TM_MSG_RETAIN           4u
+#define TM_MSG_RETAINED         8u
+#define TM_DELIVER_DROP         8u
+#define TM_DELIVER_UPGRADE_QOS  1u
+#define TM_NO_SUBSCRIBER        0xFFFFFFFFu
+typedef struct tm_deliver {
+    const uint32_t* pub_flags;
+    const uint32_t* pub_from;
+    uint32_t        flags;
+    uint32_t        reserved;
+    uint32_t*       sub_deliver;
+} tm_deliver;
+
+/* handle_dispatch/3 + run_dispatch_steps/3 for one pair, the pure function
+ * the emit kernel runs (for paths the engine does not cover):
+ *   (opts & 3) == 3              -> (pf & 3) | (pf & TM_MSG_RETAIN)           :679-680
+ *   (opts & NL) && same_client   -> TM_DELIVER_DROP                           :799-800
+ *   qos    = upgrade ? max(SubQoS, PubQoS) : min(SubQoS, PubQoS)              :803-811
+ *   retain = RETAINED ? 1 : (opts & RAP) ? the retain flag : 0                :812-817
+ *   word   = qos | retain << 2 | (opts & 0xFFFFFFF0)                          :818-819
+ * same_client is pub_from[t] != TM_NO_SUBSCRIBER && sub_id[p] == pub_from[t].
+ * The Topic-Alias test (:671-673), unset_flag(dup) and maybe_ack stay the
+ * caller's. */
+uint32_t tm_deliver_word(uint32_t opts, uint32_t pub_flags, int same_client, uint32_t flags);
+
+/* tm_match_dispatch_batch / tm_match_publish_batch / tm_dispatch_batch and
+ * their device forms, each with the delivery words: the existing call plus one
+ * tm_deliver.  tm_dispatch_batch_opts is the receiving half of forward/3
+ * (:209-216): entry i is (To i, message i) and a To may be listed once per
+ * message; a forwarded message's publisher is never a local subscriber, so
+ * its callers pass TM_NO_SUBSCRIBER (or a NULL pub_from).
+ * TM_EINVAL, besides the plain call's: a NULL deliver, a NULL pub_flags with
+ * n > 0, a NULL sub_deliver with sub_cap > 0, an unknown flag; and in the host
+ * forms a pub_flags entry whose QoS is 3.  The device forms do NOT validate
+ * pub_flags (the words are on the device): a PubQoS of 3 gives a word whose
+ * QoS field is min / max of 3 and the subscription's. */
+int tm_match_dispatch_batch_opts(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                                 uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                                 uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                                 uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                                 uint64_t* sub_needed, const tm_deliver* deliver);
+int tm_match_dispatch_batch_opts_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
+                                        uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count, uint64_t* d_out_off,
+                                        uint32_t* d_out_to, uint32_t* d_out_target, uint32_t* d_out_ndisp,
+                                        uint64_t out_cap, uint64_t* d_total, uint32_t* d_sub_count,
+                                        uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id, uint64_t sub_cap,
+                                        uint64_t* d_sub_total, const tm_deliver* deliver, void* hip_stream);
+int tm_dispatch_batch_opts(tm_engine* e, const uint8_t* to_bytes, const uint64_t* to_off, uint32_t n, uint32_t* ndisp,
+                           uint64_t* sub_off, uint32_t* sub_id, uint64_t cap, uint64_t* needed,
+                           const tm_deliver* deliver);
+
 /* ---- shared-subscription dispatch: the $share member table and the pick -------
  * (emqx_amd/csrc/share.hip)  The third clause of route/2
  * (src/emqx_broker.erl:187-189) hands a {To, Group} delivery to
@@ -742,6 +861,22 @@ int tm_match_publish_batch_device(tm_engine* e, const uint8_t* d_topic_bytes, co
                                   uint64_t* d_total, uint32_t* d_sub_count, uint64_t* d_sub_off, uint32_t* d_sub_to,
                                   uint32_t* d_sub_id, uint64_t sub_cap, uint64_t* d_sub_total, uint32_t strategy,
                                   const uint32_t* d_pub_key, uint32_t* d_out_pick, void* hip_stream);
+
+/* The two calls above with the delivery words of the (To, subscriber) pairs
+ * (see tm_deliver); the picks are those of the call without options. */
+int tm_match_publish_batch_opts(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                                uint32_t* out_count, uint64_t* out_off, uint32_t* out_to, uint32_t* out_target,
+                                uint32_t* out_ndisp, uint64_t out_cap, uint64_t* out_needed, uint32_t* sub_count,
+                                uint64_t* sub_off, uint32_t* sub_to, uint32_t* sub_id, uint64_t sub_cap,
+                                uint64_t* sub_needed, uint32_t strategy, const uint32_t* pub_key, uint32_t* out_pick,
+                                const tm_deliver* deliver);
+int tm_match_publish_batch_opts_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off,
+                                       uint32_t n, uint64_t topic_bytes, uint32_t* d_out_count, uint64_t* d_out_off,
+                                       uint32_t* d_out_to, uint32_t* d_out_target, uint32_t* d_out_ndisp,
+                                       uint64_t out_cap, uint64_t* d_total, uint32_t* d_sub_count,
+                                       uint64_t* d_sub_off, uint32_t* d_sub_to, uint32_t* d_sub_id, uint64_t sub_cap,
+                                       uint64_t* d_sub_total, uint32_t strategy, const uint32_t* d_pub_key,
+                                       uint32_t* d_out_pick, const tm_deliver* deliver, void* hip_stream);
 
 /* A publish batch's results as one dense record stream (emqx_amd/csrc/pack.hip),
  * over what tm_match_publish_batch_device (or tm_match_dispatch_batch_device,
