@@ -118,3 +118,16 @@ san_subopts: $(LIBOUT)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_subopts_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_subopts
 	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_subopts
 .PHONY: san_subopts
+
+# the member option pool (the emqx_suboption word of every $share member,
+# refreshed by the option calls and the share calls in either order, through
+# growth, deletes, member_down and compaction) and the argument checks of the
+# pick-word, pack and stream calls with options, under AddressSanitizer + UBSan
+# on a host-only engine (tools/san_pickwords.cpp); the kernels linked as built
+# and never run.
+san_pickwords: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c tools/san_pickwords.cpp -o $(BUILD)/san_pickwords_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_pickwords_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_pickwords
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_pickwords
+.PHONY: san_pickwords

@@ -108,6 +108,7 @@ class TmDeliver(ctypes.Structure):
 
 
 TM_ROUTE_ALL = 0xFFFFFFFF
+TM_NO_WORD = 0xFFFFFFFF   # pick word: no pick, or a picked member outside its set
 TM_COMM_ID_BYTES = 128
 TM_BATCHER_ROUTES = 1
 TM_BATCHER_DELIVERIES = 2
@@ -117,6 +118,8 @@ TM_BATCHER_PUBLISH = 16
 TM_BATCHER_ROUND_ROBIN = 32
 TM_BATCHER_STREAM = 64
 TM_BATCHER_STICKY = 128
+TM_BATCHER_OPTS = 256
+TM_BATCHER_UPGRADE_QOS = 512
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
 
@@ -132,6 +135,9 @@ class TmPair(ctypes.Structure):
 
 PUBLISH_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(TmDelivery),
                                    ctypes.c_uint32, ctypes.POINTER(TmPair), ctypes.c_uint32)
+PUBLISH_OPTS_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                        ctypes.POINTER(TmDelivery), c_u32p, ctypes.c_uint32, ctypes.POINTER(TmPair),
+                                        c_u32p, ctypes.c_uint32)
 
 # (name, restype, argtypes) — every symbol include/topicmatch.h declares
 SIGNATURES = [
@@ -355,6 +361,17 @@ SIGNATURES = [
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                        ctypes.c_uint64]),
+    ("tm_share_pick_words_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                  ctypes.POINTER(TmDeliver), ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_share_pick_words", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                           ctypes.POINTER(TmDeliver), ctypes.c_void_p]),
+    ("tm_debug_share_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                           ctypes.POINTER(ctypes.c_uint32)]),
     ("tm_share_cursors_open", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_share_cursors_close", None, [ctypes.c_void_p]),
     ("tm_publish_stream_workspace_bytes", ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
@@ -364,6 +381,22 @@ SIGNATURES = [
                                                 ctypes.POINTER(TmPublishCaps), ctypes.c_void_p, ctypes.c_uint64,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_publish_stream_opts_workspace_bytes", ctypes.c_uint64, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                                                 ctypes.POINTER(TmPublishCaps)]),
+    ("tm_publish_stream_opts_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TmPublishCaps),
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.POINTER(TmDeliver), ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
+    ("tm_publish_pack_opts_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p]),
     ("tm_share_pick_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
@@ -373,6 +406,9 @@ SIGNATURES = [
                                          c_u64p]),
     ("tm_batcher_submit_publish", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
                                                  PUBLISH_DONE_FN, ctypes.c_void_p, c_u64p]),
+    ("tm_batcher_submit_publish_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                      PUBLISH_OPTS_DONE_FN, ctypes.c_void_p, c_u64p]),
     ("tm_batcher_flush", ctypes.c_int, [ctypes.c_void_p]),
     ("tm_batcher_get_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats)]),
     ("tm_batcher_get_stats2", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats), ctypes.c_uint32,

@@ -9,7 +9,9 @@ their dispatch Count and $share pick, and the (To, subscriber) pairs; with
 round_robin=True the picks are the reference's default strategy, each lane a
 publisher process with its own cursors (sticky=True: `sticky` picks, a lane
 likewise a publisher with its own entries), and stream=True runs the keyed picks
-through tm_publish_stream_device too (an A/B switch).  This is the NIF's path: the callback there builds
+through tm_publish_stream_device too (an A/B switch); opts=True
+(submit_publish_opts) brings the delivery word of every pair and of every
+$share pick with the records.  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
 import itertools
@@ -22,13 +24,14 @@ from . import _lib as L
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
                  lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0, round_robin=False,
-                 stream=False, sticky=False):
+                 stream=False, sticky=False, opts=False, upgrade_qos=False):
         self.engine = engine
         self.lib = engine.lib
         flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
             (L.TM_BATCHER_PUBLISH if publish else 0) | (L.TM_BATCHER_EAGER if eager else 0) | \
             (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0) | \
-            (L.TM_BATCHER_STICKY if sticky else 0)
+            (L.TM_BATCHER_STICKY if sticky else 0) | (L.TM_BATCHER_OPTS if opts else 0) | \
+            (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
         rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))
@@ -40,6 +43,7 @@ class Batcher:
         self._keys = itertools.count(1)
         self._done = L.DONE_FN(self._on_done)     # one trampoline, kept alive with the batcher
         self._pdone = L.PUBLISH_DONE_FN(self._on_publish_done)
+        self._odone = L.PUBLISH_OPTS_DONE_FN(self._on_publish_opts_done)
 
     def _on_done(self, ctx, ticket, status, ids, dests, n):
         cb = self._cbs.pop(ctx)
@@ -87,6 +91,36 @@ class Batcher:
         if rc != L.TM_OK:
             del self._cbs[k]
             raise L.TopicMatchError(rc, "tm_batcher_submit_publish")
+        return t.value
+
+    def _on_publish_opts_done(self, ctx, ticket, status, deliv, pick_word, n_deliv, pairs, pair_word, n_pairs):
+        cb = self._cbs.pop(ctx)
+        if status != L.TM_OK:
+            cb(status, None, None, None, None)
+            return
+        # records and words are valid only during the callback: copied out here
+        def rows(ptr, n, width):
+            if not n:
+                return []
+            raw = ctypes.string_at(ctypes.addressof(ptr.contents), n * width * 4)
+            return list(map(tuple, np.frombuffer(raw, dtype=np.uint32).reshape(n, width).tolist()))
+        cb(status, rows(deliv, n_deliv, 4), [pick_word[i] for i in range(n_deliv)], rows(pairs, n_pairs, 2),
+           [pair_word[i] for i in range(n_pairs)])
+
+    def submit_publish_opts(self, topic: bytes, key: int, pub_flags: int, pub_from: int, callback):
+        """opts=True batchers: callback(status, deliveries, pick_words, pairs,
+        pair_words) runs on the worker thread; pick_words[i] is the delivery
+        word of deliveries[i]'s pick (NO_WORD without one, and for a stuck
+        member outside its set), pair_words[i] that of pairs[i]; all None on
+        error.  pub_flags / pub_from: the publish's words (tm_deliver)"""
+        t = ctypes.c_uint64()
+        k = next(self._keys)
+        self._cbs[k] = callback
+        rc = self.lib.tm_batcher_submit_publish_opts(self.h, topic, len(topic), key & 0xFFFFFFFF, pub_flags,
+                                                     pub_from & 0xFFFFFFFF, self._odone, k, ctypes.byref(t))
+        if rc != L.TM_OK:
+            del self._cbs[k]
+            raise L.TopicMatchError(rc, "tm_batcher_submit_publish_opts")
         return t.value
 
     def flush(self):

@@ -35,6 +35,13 @@
 // stateless, so a batch whose lists outgrew the lane's buffers is simply run
 // again; round robin is not offered because that rerun would advance the set
 // cursors twice.
+//
+// TM_BATCHER_OPTS adds the session side of every send (emqx_session:
+// handle_dispatch/3, src/emqx_session.erl:667-684): a submit also brings the
+// publish's pub_flags and pub_from, which go up with the keys, the lane runs
+// tm_publish_stream_opts_device whatever the strategy, and the block that comes
+// back ends with the pick words and the pair words, which the callbacks read in
+// place beside the records.
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
@@ -65,6 +72,7 @@ struct Req {
     union {
         tm_batch_done_fn fn;
         tm_publish_done_fn pfn;   // TM_BATCHER_PUBLISH
+        tm_publish_opts_done_fn ofn;   // TM_BATCHER_OPTS
     };
     void* ctx;
     uint64_t ticket;
@@ -77,6 +85,7 @@ struct Chunk {
     std::vector<uint32_t> lens;
     std::vector<Req> reqs;
     std::vector<uint32_t> keys;   // TM_BATCHER_PUBLISH: the pick key of each topic (else empty)
+    std::vector<uint32_t> pflags, pfrom;   // TM_BATCHER_OPTS: pub_flags and pub_from of each topic (else empty)
     size_t head = 0, bhead = 0;   // topics / bytes already taken
     size_t size() const { return lens.size() - head; }
     size_t nbytes() const { return bytes.size() - bhead; }
@@ -85,6 +94,8 @@ struct Chunk {
         lens.clear();
         reqs.clear();
         keys.clear();
+        pflags.clear();
+        pfrom.clear();
         head = bhead = 0;
     }
     void compact() {   // drop the taken prefix once it is the larger part
@@ -93,6 +104,10 @@ struct Chunk {
         lens.erase(lens.begin(), lens.begin() + head);
         reqs.erase(reqs.begin(), reqs.begin() + head);
         if (!keys.empty()) keys.erase(keys.begin(), keys.begin() + head);
+        if (!pflags.empty()) {
+            pflags.erase(pflags.begin(), pflags.begin() + head);
+            pfrom.erase(pfrom.begin(), pfrom.begin() + head);
+        }
         head = bhead = 0;
     }
 };
@@ -182,6 +197,8 @@ struct Lane {
     const uint64_t* r_soff = nullptr;
     const tm_delivery* r_deliv = nullptr;
     const tm_pair* r_pairs = nullptr;
+    const uint32_t* r_pickw = nullptr;   // TM_BATCHER_OPTS: the pick words (parallel to r_deliv) and the
+    const uint32_t* r_pairw = nullptr;   // pair words (parallel to r_pairs)
     double deliv_per_topic = 16.0, pairs_per_topic = 16.0;
     // TM_BATCHER_STREAM / TM_BATCHER_ROUND_ROBIN: tm_publish_stream_device's
     // workspace, the two further sizing estimates (match ids: ids_per_topic
@@ -211,6 +228,8 @@ struct tm_batcher {
     bool stream = false;    // ... through tm_publish_stream_device (TM_BATCHER_STREAM, TM_BATCHER_ROUND_ROBIN)
     bool round_robin = false;
     bool sticky = false;    // TM_BATCHER_STICKY: sticky picks, a context per lane as with round robin
+    bool opts = false;      // TM_BATCHER_OPTS: tm_publish_stream_opts_device, records and pairs with their words
+    bool upgrade = false;   // TM_BATCHER_UPGRADE_QOS
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -255,6 +274,10 @@ struct tm_batcher {
             c.lens.reserve(k);
             c.reqs.reserve(k);
             if (cfg.flags & TM_BATCHER_PUBLISH) c.keys.reserve(k);
+            if (cfg.flags & TM_BATCHER_OPTS) {
+                c.pflags.reserve(k);
+                c.pfrom.reserve(k);
+            }
             c.bytes.reserve(k * 64);
             return c;
         }
@@ -334,6 +357,10 @@ struct tm_batcher {
                 c.lens.assign(x.cur.lens.begin() + h, x.cur.lens.begin() + h + k);
                 c.reqs.assign(x.cur.reqs.begin() + h, x.cur.reqs.begin() + h + k);
                 if (!x.cur.keys.empty()) c.keys.assign(x.cur.keys.begin() + h, x.cur.keys.begin() + h + k);
+                if (!x.cur.pflags.empty()) {
+                    c.pflags.assign(x.cur.pflags.begin() + h, x.cur.pflags.begin() + h + k);
+                    c.pfrom.assign(x.cur.pfrom.begin() + h, x.cur.pfrom.begin() + h + k);
+                }
                 x.cur.head += k;
                 x.cur.bhead += kb;
                 x.cur.compact();
@@ -506,21 +533,30 @@ struct tm_batcher {
     }
 
     // TM_BATCHER_PUBLISH: [offsets (n+1) u64][keys n u32, padded to 8 B][bytes]
-    // in one pinned block, up in one copy
+    // in one pinned block, up in one copy.  TM_BATCHER_OPTS: pub_flags and
+    // pub_from (n u32 each, padded alike) between the keys and the bytes, in
+    // the same copy
     static uint64_t keyb_of(uint32_t n) { return ((uint64_t)n * 4 + 7) & ~7ull; }
+    uint64_t upb_of(uint32_t n) const { return keyb_of(n) * (opts ? 3u : 1u); }   // the u32 planes that go up
     bool pack_publish(Lane& L) {
         uint64_t nb = 0;
         for (const Chunk& c : L.chunks) nb += c.nbytes();
-        const uint64_t offb = ((uint64_t)L.n + 1) * 8, keyb = keyb_of(L.n);
-        if (!L.h_io.ensure(offb + keyb + nb + 16)) return false;
+        const uint64_t offb = ((uint64_t)L.n + 1) * 8, keyb = keyb_of(L.n), upb = upb_of(L.n);
+        if (!L.h_io.ensure(offb + upb + nb + 16)) return false;
         uint64_t* ho = (uint64_t*)L.h_io.p;
         uint32_t* hk = (uint32_t*)((uint8_t*)L.h_io.p + offb);
-        uint8_t* hb = (uint8_t*)L.h_io.p + offb + keyb;
+        uint32_t* hf = (uint32_t*)((uint8_t*)L.h_io.p + offb + keyb);
+        uint32_t* hr = (uint32_t*)((uint8_t*)L.h_io.p + offb + 2 * keyb);
+        uint8_t* hb = (uint8_t*)L.h_io.p + offb + upb;
         uint64_t o = 0, k = 0;
         ho[0] = 0;
         for (const Chunk& c : L.chunks) {
             if (c.nbytes()) std::memcpy(hb + o, c.bytes.data() + c.bhead, c.nbytes());
             if (c.size()) std::memcpy(hk + k, c.keys.data() + c.head, c.size() * 4);
+            if (opts && c.size()) {
+                std::memcpy(hf + k, c.pflags.data() + c.head, c.size() * 4);
+                std::memcpy(hr + k, c.pfrom.data() + c.head, c.size() * 4);
+            }
             for (size_t j = c.head; j < c.lens.size(); ++j) {
                 o += c.lens[j];
                 ho[++k] = o;
@@ -630,16 +666,25 @@ struct tm_batcher {
     int run_publish_stream(Lane& L, uint64_t& results) {
         auto chk = [](hipError_t e) { return e == hipSuccess; };
         const uint32_t n = L.n;
-        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), head = ps_head(n);
+        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), upb = upb_of(n), head = ps_head(n);
         const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
-        if (!L.d_io.ensure(offb + keyb + nbytes + 16)) return TM_ENOMEM;
+        if (!L.d_io.ensure(offb + upb + nbytes + 16)) return TM_ENOMEM;
         hipStream_t s = L.stream;
         clk::time_point t0 = clk::now();
-        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + keyb + nbytes + 8, hipMemcpyHostToDevice, s)))
+        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + upb + nbytes + 8, hipMemcpyHostToDevice, s)))
             return TM_EDEVICE;
         const uint64_t* d_off = (const uint64_t*)L.d_io.p;
         const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
-        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + keyb;
+        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + upb;
+        // TM_BATCHER_OPTS: the publishes' words went up with the keys, and the block
+        // that comes back grows by the two word planes:
+        // [hdr][doff][sub_off][deliveries cap x 16 B][pairs scap x 8 B][pick words cap x 4 B][pair words scap x 4 B]
+        const uint64_t wb = opts ? 4 : 0;   // word bytes per record and per pair
+        tm_deliver dv{};
+        dv.pub_flags = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + keyb);
+        dv.pub_from = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + 2 * keyb);
+        dv.flags = upgrade ? TM_DELIVER_UPGRADE_QOS : 0u;
+        const uint32_t strategy = round_robin ? TM_SHARE_ROUND_ROBIN : sticky ? TM_SHARE_STICKY : TM_SHARE_KEYED;
         tm_publish_caps caps = stream_caps(L, n);
         const bool eager = n <= EAGER_TOPICS;
         for (int pass = 0; pass < 5; ++pass) {
@@ -648,19 +693,23 @@ struct tm_batcher {
                 ++L.reruns;
             }
             const uint64_t cap = caps.routes, scap = caps.pairs;
-            const uint64_t outb = head + cap * 16 + scap * 8;
-            const uint64_t wsb = tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
+            const uint64_t o_pickw = head + cap * 16 + scap * 8, o_pairw = o_pickw + cap * wb;
+            const uint64_t outb = o_pairw + scap * wb;
+            const uint64_t wsb = opts ? tm_publish_stream_opts_workspace_bytes(eng, n, nbytes, &caps)
+                                      : tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
             if (!wsb) return TM_ERANGE;
             if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? outb : head)) return TM_ENOMEM;
             uint8_t* d = (uint8_t*)L.d_out.p;
-            const int rc = tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes,
-                                                    round_robin ? TM_SHARE_ROUND_ROBIN
-                                                    : sticky    ? TM_SHARE_STICKY
-                                                                : TM_SHARE_KEYED,
-                                                    d_key,
-                                                    L.cursors, &caps, L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
-                                                    (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                    (tm_pair*)(d + head + cap * 16), s);
+            dv.sub_deliver = (uint32_t*)(d + o_pairw);
+            const int rc =
+                opts ? tm_publish_stream_opts_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
+                                                     L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
+                                                     (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
+                                                     (tm_pair*)(d + head + cap * 16), &dv, (uint32_t*)(d + o_pickw), s)
+                     : tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
+                                                L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
+                                                (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
+                                                (tm_pair*)(d + head + cap * 16), s);
             if (rc != TM_OK) return rc;
             if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? outb : head, hipMemcpyDeviceToHost, s)))
                 return TM_EDEVICE;
@@ -684,11 +733,17 @@ struct tm_batcher {
                     if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, head + D * 16, hipMemcpyDeviceToHost, s)) ||
                         (P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + head + cap * 16, d + head + cap * 16, P * 8,
                                                   hipMemcpyDeviceToHost, s))) ||
+                        (opts && D && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o_pickw, d + o_pickw, D * 4,
+                                                          hipMemcpyDeviceToHost, s))) ||
+                        (opts && P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o_pairw, d + o_pairw, P * 4,
+                                                          hipMemcpyDeviceToHost, s))) ||
                         !chk(hipStreamSynchronize(s)))
                         return TM_EDEVICE;
                     L.sync_ns += ns_since(t0);
                     h = (const uint8_t*)L.h_out.p;
                 }
+                L.r_pickw = (const uint32_t*)(h + o_pickw);
+                L.r_pairw = (const uint32_t*)(h + o_pairw);
                 L.r_doff = (const uint64_t*)(h + 64);
                 L.r_soff = (const uint64_t*)(h + 64 + offb);
                 L.r_deliv = (const tm_delivery*)(h + head);
@@ -728,7 +783,14 @@ struct tm_batcher {
             for (size_t j = c.head + (lo > i ? lo - i : 0u); j < c.reqs.size() && i + (j - c.head) < hi; ++j) {
                 const uint32_t k = i + (uint32_t)(j - c.head);
                 const Req& r = c.reqs[j];
-                if (publish) {
+                if (opts) {
+                    if (rc == TM_OK)
+                        r.ofn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], L.r_pickw + L.r_doff[k],
+                              (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]), L.r_pairs + L.r_soff[k],
+                              L.r_pairw + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]));
+                    else
+                        r.ofn(r.ctx, r.ticket, rc, nullptr, nullptr, 0, nullptr, nullptr, 0);
+                } else if (publish) {
                     if (rc == TM_OK)
                         r.pfn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]),
                               L.r_pairs + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]));
@@ -947,7 +1009,9 @@ struct tm_batcher {
 namespace {
 // one topic into the calling thread's stripe (pub_key: TM_BATCHER_PUBLISH only)
 inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_t* topic, uint32_t len, Req r,
-                                                     bool publish, uint32_t pub_key, uint64_t* ticket_out) {
+                                                     bool publish, uint32_t pub_key, uint64_t* ticket_out,
+                                                     bool opts = false, uint32_t pub_flags = 0,
+                                                     uint32_t pub_from = 0) {
     if (t_stripe < 0) t_stripe = (int)(g_stripe_rr.fetch_add(1, std::memory_order_relaxed) % NSTRIPE);
     Stripe& s = b->stripes[t_stripe];
     uint64_t t, was;
@@ -959,6 +1023,10 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
         r.ticket = t;
         s.cur.reqs.push_back(r);
         if (publish) s.cur.keys.push_back(pub_key);
+        if (opts) {   // TM_BATCHER_OPTS
+            s.cur.pflags.push_back(pub_flags);
+            s.cur.pfrom.push_back(pub_from);
+        }
         // the counters change only under the stripe lock: plain load + store
         // (no read-modify-write per publish); the 0 -> 1 step is seq_cst for
         // the sealer's idle hand-shake below
@@ -1003,9 +1071,17 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
         delete b;
         return TM_EINVAL;
     }
+    if (((b->cfg.flags & TM_BATCHER_OPTS) && !b->publish) ||
+        ((b->cfg.flags & TM_BATCHER_UPGRADE_QOS) && !(b->cfg.flags & TM_BATCHER_OPTS))) {
+        delete b;
+        return TM_EINVAL;
+    }
     b->round_robin = (b->cfg.flags & TM_BATCHER_ROUND_ROBIN) != 0;
     b->sticky = (b->cfg.flags & TM_BATCHER_STICKY) != 0;
-    b->stream = b->round_robin || b->sticky || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
+    b->opts = (b->cfg.flags & TM_BATCHER_OPTS) != 0;
+    b->upgrade = (b->cfg.flags & TM_BATCHER_UPGRADE_QOS) != 0;
+    // an options lane takes one path, the stream-ordered call, for keyed picks too
+    b->stream = b->round_robin || b->sticky || b->opts || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
@@ -1067,10 +1143,12 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
             if (L->device < 0 || hipSetDevice(L->device) != hipSuccess) continue;
             if (b->stream) {   // the first batch's four capacities
                 const tm_publish_caps c = b->stream_caps(*L, pre);
-                const uint64_t io = offb + tm_batcher::keyb_of((uint32_t)pre) + nbytes + 16;
-                const uint64_t outb = tm_batcher::ps_head((uint32_t)pre) + c.routes * 16 + c.pairs * 8;
+                const uint64_t io = offb + b->upb_of((uint32_t)pre) + nbytes + 16;
+                const uint64_t wb = b->opts ? 4 : 0;
+                const uint64_t outb = tm_batcher::ps_head((uint32_t)pre) + c.routes * (16 + wb) + c.pairs * (8 + wb);
                 (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(outb) && L->h_out.ensure(outb) &&
-                       L->d_ws.ensure(tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
+                       L->d_ws.ensure(b->opts ? tm_publish_stream_opts_workspace_bytes(e, (uint32_t)pre, nbytes, &c)
+                                              : tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
                 continue;
             }
             if (b->publish) {   // the first batch's capacities (Lane::deliv_per_topic, pairs_per_topic)
@@ -1112,7 +1190,7 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
 
 int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn fn, void* ctx,
                       uint64_t* ticket_out) {
-    if (!b || !fn || (!topic && len) || b->publish) return TM_EINVAL;
+    if (!b || !fn || (!topic && len) || b->publish) return TM_EINVAL;   // (an options batcher is a publish one)
     Req r;
     r.fn = fn;
     r.ctx = ctx;
@@ -1122,12 +1200,23 @@ int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batc
 
 int tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
                               tm_publish_done_fn fn, void* ctx, uint64_t* ticket_out) {
-    if (!b || !fn || (!topic && len) || !b->publish) return TM_EINVAL;
+    if (!b || !fn || (!topic && len) || !b->publish || b->opts) return TM_EINVAL;
     Req r;
     r.pfn = fn;
     r.ctx = ctx;
     r.ticket = 0;
     return submit_one(b, topic, len, r, true, pub_key, ticket_out);
+}
+
+int tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
+                                   uint32_t pub_flags, uint32_t pub_from, tm_publish_opts_done_fn fn, void* ctx,
+                                   uint64_t* ticket_out) {
+    if (!b || !fn || (!topic && len) || !b->opts || (pub_flags & 3u) == 3u) return TM_EINVAL;
+    Req r;
+    r.ofn = fn;
+    r.ctx = ctx;
+    r.ticket = 0;
+    return submit_one(b, topic, len, r, true, pub_key, ticket_out, true, pub_flags, pub_from);
 }
 
 int tm_batcher_flush(tm_batcher* b) {

@@ -277,8 +277,9 @@ tm_dispatch_emit(const uint32_t* __restrict__ pool, const uint64_t* __restrict__
 __global__ void __launch_bounds__(DBLOCK)
 tm_dispatch_emit_opts(const uint32_t* __restrict__ pool, const uint64_t* __restrict__ P, uint64_t slots,
                       const uint32_t* __restrict__ pseg, const uint32_t* __restrict__ to,
-                      uint32_t* __restrict__ sub_to, uint32_t* __restrict__ sub_id, uint64_t cap, DeliverArgs dv) {
-    dispatch_emit_body<true>(pool, P, slots, pseg, to, sub_to, sub_id, cap, nullptr, dv);
+                      uint32_t* __restrict__ sub_to, uint32_t* __restrict__ sub_id, uint64_t cap, DeliverArgs dv,
+                      const uint64_t* __restrict__ gate) {
+    dispatch_emit_body<true>(pool, P, slots, pseg, to, sub_to, sub_id, cap, gate, dv);
 }
 
 static inline uint32_t ddiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
@@ -330,7 +331,8 @@ hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t s
 hipError_t launch_dispatch_emit_opts(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                      const uint32_t* to, const uint32_t* ppub, const uint32_t* pub_flags,
                                      const uint32_t* pub_from, uint32_t flags, uint32_t* sub_to, uint32_t* sub_id,
-                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st) {
+                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st,
+                                     const uint64_t* gate) {
     const uint64_t bound = pairs_bound < cap ? pairs_bound : cap;
     if (slots == 0 || bound == 0) return hipSuccess;
     if (!sv.opt || !pub_flags || !sub_deliver) return hipErrorInvalidValue;
@@ -338,7 +340,7 @@ hipError_t launch_dispatch_emit_opts(const SubView& sv, const uint64_t* P, uint6
     if (blocks > 2048u) blocks = 2048u;
     const DeliverArgs dv{sv.opt, ppub, pub_flags, pub_from, flags, sub_deliver};
     hipLaunchKernelGGL(tm_dispatch_emit_opts, dim3(blocks), dim3(DBLOCK), 0, st, sv.pool, P, slots, pseg, to, sub_to,
-                       sub_id, cap, dv);
+                       sub_id, cap, dv, gate);
     return hipGetLastError();
 }
 

@@ -464,6 +464,7 @@ struct Image {
     // share image (share.hip), same epoch; cursor: the replica's round-robin
     // cursors (DevState::sh_cursor) as they were when this image was written
     DevBuf d_hsets, d_htx, d_harena, d_hpool, d_hfx;
+    DevBuf d_hopt;     // the members' emqx_suboption words, parallel to d_hpool
     DevBuf d_fwd;      // forward table (forward.hip): target id -> forwardable node, same epoch
     uint32_t* cursor = nullptr;
     uint32_t* sticky = nullptr;   // the replica's sticky entries (DevState::sh_sticky), likewise
@@ -487,7 +488,7 @@ struct Image {
         for (DevBuf* b : {&d_nodes, &d_edges, &d_hedges, &d_dict, &d_arena, &d_woff, &d_inner, &d_leaf, &d_rslots,
                           &d_rarena, &d_rdest, &d_fr_meta, &d_rank_src, &d_dt, &d_rank_tg, &d_fshape, &d_wheat,
                           &d_sslots, &d_sarena, &d_spool, &d_sopt, &d_fs_meta, &d_hsets, &d_htx, &d_harena, &d_hpool, &d_hfx,
-                          &d_fwd})
+                          &d_hopt, &d_fwd})
             b->release();
         for (hipEvent_t ev : uses) (void)hipEventDestroy(ev);
         uses.clear();
@@ -594,6 +595,7 @@ struct DevState {
     // prefix, the (key, slot) pairs and their sort, the head flags and their
     // prefixes, and the host-buffer call's planes and results
     DevBuf w_fflag, w_fpub, w_fpre, w_fscan, w_fpairs, w_fhead, w_fhpre, w_fcounts, w_foff, w_fsscan, w_fin, w_fout;
+    DevBuf w_kin;     // pick words (share.hip tm_share_pick_words): the host-buffer call's planes and words
     // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
     // the image epochs, so a batch continues where the one before it stopped
     // whichever image each was launched on
@@ -649,7 +651,7 @@ struct DevState {
                           &w_xppub, &w_xdpub, &w_hcnt, &w_hseg, &w_hset, &w_hflag, &w_hpre, &w_hscan, &w_hpairs, &w_hnew, &w_hcounts,
                           &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor, &sh_sticky, &w_hkplane,
                           &w_htg, &w_hfail, &w_hfoff, &w_hdown, &w_fflag, &w_fpub, &w_fpre, &w_fscan, &w_fpairs,
-                          &w_fhead, &w_fhpre, &w_fcounts, &w_foff, &w_fsscan, &w_fin, &w_fout,
+                          &w_fhead, &w_fhpre, &w_fcounts, &w_foff, &w_fsscan, &w_fin, &w_fout, &w_kin,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -1010,6 +1012,15 @@ struct tm_engine {
     MirrorTable<ShareTopicSlot, ShareTopic> sh_tx;
     TopicArena sh_arena;
     SegPool sh_pool;
+    // emqx_suboption for the members: sh_opt[i] is the option word of the
+    // member at sh_pool.v[i] for its set's topic, sub_bag[topic].opts[member]
+    // (SUBOPT_NONE without an entry or without a SubRec: a member id is the
+    // subscriber id).  It shares the segments' {off, cap}, moves wherever they
+    // move, and is refreshed from both sides: the share calls write a new
+    // member's word, the option calls the word of every set that holds the
+    // subscriber (share_opt_sync).
+    std::vector<uint32_t> sh_opt;
+    Track t_hopt;
     FilterLink<uint32_t, ShareTopic> sh_fx{SLOT_NONE};   // filter id -> xid of the wildcard topic it is
     std::vector<uint32_t> sh_free_xid;   // an xid names a topic only within one image: reusable at once
     uint32_t sh_next_xid = 0;
@@ -1807,6 +1818,7 @@ struct tm_engine {
             if (opts) {
                 it->second.opts[sub] = *opts;
                 opt_word_sync(it->second, sub);
+                share_opt_sync(it->first, sub, *opts);
             }
             return;
         }
@@ -1822,7 +1834,10 @@ struct tm_engine {
             if (tm_topic_wildcard(t, tlen)) link_filter(r, filter_of(t, tlen));
         }
         SubRec& r = it->second;
-        if (opts) r.opts[sub] = *opts;   // before the append: the new plain entry's word
+        if (opts) {
+            r.opts[sub] = *opts;   // before the append: the new plain entry's word
+            share_opt_sync(it->first, sub, *opts);
+        }
         r.bag.emplace_back(sub, gid);
         if (gid == NO_GROUP) {
             ++r.n_plain;
@@ -1842,6 +1857,7 @@ struct tm_engine {
         auto it = sub_bag.find(std::string(reinterpret_cast<const char*>(t), tlen));
         if (it == sub_bag.end()) return 0;
         const bool had = it->second.opts.erase(sub) != 0;
+        if (had) share_opt_sync(it->first, sub, SUBOPT_NONE);
         const uint32_t left = sub_del_object(it, sub, g, glen);
         // a plain entry that stays lost its word (one that went: sseg_rewrite)
         if (had && left && it->second.has_plain(sub)) opt_word_sync(it->second, sub);
@@ -1873,6 +1889,8 @@ struct tm_engine {
             else sx_sync(r);
             return (uint32_t)r.bag.size();
         }
+        // the option entries go with the record: the members that had one lose their word
+        for (const auto& o : r.opts) share_opt_sync(it->first, o.first, SUBOPT_NONE);
         unlink_filter(r);
         sx_slots.del(&r);
         sx_pool.drop(r.cap);
@@ -1893,6 +1911,7 @@ struct tm_engine {
         if (w == oi->second) return true;
         oi->second = w;
         if (r.has_plain(sub)) opt_word_sync(r, sub);
+        share_opt_sync(it->first, sub, w);
         return true;
     }
     const SubRec* subscribers(const uint8_t* t, uint32_t tlen) const {
@@ -2006,13 +2025,44 @@ struct tm_engine {
         x.seg = s.off;
         sh_sets.t.cur.mark(s.slot);
     }
-    // the members of s into its segment
+    // the option word of `member` for the topic of its set (sr: that topic's SubRec, null without one)
+    static uint32_t share_opt_word(const SubRec* sr, uint32_t member) {
+        return sr ? opt_word(*sr, member) : SUBOPT_NONE;
+    }
+    const SubRec* share_sub_rec(const ShareSet& s) const {
+        auto it = sub_bag.find(*s.topic->key);
+        return it == sub_bag.end() ? nullptr : &it->second;
+    }
+    // the members of s and their option words into its segment
     void share_seg_rewrite(ShareSet& s) {
         const size_t n = s.members.size();
         sh_pool.fit(s.off, s.cap, n, "share member pool past 2^32 entries");
+        sh_opt.resize(sh_pool.v.size(), SUBOPT_NONE);
         std::copy(s.members.begin(), s.members.end(), sh_pool.v.begin() + s.off);
+        const SubRec* sr = share_sub_rec(s);
+        for (size_t k = 0; k < n; ++k) sh_opt[s.off + k] = share_opt_word(sr, s.members[k]);
         sh_pool.t.mark_range(s.off, s.off + n);
+        t_hopt.mark_range(s.off, s.off + n);
         share_sync(s);
+    }
+    // the option side: emqx_suboption's entry of (topic, sub) became w
+    // (SUBOPT_NONE: erased).  Every set of that topic that holds sub as a
+    // member takes the word, found through the member index; an unchanged word
+    // logs nothing.
+    void share_opt_sync(const std::string& topic, uint32_t sub, uint32_t w) {
+        if (sh_member_sets.empty()) return;
+        auto mi = sh_member_sets.find(sub);
+        if (mi == sh_member_sets.end()) return;
+        for (const ShareSet* s : mi->second) {
+            if (*s->topic->key != topic) continue;
+            const size_t k = (size_t)(std::find(s->members.begin(), s->members.end(), sub) - s->members.begin());
+            if (k == s->members.size()) continue;
+            const size_t i = s->off + k;
+            if (sh_opt[i] == w) continue;
+            sh_opt[i] = w;
+            t_hopt.cur.mark(i);
+            dev_dirty = true;
+        }
     }
     uint32_t share_alloc_six() {
         if (!sh_free_six.empty()) {
@@ -2081,7 +2131,10 @@ struct tm_engine {
         if (s.members.size() > s.cap) {
             share_seg_rewrite(s);
         } else {
-            sh_pool.set(s.off + s.members.size() - 1, member);
+            const size_t i = s.off + s.members.size() - 1;
+            sh_pool.set(i, member);
+            sh_opt[i] = share_opt_word(share_sub_rec(s), member);
+            t_hopt.cur.mark(i);
             share_sync(s);
         }
         if (s.slot == SLOT_NONE) share_slot_put(s);   // a new set: in the table once it has its member
@@ -2154,17 +2207,30 @@ struct tm_engine {
         return (uint32_t)of.size();
     }
     void maybe_compact_shares() {
+        std::vector<uint32_t> nopt;   // the option words follow their segments
+        bool pool_gc = false;
         compact(sh_pool, sh_arena, route_gc_min, [&](auto seg, auto top) {
             for (auto& kv : sh_topics) {
                 ShareTopic& tp = kv.second;
-                for (auto& sk : tp.sets)
-                    if (seg(sk.second->off, sk.second->cap)) share_sync(*sk.second);
+                for (auto& sk : tp.sets) {
+                    const uint32_t from = sk.second->off;
+                    if (seg(sk.second->off, sk.second->cap)) {
+                        pool_gc = true;
+                        nopt.insert(nopt.end(), sh_opt.begin() + from, sh_opt.begin() + from + sk.second->cap);
+                        share_sync(*sk.second);
+                    }
+                }
                 if (top(tp.arena, tp.words)) {
                     sh_tx.slots[tp.slot].arena = tp.arena * 8;
                     sh_tx.t.cur.mark(tp.slot);
                 }
             }
         });
+        if (pool_gc || sh_opt.size() != sh_pool.v.size()) {   // (a pool of garbage only: rewritten empty)
+            sh_opt.swap(nopt);
+            sh_opt.resize(sh_pool.v.size(), SUBOPT_NONE);
+            t_hopt.cur.all = true;
+        }
     }
     ShareView make_share_view(const Image& g) const {
         ShareView hv;
@@ -2174,6 +2240,7 @@ struct tm_engine {
         hv.tx_mask = sh_tx.slots.size() - 1;
         hv.tx_arena = g.d_harena.as<const uint8_t>();
         hv.pool = g.d_hpool.as<const uint32_t>();
+        hv.opt = g.d_hopt.as<const uint32_t>();
         hv.fx = g.d_hfx.as<const uint32_t>();
         hv.n_filters = (uint32_t)sh_fx.meta.size();
         hv.cursor = g.cursor;
@@ -2764,6 +2831,7 @@ struct tm_engine {
         f(sh_tx.slots, sh_tx.t, &Image::d_htx, true);
         f(sh_arena.words, sh_arena.t, &Image::d_harena, true);
         f(sh_pool.v, sh_pool.t, &Image::d_hpool, true);
+        f(sh_opt, t_hopt, &Image::d_hopt, true);
         f(sh_fx.meta, sh_fx.t, &Image::d_hfx, true);
         f(fshape, t_fshape, &Image::d_fshape, shape_keys != 0);
     }
@@ -3514,8 +3582,9 @@ struct tm_engine {
         uint64_t ctl, raw, rcounts, roff, rids, rexact, rscan, dcount, aoff, dsrc, ddest, akey, alarge, acount, to, tg,
             ndisp, pick, sub_count, sub_to, sub_id, xpcnt, xpseg, xpre, xscan, hcnt, hseg, hset, hflag, hpre, hscan,
             hk, hnew, hcounts, hoff, hsscan, pscan, hkplane, bytes;
+        uint64_t xppub, pword;   // tm_publish_stream_opts_device only
     };
-    static StreamLayout stream_layout(uint32_t n, const tm_publish_caps& c) {
+    static StreamLayout stream_layout(uint32_t n, const tm_publish_caps& c, bool opts = false) {
         StreamLayout L{};
         uint64_t at = 0;
         auto take = [&](uint64_t bytes) {
@@ -3565,6 +3634,12 @@ struct tm_engine {
         // sticky: the flagged slots' keys.  Last, so the other pieces keep their offsets; taken for every
         // strategy, because the need is one function of n and the capacities (tm_publish_stream_workspace_bytes)
         L.hkplane = take(R1 * 4);
+        // the call with options: each slot's publish index (the delivery-word emit) and the slot-indexed
+        // pick words (share.hip tm_share_pick_words), behind everything the plain call takes
+        if (opts) {
+            L.xppub = take(R1 * 4);
+            L.pword = take(R1 * 4);
+        }
         L.bytes = at;
         return L;
     }
@@ -3581,8 +3656,16 @@ struct tm_engine {
                             uint32_t strategy, const uint32_t* pub_key, uint32_t* cur, uint32_t* stk,
                             const tm_publish_caps& c,
                             uint8_t* ws, uint64_t* hdr, uint64_t* doff, uint64_t* sub_off, void* deliv, void* pairs,
-                            hipStream_t st) {
-        const StreamLayout L = stream_layout(n, c);
+                            hipStream_t st, const tm_deliver* dv = nullptr, uint32_t* pick_word = nullptr) {
+        // dv (tm_publish_stream_opts_device; device pointers): the delivery
+        // words too -- dv->sub_deliver parallel to pairs, pick_word parallel to
+        // deliv.  The count pass stores each slot's publish index and the
+        // emit writes the pair words (the two kernels of the batch calls with
+        // options, bounded as the plain ones are here); the pick words are
+        // computed per slot once the picks are final and packed with the
+        // records.  Nothing else differs, and the cursor / sticky store stays
+        // the last kernel.
+        const StreamLayout L = stream_layout(n, c, dv != nullptr);
         auto u32 = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(ws + o); };
         auto u64 = [&](uint64_t o) { return reinterpret_cast<uint64_t*>(ws + o); };
         uint64_t* ctl = u64(L.ctl);
@@ -3607,12 +3690,17 @@ struct tm_engine {
                             st, gate));
         uint64_t* P = u64(L.xpre);
         HIPCHK(launch_dispatch_count(sub_view(d), bytes, off, n, acount, u64(L.aoff), to, tg, R, ndisp, u32(L.xpcnt),
-                                     u32(L.xpseg), st, raw + 1, gate));
+                                     u32(L.xpseg), st, raw + 1, gate, dv ? u32(L.xppub) : nullptr));
         HIPCHK(launch_scan0(u32(L.xpcnt), (uint32_t)R, P, P + R, u64(L.xscan), st));
         HIPCHK(launch_stream_check(ctl, 3, P + R, c.pairs, st));
         HIPCHK(launch_dispatch_offsets(P, R, u64(L.aoff), n, u32(L.sub_count), sub_off, st, gate));
-        HIPCHK(launch_dispatch_emit(sub_view(d), P, R, u32(L.xpseg), to, u32(L.sub_to), u32(L.sub_id), c.pairs, c.pairs,
-                                    st, gate));
+        if (dv)
+            HIPCHK(launch_dispatch_emit_opts(sub_view(d), P, R, u32(L.xpseg), to, u32(L.xppub), dv->pub_flags,
+                                             dv->pub_from, dv->flags, u32(L.sub_to), u32(L.sub_id), dv->sub_deliver,
+                                             c.pairs, c.pairs, st, gate));
+        else
+            HIPCHK(launch_dispatch_emit(sub_view(d), P, R, u32(L.xpseg), to, u32(L.sub_to), u32(L.sub_id), c.pairs,
+                                        c.pairs, st, gate));
         // 4. the $share picks
         ShareView hv = share_view(d);
         hv.cursor = cur;
@@ -3650,9 +3738,16 @@ struct tm_engine {
                 HIPCHK(launch_share_rr_pick(hv, odd ? k1 : k0, odd ? v1 : v0, (uint32_t)c.rr, u32(L.hcnt), u32(L.hseg),
                                             pick, u32(L.hnew), HP + R, gate, st));
         }
+        // the picks are final: their delivery words, per slot
+        if (dv)
+            HIPCHK(launch_share_pick_words(hv, local, bytes, off, n, acount, u64(L.aoff), to, tg, pick, R, dv->pub_flags,
+                                           dv->pub_from, dv->flags, u32(L.pword), raw + 1, gate, st));
         // 5. the dense records and the header
         HIPCHK(launch_publish_pack(n, acount, u64(L.aoff), to, tg, ndisp, pick, R, raw + 1, u32(L.sub_to), u32(L.sub_id),
                                    c.pairs, P + R, hdr, doff, deliv, R, pairs, c.pairs, u64(L.pscan), st, gate));
+        if (dv)   // the pair words are dense already (the pairs keep their positions)
+            HIPCHK(launch_publish_pack_words(n, acount, u64(L.aoff), u32(L.pword), R, raw + 1, nullptr, 0, nullptr, doff,
+                                             pick_word, R, nullptr, 0, st, gate));
         HIPCHK(launch_stream_finish(ctl, doff, n, hdr, st));
         // 6. the new cursors, only when the whole batch fitted: a rerun of a
         // batch that did not starts from the cursors its first run found
@@ -5407,6 +5502,40 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
     return rc;
 }
 
+int tm_publish_pack_opts_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                                const uint32_t* d_to, const uint32_t* d_target, const uint32_t* d_ndisp,
+                                const uint32_t* d_pick, uint64_t out_cap, const uint64_t* d_total,
+                                const uint64_t* d_sub_off, const uint32_t* d_sub_to, const uint32_t* d_sub_id,
+                                uint64_t sub_cap, const uint64_t* d_sub_total, uint64_t* d_hdr, uint64_t* d_doff,
+                                tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
+                                const uint32_t* d_sub_deliver, const uint32_t* d_pick_word_slots,
+                                uint32_t* d_pair_word, uint32_t* d_pick_word, void* hip_stream) {
+    if ((out_cap && deliv_cap && (!d_pick_word_slots || !d_pick_word)) ||
+        (sub_cap && pair_cap && (!d_sub_deliver || !d_pair_word)))
+        return TM_EINVAL;
+    // the records, the offsets and the header: the plain pack, then the two word planes on the same stream
+    if (int rc = tm_publish_pack_device(e, n, d_count, d_off, d_to, d_target, d_ndisp, d_pick, out_cap, d_total,
+                                        d_sub_off, d_sub_to, d_sub_id, sub_cap, d_sub_total, d_hdr, d_doff, d_deliv,
+                                        deliv_cap, d_pairs, pair_cap, hip_stream))
+        return rc;
+    DevState& d = *e->replica_for(d_off);
+    std::string err;
+    const int rc = catching(err, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        HIPCHK(launch_publish_pack_words(n, d_count, d_off, d_pick_word_slots, out_cap, d_total, d_sub_deliver, sub_cap,
+                                         d_sub_total, d_doff, d_pick_word, deliv_cap,
+                                         (sub_cap && pair_cap) ? d_pair_word : nullptr, pair_cap, st));
+        return TM_OK;
+    });
+    if (rc != TM_OK)
+        return guarded(e, [&] {
+            e->last_error = err;
+            return rc;
+        });
+    return rc;
+}
+
 static_assert(sizeof(tm_forward_group) == 16, "forward.hip stores 16 B group records");
 
 int tm_forward_plan_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
@@ -5479,6 +5608,119 @@ int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint6
     }, [] {});
 }
 
+static_assert(TM_NO_WORD == 0xFFFFFFFFu && (TM_NO_WORD & 3u) == tmx::SUBOPT_NONE, "a delivery word's QoS is never 3");
+
+// the descriptor of the pick-word pass: tm_deliver's per-publish arrays and flag, no pair words
+static bool pick_words_args_bad(const tm_deliver* dv, uint32_t n) {
+    return !dv || (n && !dv->pub_flags) || dv->sub_deliver || (dv->flags & ~TM_DELIVER_UPGRADE_QOS);
+}
+
+int tm_share_pick_words_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_topic_off, uint32_t n,
+                               const uint32_t* d_count, const uint64_t* d_off, const uint32_t* d_to,
+                               const uint32_t* d_target, const uint32_t* d_pick, uint64_t out_cap,
+                               const uint64_t* d_total, const tm_deliver* deliver, uint32_t* d_pick_word,
+                               void* hip_stream) {
+    if (!d_topic_off || !d_off || !d_total || (n && !d_count) ||
+        (out_cap && (!d_to || !d_target || !d_pick || !d_pick_word)) || pick_words_args_bad(deliver, n))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "pick words");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->replica_for(d_off);
+    return batch_call(e, {&d}, [&]() -> int {
+        if (n == 0 || out_cap == 0) return TM_OK;
+        if (out_cap >= 0xFFFFFFFEull) throw RangeError("pick words: more than 2^32 - 2 delivery slots in one batch");
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        HIPCHK(launch_share_pick_words(tm_engine::share_view(d), tm_engine::sub_view(d).local_target, d_bytes,
+                                       d_topic_off, n, d_count, d_off, d_to, d_target, d_pick, out_cap,
+                                       deliver->pub_flags, deliver->pub_from, deliver->flags, d_pick_word, d_total,
+                                       nullptr, st));
+        d.note_use(st);   // the pass read the pinned share image
+        return TM_OK;
+    }, [] {});
+}
+
+int tm_share_pick_words(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                        const uint32_t* count, const uint64_t* off, const uint32_t* to, const uint32_t* target,
+                        const uint32_t* pick, uint64_t out_cap, uint64_t total, const tm_deliver* deliver,
+                        uint32_t* pick_word) {
+    if (!topic_off || !off || (n && !count) || (out_cap && (!to || !target || !pick || !pick_word)) ||
+        pick_words_args_bad(deliver, n))
+        return TM_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if ((deliver->pub_flags[i] & 3u) == 3u) return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "pick words");
+    if (int rc = local_node_unset(e)) return rc;
+    DevState& d = *e->devs[0];
+    return batch_call(e, {&d}, [&]() -> int {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (topic_off[i + 1] < topic_off[i]) throw ArgError("topic offsets not monotone");
+            if (off[i + 1] < off[i]) throw ArgError("delivery offsets not monotone");
+        }
+        const uint64_t c = std::min(total, out_cap);   // the live slots: what the planes hold
+        if (n == 0 || c == 0) return TM_OK;
+        if (off[n] < off[0] || c < off[0]) throw ArgError("delivery offsets past the slots");
+        const uint64_t tb0 = topic_off[0], tbytes = topic_off[n] - tb0;
+        if (tbytes && !topic_bytes) throw ArgError("null topic bytes");
+        if (c >= 0xFFFFFFFEull) throw RangeError("pick words: more than 2^32 - 2 delivery slots in one batch");
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        // [topic off][off][total][count][pub_flags][pub_from][to][target][pick][word][bytes]
+        const size_t o_off = (size_t)(n + 1) * 8, o_total = o_off * 2, o_count = o_total + 8,
+                     o_pf = o_count + (size_t)n * 4, o_from = o_pf + (size_t)n * 4, o_to = o_from + (size_t)n * 4,
+                     o_tg = o_to + (size_t)c * 4, o_pick = o_tg + (size_t)c * 4, o_word = o_pick + (size_t)c * 4,
+                     o_bytes = o_word + (size_t)c * 4;
+        // no kernel of an earlier call reads the buffer: every call waits for its own
+        d.w_kin.ensure(o_bytes + tbytes + 16);
+        uint8_t* in = d.w_kin.as<uint8_t>();
+        std::vector<uint64_t> toff(n + 1);   // the bytes go up from topic_off[0]
+        for (uint32_t i = 0; i <= n; ++i) toff[i] = topic_off[i] - tb0;
+        HIPCHK(hipMemcpyAsync(in, toff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_total, &c, 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_count, count, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_pf, deliver->pub_flags, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        if (deliver->pub_from)
+            HIPCHK(hipMemcpyAsync(in + o_from, deliver->pub_from, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_to, to, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_tg, target, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(in + o_pick, pick, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        // the words as they are: the pass leaves holes untouched
+        HIPCHK(hipMemcpyAsync(in + o_word, pick_word, (size_t)c * 4, hipMemcpyHostToDevice, s));
+        if (tbytes) HIPCHK(hipMemcpyAsync(in + o_bytes, topic_bytes + tb0, tbytes, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_share_pick_words(
+            tm_engine::share_view(d), tm_engine::sub_view(d).local_target, in + o_bytes,
+            reinterpret_cast<const uint64_t*>(in), n, reinterpret_cast<const uint32_t*>(in + o_count),
+            reinterpret_cast<const uint64_t*>(in + o_off), reinterpret_cast<const uint32_t*>(in + o_to),
+            reinterpret_cast<const uint32_t*>(in + o_tg), reinterpret_cast<const uint32_t*>(in + o_pick), c,
+            reinterpret_cast<const uint32_t*>(in + o_pf),
+            deliver->pub_from ? reinterpret_cast<const uint32_t*>(in + o_from) : nullptr, deliver->flags,
+            reinterpret_cast<uint32_t*>(in + o_word), reinterpret_cast<const uint64_t*>(in + o_total), nullptr, s));
+        d.note_use(s);
+        HIPCHK(hipMemcpyAsync(pick_word, in + o_word, (size_t)c * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return TM_OK;
+    }, [] {});
+}
+
+// the option words of a set's members, in list order, from the host mirror of
+// the member option pool (diagnostic: the tests compare them with tm_sub_get_opts)
+int tm_debug_share_opts(tm_engine* e, const uint8_t* group, uint32_t glen, const uint8_t* topic, uint32_t tlen,
+                        uint32_t* out, uint32_t cap, uint32_t* out_n) {
+    if (!e || (glen && !group) || (tlen && !topic) || !out_n || (cap && !out)) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        *out_n = 0;
+        const tm_engine::ShareSet* s = e->share_find(group, glen, topic, tlen);
+        if (!s) return TM_OK;
+        const uint32_t k = (uint32_t)s->members.size();
+        *out_n = k;
+        for (uint32_t i = 0; i < k && i < cap; ++i) out[i] = e->sh_opt[s->off + i];
+        return k > cap ? TM_ENOSPC : TM_OK;
+    });
+}
+
 int tm_share_cursors_open(tm_engine* e, uint32_t replica, tm_share_cursors** out) {
     if (!e || !out) return TM_EINVAL;
     *out = nullptr;
@@ -5534,11 +5776,21 @@ uint64_t tm_publish_stream_workspace_bytes(tm_engine* e, uint32_t n, uint64_t to
     return tm_engine::stream_layout(n, *caps).bytes;
 }
 
-int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
-                             uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
-                             tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
-                             uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
-                             tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream) {
+uint64_t tm_publish_stream_opts_workspace_bytes(tm_engine* e, uint32_t n, uint64_t topic_bytes,
+                                                const tm_publish_caps* caps) {
+    (void)e;
+    (void)topic_bytes;
+    if (!caps || !tm_engine::stream_caps_ok(*caps)) return 0;
+    return tm_engine::stream_layout(n, *caps, true).bytes;
+}
+
+// dv != null: the call with options (dv validated by the caller)
+static int publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                 uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                                 tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                                 uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                                 tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream, const tm_deliver* dv,
+                                 uint32_t* d_pick_word) {
     if (!d_off || !d_hdr || !d_doff || !d_sub_off || !caps || !d_workspace) return TM_EINVAL;
     if (!share_strategy_ok(strategy)) return TM_EINVAL;
     if (share_strategy_keyed(strategy) && n && !d_pub_key) return TM_EINVAL;
@@ -5546,7 +5798,7 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_
     tm_publish_caps c = *caps;
     if (strategy == TM_SHARE_KEYED) c.rr = 0;   // ignored: keyed picks rank nothing
     if (!tm_engine::stream_caps_ok(c)) return TM_ERANGE;
-    if (workspace_bytes < tm_engine::stream_layout(n, c).bytes) return TM_EINVAL;
+    if (workspace_bytes < tm_engine::stream_layout(n, c, dv != nullptr).bytes) return TM_EINVAL;
     if (!e) return TM_EINVAL;
     if (e->devs.empty()) return no_device(e, "publish");
     if (int rc = local_node_unset(e)) return rc;
@@ -5566,9 +5818,33 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_
         uint32_t* cur = cursors ? cursors->buf.as<uint32_t>() : tm_engine::share_view(d).cursor;
         uint32_t* stk = cursors ? cursors->sbuf.as<uint32_t>() : tm_engine::share_view(d).sticky;
         e->run_publish_stream(d, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cur, stk, c,
-                              static_cast<uint8_t*>(d_workspace), d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, st);
+                              static_cast<uint8_t*>(d_workspace), d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, st, dv,
+                              d_pick_word);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
+}
+
+int tm_publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                             uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                             tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                             uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                             tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream) {
+    return publish_stream_device(e, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cursors, caps, d_workspace,
+                                 workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, hip_stream, nullptr,
+                                 nullptr);
+}
+
+int tm_publish_stream_opts_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                  uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                                  tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                                  uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                                  tm_delivery* d_deliv, tm_pair* d_pairs, const tm_deliver* deliver,
+                                  uint32_t* d_pick_word, void* hip_stream) {
+    if (!deliver || !caps || deliver_args_bad(deliver, n, caps->pairs) || (caps->routes && !d_pick_word))
+        return TM_EINVAL;
+    return publish_stream_device(e, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cursors, caps, d_workspace,
+                                 workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, hip_stream, deliver,
+                                 d_pick_word);
 }
 
 // pick/5 with FailedSubs (share.hip tm_share_retry_resolve / tm_share_retry_pick):
@@ -6195,6 +6471,14 @@ extern "C" int tm_debug_check_shares(tm_engine* e) {
                 if (st.cap < st.members.size() || (uint64_t)st.off + st.cap > e->sh_pool.v.size() ||
                     !std::equal(st.members.begin(), st.members.end(), e->sh_pool.v.begin() + st.off))
                     return fail("segment of " + kv.first);
+                if ((uint64_t)st.off + st.cap > e->sh_opt.size()) return fail("option segment of " + kv.first);
+                {
+                    auto sb = e->sub_bag.find(kv.first);
+                    const tm_engine::SubRec* sr = sb == e->sub_bag.end() ? nullptr : &sb->second;
+                    for (size_t k = 0; k < st.members.size(); ++k)
+                        if (e->sh_opt[st.off + k] != tm_engine::share_opt_word(sr, st.members[k]))
+                            return fail("option word of " + kv.first);
+                }
                 std::unordered_set<uint32_t> uniq(st.members.begin(), st.members.end());
                 if (uniq.size() != st.members.size()) return fail("duplicate member in " + kv.first);
                 for (uint32_t mbr : st.members) {
@@ -6237,6 +6521,7 @@ extern "C" int tm_debug_check_shares(tm_engine* e) {
             if (!six_seen.insert(q.second).second) return fail("quarantined set index in use");
         if (six_seen.size() != e->sh_next_six) return fail("set index accounting");
         check_accounting(e->sh_pool, e->sh_arena, live_cap, live_words, fail);
+        if (e->sh_opt.size() != e->sh_pool.v.size()) return fail("option pool size");
         return TM_OK;
     });
 }

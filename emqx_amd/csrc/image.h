@@ -256,6 +256,10 @@ struct ShareView {
     uint64_t              tx_mask;
     const uint8_t*        tx_arena;
     const uint32_t*       pool;      // the member pool
+    // emqx_suboption for the members, parallel to pool: opt[i] is the option
+    // word (deliver.h) of the member at pool[i] for its set's topic,
+    // SUBOPT_NONE without an entry (a member id is the subscriber id)
+    const uint32_t*       opt;
     const uint32_t*       fx;        // n_filters: filter id -> xid of that wildcard topic (0xFFFFFFFF: none)
     uint32_t              n_filters;
     uint32_t*             cursor;    // set index -> stored Rem, 0xFFFFFFFF = undefined (per replica)

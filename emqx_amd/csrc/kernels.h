@@ -194,11 +194,13 @@ hipError_t launch_dispatch_emit(const SubView& sv, const uint64_t* P, uint64_t s
 // second emit kernel that reads sv.opt beside sv.pool and writes
 // sub_deliver[p] beside sub_id[p].  ppub == null: slot i belongs to publish i
 // (launch_dispatch_lookup's geometry).  pub_flags / pub_from: n device words
-// each (pub_from may be null).  Calls without options launch neither.
+// each (pub_from may be null).  Calls without options launch neither.  gate:
+// as launch_dispatch_emit's (the stream-ordered publish call with options).
 hipError_t launch_dispatch_emit_opts(const SubView& sv, const uint64_t* P, uint64_t slots, const uint32_t* pseg,
                                      const uint32_t* to, const uint32_t* ppub, const uint32_t* pub_flags,
                                      const uint32_t* pub_from, uint32_t flags, uint32_t* sub_to, uint32_t* sub_id,
-                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st);
+                                     uint32_t* sub_deliver, uint64_t cap, uint64_t pairs_bound, hipStream_t st,
+                                     const uint64_t* gate = nullptr);
 
 // emqx_shared_sub:dispatch/3 member pick (share.hip) over the same deliveries
 // CSR and slot geometry as launch_dispatch_count.
@@ -261,6 +263,16 @@ hipError_t launch_share_retry_resolve(const ShareView& hv, const uint8_t* bytes,
 hipError_t launch_share_retry_pick(const ShareView& hv, uint32_t strategy, const uint32_t* keys, const uint32_t* vals,
                                    uint32_t n, const uint32_t* rcnt, const uint32_t* rseg, const uint32_t* pub_key,
                                    const uint32_t* failed, const uint64_t* failed_off, uint32_t* pick, hipStream_t st);
+// the delivery word of every $share pick of a publish call's planes (a
+// post-pass, stateless): pick_word[slot] for every live slot below
+// min(*dtotal, slots) -- deliver.h's word over the picked member's option word
+// (ShareView::opt), TM_NO_WORD without a pick or when the member is not in the
+// slot's set; pub_from may be null; dtotal / gate as launch_share_lookup
+hipError_t launch_share_pick_words(const ShareView& hv, uint32_t local_target, const uint8_t* bytes,
+                                   const uint64_t* off, uint32_t n, const uint32_t* acount, const uint64_t* aoff,
+                                   const uint32_t* to, const uint32_t* tg, const uint32_t* pick, uint64_t slots,
+                                   const uint32_t* pub_flags, const uint32_t* pub_from, uint32_t flags,
+                                   uint32_t* pick_word, const uint64_t* dtotal, const uint64_t* gate, hipStream_t st);
 
 // emqx_broker:forward/3's sending half (forward.hip): the remote-node
 // deliveries of a batch regrouped per (target, To), over the same deliveries
@@ -305,6 +317,17 @@ hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t
                                const uint64_t* sub_total, uint64_t* hdr, uint64_t* doff, void* deliv,
                                uint64_t deliv_cap, void* pairs, uint64_t pair_cap, uint64_t* scan_tmp, hipStream_t st,
                                const uint64_t* gate = nullptr);
+// the word planes of a publish call with options, dense beside the records of
+// launch_publish_pack (which ran before and left doff): pick_word[doff[t] + k] =
+// slot_word[off[t] + k] for the records below deliv_cap (holes removed), and
+// (pair_word != null) pair_word[p] = sub_deliver[p] for p < min(*sub_total,
+// sub_cap, pair_cap).  Nothing is written at or past the two capacities.
+hipError_t launch_publish_pack_words(uint32_t n, const uint32_t* count, const uint64_t* off,
+                                     const uint32_t* slot_word, uint64_t out_cap, const uint64_t* total,
+                                     const uint32_t* sub_deliver, uint64_t sub_cap, const uint64_t* sub_total,
+                                     const uint64_t* doff, uint32_t* pick_word, uint64_t deliv_cap,
+                                     uint32_t* pair_word, uint64_t pair_cap, hipStream_t st,
+                                     const uint64_t* gate = nullptr);
 
 // Sharded mode (shard.hip): merge per-topic match lists of S filter shards
 // for m topics.  counts [S][m]; source s's items start at src_base[s] of

@@ -119,6 +119,83 @@ hipError_t launch_publish_pack(uint32_t n, const uint32_t* count, const uint64_t
     return hipGetLastError();
 }
 
+// ---- the word planes of a publish call with options ---------------------------
+// The delivery words travel beside the records as two dense u32 planes, so
+// the 16 B and 8 B record layouts stay what they are: pick_word[g] for record
+// g = doff[t] + k is the word of slot off[t] + k (share.hip
+// tm_share_pick_words' plane, holes removed), and pair_word[p] = sub_deliver[p]
+// (the pairs keep their positions).  The geometry is tm_publish_pack's, which
+// ran before and left doff; no header is written here.  One 4 B store per
+// word, neighbouring lanes on neighbouring words; no atomics, no scratch.
+__global__ void __launch_bounds__(PKBLOCK)
+tm_publish_pack_words(uint32_t n, const uint32_t* __restrict__ count, const uint64_t* __restrict__ off,
+                      const uint32_t* __restrict__ slot_word, uint64_t out_cap, const uint64_t* __restrict__ total,
+                      const uint32_t* __restrict__ sub_deliver, uint64_t sub_cap,
+                      const uint64_t* __restrict__ sub_total, const uint64_t* __restrict__ doff,
+                      uint32_t* __restrict__ pick_word, uint64_t deliv_cap, uint32_t* __restrict__ pair_word,
+                      uint64_t pair_cap, uint32_t split, const uint64_t* __restrict__ gate) {
+    __shared__ uint64_t lds_inc[PKBLOCK];   // inclusive prefix of the block's delivery counts
+    __shared__ uint64_t lds_scan[PKBLOCK / 64];
+    if (gate && *gate) return;
+    const uint64_t rtotal = *total;
+    const uint64_t slots = rtotal < out_cap ? rtotal : out_cap;
+    const uint32_t nblk = (n + PKBLOCK - 1) / PKBLOCK;
+    for (uint64_t v = blockIdx.x; v < (uint64_t)nblk * split; v += gridDim.x) {
+        const uint32_t t0 = (uint32_t)(v / split) * PKBLOCK;
+        const uint32_t part = (uint32_t)(v % split);
+        const uint32_t tn = n - t0 < (uint32_t)PKBLOCK ? n - t0 : (uint32_t)PKBLOCK;
+        const uint64_t c = threadIdx.x < tn ? count[t0 + threadIdx.x] : 0ull;
+        uint64_t agg;
+        const uint64_t ex = block_exclusive_scan<PKBLOCK>(c, lds_scan, agg);
+        lds_inc[threadIdx.x] = ex + c;
+        __syncthreads();
+        const uint64_t base = doff[t0];
+        for (uint64_t j = (uint64_t)part * PKBLOCK + threadIdx.x; j < agg; j += (uint64_t)split * PKBLOCK) {
+            const uint64_t g = base + j;
+            if (g >= deliv_cap) break;   // nothing is written at or past the record capacity
+            uint32_t lo = 0, hi = tn - 1;   // local topic of record j: the first with inclusive prefix > j
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (lds_inc[mid] > j) hi = mid;
+                else lo = mid + 1;
+            }
+            const uint64_t s = off[t0 + lo] + (j - (lo ? lds_inc[lo - 1] : 0ull));
+            if (s >= slots) continue;   // the batch did not fit: the word is unspecified
+            pick_word[g] = slot_word[s];
+        }
+        __syncthreads();   // lds_inc is rewritten by the next block of topics
+    }
+    if (!pair_word) return;
+    const uint64_t ptotal = *sub_total;
+    uint64_t np = ptotal < sub_cap ? ptotal : sub_cap;   // pairs past sub_cap were dropped there
+    if (pair_cap < np) np = pair_cap;
+    for (uint64_t p = (uint64_t)blockIdx.x * PKBLOCK + threadIdx.x; p < np; p += (uint64_t)gridDim.x * PKBLOCK)
+        pair_word[p] = sub_deliver[p];
+}
+
+hipError_t launch_publish_pack_words(uint32_t n, const uint32_t* count, const uint64_t* off,
+                                     const uint32_t* slot_word, uint64_t out_cap, const uint64_t* total,
+                                     const uint32_t* sub_deliver, uint64_t sub_cap, const uint64_t* sub_total,
+                                     const uint64_t* doff, uint32_t* pick_word, uint64_t deliv_cap,
+                                     uint32_t* pair_word, uint64_t pair_cap, hipStream_t st, const uint64_t* gate) {
+    if (n == 0) return hipSuccess;
+    const uint64_t pc = pair_word ? (sub_cap < pair_cap ? sub_cap : pair_cap) : 0;
+    const uint64_t dc = out_cap < deliv_cap ? out_cap : deliv_cap;
+    if (dc == 0 && pc == 0) return hipSuccess;
+    // the grid of launch_publish_pack
+    const uint64_t nblk = ((uint64_t)n + PKBLOCK - 1) / PKBLOCK;
+    uint64_t split = (dc + nblk * 4 * PKBLOCK - 1) / (nblk * 4 * PKBLOCK);
+    split = split < 1 ? 1 : split > 64 ? 64 : split;
+    uint64_t grid = nblk * split;
+    const uint64_t pgrid = (pc + 4 * PKBLOCK - 1) / (4 * PKBLOCK);
+    if (pgrid > grid) grid = pgrid;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(tm_publish_pack_words, dim3((uint32_t)grid), dim3(PKBLOCK), 0, st, n, count, off, slot_word,
+                       out_cap, total, sub_deliver, sub_cap, sub_total, doff, pick_word, deliv_cap, pair_word, pair_cap,
+                       (uint32_t)split, gate);
+    return hipGetLastError();
+}
+
 // ---- the state word of the stream-ordered publish call ----------------------
 // tm_publish_stream_device bounds every stage by a capacity given up front and
 // never reads a total back.  ctl is 8 u64 of its workspace, zeroed first:

@@ -47,6 +47,7 @@
 #include "image.h"
 #include "kernels.h"
 #include "device_bytes.h"
+#include "deliver.h"
 #include "../../include/topicmatch.h"
 
 namespace tmx {
@@ -498,7 +499,141 @@ tm_share_retry_pick(ShareView hv, uint32_t strategy, const uint32_t* __restrict_
     }
 }
 
+// ---- tm_share_pick_words: the delivery word of every $share pick ----
+//
+// emqx_shared_sub:dispatch/4 sends the picked member the same {dispatch, Topic,
+// Msg} (:121-140) and that member's session runs handle_dispatch/3
+// (src/emqx_session.erl:667-684): the word of deliver.h over the member's
+// option entry for the set's topic (ShareView::opt, parallel to the pool).
+// A post-pass over the planes of a publish call, stateless: it reads pick, no
+// cursor and no sticky entry, so it serves every strategy and a rerun.  The
+// slot walk is tm_share_lookup's (blocks of 256 topics), with every lane of a
+// wave kept in the loop so that the wave can scan together:
+//   no pick              -> TM_NO_WORD
+//   set of <= 8 members  -> the slot's own lane scans its segment
+//   wider set            -> the wave takes the slot: 64 members per step, the
+//                           hit's position from a ballot; the lanes of the
+//                           wave that wait for the same (segment, member) take
+//                           the answer with it
+//   member not in the segment (a stuck member that left its set, or a set an
+//   intervening commit removed) -> TM_NO_WORD: the caller's own lookup
+// One plain store per live slot; holes and slots at or past min(*dtotal,
+// slots) are not written.
+constexpr uint32_t PICKWORD_LANE_SCAN = 8;   // sets up to this many members are scanned by their slot's lane
+
+__global__ void __launch_bounds__(HBLOCK)
+tm_share_pick_words(ShareView hv, uint32_t local_target, const uint8_t* __restrict__ bytes,
+                    const uint64_t* __restrict__ off, uint32_t n, const uint32_t* __restrict__ acount,
+                    const uint64_t* __restrict__ aoff, const uint32_t* __restrict__ to,
+                    const uint32_t* __restrict__ tg, const uint32_t* __restrict__ pick, uint64_t slots,
+                    const uint32_t* __restrict__ pub_flags, const uint32_t* __restrict__ pub_from, uint32_t flags,
+                    uint32_t* __restrict__ pick_word, const uint64_t* __restrict__ dtotal,
+                    const uint64_t* __restrict__ gate) {
+    __shared__ uint64_t lds_inc[HBLOCK];   // inclusive prefix of the block's spans
+    __shared__ uint64_t lds_scan[HBLOCK / 64];
+    if (gate && *gate) return;   // an earlier stage of a stream-ordered publish overflowed (wave-uniform)
+    if (dtotal) {
+        const uint64_t r = *dtotal;
+        if (r < slots) slots = r;
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t t0 = blockIdx.x * HBLOCK;
+    const uint32_t tn = n - t0 < (uint32_t)HBLOCK ? n - t0 : (uint32_t)HBLOCK;
+    const uint32_t t = t0 + threadIdx.x;
+    const uint64_t span = threadIdx.x < tn ? aoff[t + 1] - aoff[t] : 0ull;
+    uint64_t agg;
+    const uint64_t ex = block_exclusive_scan<HBLOCK>(span, lds_scan, agg);
+    lds_inc[threadIdx.x] = ex + span;
+    __syncthreads();
+    const uint64_t base = aoff[t0];
+    // jb is block-uniform: every lane stays in the loop for the wave's ballots
+    for (uint64_t jb = 0; jb < agg; jb += HBLOCK) {
+        const uint64_t j = jb + threadIdx.x;
+        const uint64_t g = base + j;
+        bool live = j < agg && g < slots;   // deliveries at or past the caller's capacity were dropped
+        uint32_t tl = t0, pk = TM_NO_MEMBER_ID, c = 0, sg = 0;
+        if (live) {
+            uint32_t lo = 0, hi = tn - 1;   // local topic of slot j: the first with inclusive prefix > j
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (lds_inc[mid] > j) hi = mid;
+                else lo = mid + 1;
+            }
+            tl = t0 + lo;
+            live = g - aoff[tl] < acount[tl];   // else a hole aggre's usort left
+        }
+        if (live) pk = pick[g];
+        if (pk != TM_NO_MEMBER_ID) {
+            const uint32_t gt = tg[g];
+            if (gt != local_target) {   // node() is never a group (as tm_share_lookup)
+                const uint32_t id = to[g];
+                uint32_t key = 0xFFFFFFFFu;
+                bool keyed;
+                if (id == TM_ROUTE_TOPIC_ID) {
+                    keyed = share_topic_lookup(hv, bytes, off[tl], (uint32_t)(off[tl + 1] - off[tl]), key);
+                } else {
+                    if (id < hv.n_filters) key = hv.fx[id];
+                    keyed = key != 0xFFFFFFFFu;
+                }
+                if (keyed) {
+                    for (uint64_t s = share_set_hash(gt, key) & hv.set_mask;; s = (s + 1) & hv.set_mask) {
+                        const ShareSetSlot e = hv.sets[s];
+                        if (e.count == 0) break;
+                        if (e.tg == gt && e.xid == key) {
+                            c = e.count;
+                            sg = e.seg;
+                            break;
+                        }
+                    }
+                }
+            }
+        }
+        uint32_t k = 0xFFFFFFFFu;   // the pick's position in its segment
+        if (c && c <= PICKWORD_LANE_SCAN) {
+            for (uint32_t i = 0; i < c; ++i)
+                if (hv.pool[sg + i] == pk) k = i;   // no break: at most 8 independent loads, and a member
+                                                    // is in its set once, so at most one i matches
+        }
+        uint64_t need = __ballot(c > PICKWORD_LANE_SCAN);
+        while (need) {
+            const int src = (int)__builtin_ctzll(need);
+            const uint32_t wc = __shfl(c, src, 64), wsg = __shfl(sg, src, 64), wpk = __shfl(pk, src, 64);
+            uint32_t wk = 0xFFFFFFFFu;
+            for (uint32_t i0 = 0; i0 < wc; i0 += 64) {
+                const uint32_t i = i0 + lane;   // wc < 2^32 - 64 (a pool segment)
+                const bool hit = i < wc && hv.pool[wsg + i] == wpk;
+                const uint64_t b = __ballot(hit);
+                if (b) {
+                    wk = i0 + (uint32_t)__builtin_ctzll(b);
+                    break;
+                }
+            }
+            const bool mine = c > PICKWORD_LANE_SCAN && sg == wsg && pk == wpk;   // src's lane among them
+            if (mine) k = wk;
+            need &= ~__ballot(mine);
+        }
+        if (!live) continue;
+        uint32_t w = TM_NO_WORD;
+        if (k != 0xFFFFFFFFu) {
+            const uint32_t from = pub_from ? pub_from[tl] : NO_SUBSCRIBER;
+            w = deliver_word(hv.opt[sg + k], pub_flags[tl], from != NO_SUBSCRIBER && pk == from, flags);
+        }
+        pick_word[g] = w;
+    }
+}
+
 static inline uint32_t hdiv_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+hipError_t launch_share_pick_words(const ShareView& hv, uint32_t local_target, const uint8_t* bytes,
+                                   const uint64_t* off, uint32_t n, const uint32_t* acount, const uint64_t* aoff,
+                                   const uint32_t* to, const uint32_t* tg, const uint32_t* pick, uint64_t slots,
+                                   const uint32_t* pub_flags, const uint32_t* pub_from, uint32_t flags,
+                                   uint32_t* pick_word, const uint64_t* dtotal, const uint64_t* gate, hipStream_t st) {
+    if (n == 0 || slots == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_share_pick_words, dim3(hdiv_up(n, HBLOCK)), dim3(HBLOCK), 0, st, hv, local_target, bytes,
+                       off, n, acount, aoff, to, tg, pick, slots, pub_flags, pub_from, flags, pick_word, dtotal, gate);
+    return hipGetLastError();
+}
 
 hipError_t launch_share_lookup(const ShareView& hv, uint32_t local_target, const uint8_t* bytes, const uint64_t* off,
                                uint32_t n, const uint32_t* acount, const uint64_t* aoff, const uint32_t* to,

@@ -40,11 +40,15 @@ Published = namedtuple("Published", "deliveries pairs")
 class SharedPublished(Published):
     """a Published (the same two fields, equal to the plain one) with .picks:
     [(To, Group, member | None)] of the $share deliveries in delivery order,
-    None = do_pick/5's `false`"""
+    None = do_pick/5's `false`; and, for a publish with its message,
+    .pick_deliver parallel to .picks: what the picked member's session makes of
+    the message -- False without a member, None = dropped by no-local, else
+    (qos, retain, subid | None)"""
 
-    def __new__(cls, deliveries, pairs, picks):
+    def __new__(cls, deliveries, pairs, picks, pick_deliver=None):
         self = super().__new__(cls, deliveries, pairs)
         self.picks = picks
+        self.pick_deliver = pick_deliver
         return self
 
 
@@ -170,15 +174,28 @@ class Broker:
         member | None)] per $share delivery.  strategy: "round_robin", or
         "hash" / "random" / "keyed" / "sticky" with keys = one u32 per topic
         (erlang:phash2(ClientId), or a uniform draw); default: self.shared.strategy.
-        msgs / upgrade_qos: as publish_many (the picks carry no option word)"""
+        msgs / upgrade_qos: as publish_many; the picks then come with
+        .pick_deliver, from the device's pick words (tm_share_pick_words).  The
+        one case the device does not answer -- a stuck member that left its set
+        -- is looked up here (get_subopts/2 + tm_deliver_word)"""
         topics = list(topics)
         buf, off = pack(topics)
         dv = self._deliver(msgs, len(topics), upgrade_qos)
         out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys,
-                                              deliver=dv)
-        return self._published(topics, out[:9], out[9], out[10] if dv else None)
+                                              deliver=dv, pick_words=dv is not None)
+        return self._published(topics, out[:9], out[9], out[10] if dv else None, out[11] if dv else None, dv)
 
-    def _published(self, topics, out, pick, words=None):
+    def _pick_deliver(self, to, member, word, t, dv):
+        if member == Engine.NO_MEMBER:
+            return False
+        if word == Engine.NO_WORD:                       # the caller's fallback
+            opts = self.engine.sub_get_opts(to, member)
+            pf, fr, fl = dv
+            word = self.engine.deliver_word(Engine.SUBOPT_NONE if opts is None else opts, int(pf[t]),
+                                            int(fr[t]) != Engine.NO_SUBSCRIBER and int(fr[t]) == member, fl)
+        return unpack_deliver(word)
+
+    def _published(self, topics, out, pick, words=None, pick_words=None, dv=None):
         counts, offs, to, tg, nd, scount, soff, sto, sid = out
         names, tnames, res = {}, {}, []
 
@@ -192,6 +209,7 @@ class Broker:
         for t, topic in enumerate(topics):
             dels = []
             picks = None if pick is None else []
+            pdv = None if pick_words is None else []
             for k in range(int(offs[t]), int(offs[t]) + int(counts[t])):
                 g = int(tg[k])
                 if g not in tnames:
@@ -201,11 +219,13 @@ class Broker:
                 if pick is not None and tnames[g][0] == Engine.TARGET_GROUP:
                     m = int(pick[k])
                     picks.append((dels[-1].to, tnames[g][1], None if m == Engine.NO_MEMBER else m))
+                    if pdv is not None:
+                        pdv.append(self._pick_deliver(dels[-1].to, m, int(pick_words[k]), t, dv))
             a = int(soff[t])
             pairs = [(name_of(int(sto[k]), topic), int(sid[k])) for k in range(a, a + int(scount[t]))]
             if words is not None:
                 pairs = [pr + (unpack_deliver(int(words[a + k])),) for k, pr in enumerate(pairs)]
-            res.append(Published(dels, pairs) if pick is None else SharedPublished(dels, pairs, picks))
+            res.append(Published(dels, pairs) if pick is None else SharedPublished(dels, pairs, picks, pdv))
         return res
 
     # route/2's {To, Node} clause and forward/3 — :185-186, :209-216

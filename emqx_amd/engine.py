@@ -795,13 +795,95 @@ class Engine:
         self.lib.tm_debug_check_shares.argtypes = [ctypes.c_void_p]
         return self._check(self.lib.tm_debug_check_shares(self.h), "tm_debug_check_shares")
 
-    def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None, deliver=None):
+    NO_WORD = L.TM_NO_WORD            # pick word: no pick, or a picked member outside its set
+
+    def debug_share_opts(self, group: bytes, topic: bytes):
+        """the option words of a set's members in list order, from the host
+        mirror of the member option pool (diagnostic, tm_debug_share_opts)"""
+        n = ctypes.c_uint32()
+        c = 16
+        while True:
+            out = np.zeros(max(c, 1), dtype=np.uint32)
+            rc = self.lib.tm_debug_share_opts(self.h, group, len(group), topic, len(topic), _ptr(out), c,
+                                              ctypes.byref(n))
+            if rc == L.TM_ENOSPC:
+                c = n.value
+                continue
+            self._check(rc, "tm_debug_share_opts")
+            return [int(x) for x in out[: n.value]]
+
+    def share_pick_words(self, buf, off, counts, offs, to, target, pick, deliver, total=None, out_cap=None,
+                         pick_word=None):
+        """tm_share_pick_words over the host planes match_publish_batch
+        returned -> pick_word u32 (one per delivery slot): the delivery word of
+        every $share pick, NO_WORD for a slot without a pick and for a picked
+        member that is not in its set.  deliver=(pub_flags u32[n], pub_from
+        u32[n] | None, flags).  total: the route total (default len(to));
+        out_cap: the planes' capacity (default len(to)).  pick_word: the array
+        to write into (holes and slots past the bound keep what it holds)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        to = np.ascontiguousarray(to, dtype=np.uint32)
+        target = np.ascontiguousarray(target, dtype=np.uint32)
+        pick = np.ascontiguousarray(pick, dtype=np.uint32)
+        n = len(off) - 1
+        pf, fr, fl = self._host_deliver(deliver, n)
+        total = len(to) if total is None else total
+        out_cap = len(to) if out_cap is None else out_cap
+        live = min(total, out_cap)
+        own = pick_word is None
+        if own:
+            pick_word = np.full(max(live, 1), L.TM_NO_WORD, dtype=np.uint32)
+        elif pick_word.dtype != np.uint32 or not pick_word.flags.c_contiguous or len(pick_word) < live:
+            raise ValueError("pick_word: a contiguous u32 array of at least min(total, out_cap) words")
+        dv = self._deliver_struct(_ptr(pf), _ptr(fr), fl, None)
+        rc = self.lib.tm_share_pick_words(self.h, _ptr(buf), _ptr(off), n, _ptr(counts), _ptr(offs), _ptr(to),
+                                          _ptr(target), _ptr(pick), out_cap, total, ctypes.byref(dv),
+                                          _ptr(pick_word))
+        self._check(rc, "tm_share_pick_words")
+        return pick_word[:live] if own else pick_word
+
+    def share_pick_words_device(self, d_bytes, d_off, n, d_counts, d_offs, d_to, d_target, d_pick, out_cap, d_total,
+                                deliver, d_pick_word, stream=None):
+        """tm_share_pick_words_device over device pointers (tensors or ints;
+        None = NULL): deliver=(d_pub_flags, d_pub_from | None, flags)"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        dv = None
+        if deliver is not None:
+            dv = ctypes.byref(self._deliver_struct(p(deliver[0]), p(deliver[1]), int(deliver[2]),
+                                                   p(deliver[3]) if len(deliver) > 3 else None))
+        rc = self.lib.tm_share_pick_words_device(self.h, p(d_bytes), p(d_off), n, p(d_counts), p(d_offs), p(d_to),
+                                                 p(d_target), p(d_pick), out_cap, p(d_total), dv, p(d_pick_word), st)
+        return self._check(rc, "tm_share_pick_words_device")
+
+    def match_publish_batch(self, buf, off, strategy, keys=None, out_cap=None, sub_cap=None, deliver=None,
+                            pick_words=False):
         """match_dispatch_batch's tuple plus pick u32 (one per delivery slot):
         the member picked for a $share delivery, NO_MEMBER otherwise.
         strategy SHARE_KEYED and SHARE_STICKY take keys (u32[n]);
         SHARE_ROUND_ROBIN none.  A short out_cap / sub_cap: as
         match_dispatch_batch (no cursor moves, no sticky entry is stored).
-        deliver: as match_dispatch_batch, sub_deliver goes last."""
+        deliver: as match_dispatch_batch, sub_deliver goes last.
+        pick_words=True (with deliver): the tuple gains, after sub_deliver,
+        pick_word u32 (one per delivery slot) from the share_pick_words
+        post-pass.  That is a second, synchronous device call (the planes go
+        up again) on the epoch current at that moment: a commit between the
+        two calls changes the words, not the picks."""
+        if pick_words:
+            if deliver is None:
+                raise ValueError("pick_words needs deliver")
+            res = self.match_publish_batch(buf, off, strategy, keys=keys, out_cap=out_cap, sub_cap=sub_cap,
+                                           deliver=deliver)
+            words = self.share_pick_words(buf, off, res[0], res[1], res[2], res[3], res[9], deliver)
+            return res + (words[: len(res[2])],)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         n = len(off) - 1
@@ -948,6 +1030,56 @@ class Engine:
                                                p(d_workspace), workspace_bytes, p(d_hdr), p(d_doff), p(d_sub_off),
                                                p(d_deliv), p(d_pairs), st)
         return self._check(rc, "tm_publish_stream_device")
+
+    def publish_stream_opts_workspace_bytes(self, n, topic_bytes, caps):
+        """the workspace need of publish_stream_opts_device; caps: (ids, routes, pairs, rr)"""
+        c = L.TmPublishCaps(*[int(x) for x in caps])
+        return int(self.lib.tm_publish_stream_opts_workspace_bytes(self.h, n, topic_bytes, ctypes.byref(c)))
+
+    def publish_stream_opts_device(self, d_bytes, d_off, n, topic_bytes, strategy, d_keys, cursors, caps,
+                                   d_workspace, workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, deliver,
+                                   d_pick_word, stream=None):
+        """tm_publish_stream_opts_device: publish_stream_device with the
+        delivery words.  deliver=(d_pub_flags, d_pub_from | None, flags,
+        d_pair_word): d_pair_word (caps.pairs words) is written parallel to
+        d_pairs, d_pick_word (caps.routes words) parallel to d_deliv"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        c = L.TmPublishCaps(*[int(x) for x in caps])
+        dv = None
+        if deliver is not None:
+            dv = ctypes.byref(self._deliver_struct(p(deliver[0]), p(deliver[1]), int(deliver[2]), p(deliver[3])))
+        rc = self.lib.tm_publish_stream_opts_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, strategy, p(d_keys),
+                                                    cursors.h if cursors is not None else None, ctypes.byref(c),
+                                                    p(d_workspace), workspace_bytes, p(d_hdr), p(d_doff),
+                                                    p(d_sub_off), p(d_deliv), p(d_pairs), dv, p(d_pick_word), st)
+        return self._check(rc, "tm_publish_stream_opts_device")
+
+    def publish_pack_opts(self, n, d_counts, d_offs, d_to, d_target, d_ndisp, d_pick, out_cap, d_total, d_sub_off,
+                          d_sub_to, d_sub_id, sub_cap, d_sub_total, d_hdr, d_doff, d_deliv, deliv_cap, d_pairs,
+                          pair_cap, d_sub_deliver, d_pick_word_slots, d_pair_word, d_pick_word, stream=None):
+        """tm_publish_pack_opts_device: publish_pack plus the two dense word
+        planes (d_pair_word parallel to d_pairs, d_pick_word parallel to
+        d_deliv) from the publish call's pair words and the pick-word pass's
+        slot plane"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_publish_pack_opts_device(self.h, n, p(d_counts), p(d_offs), p(d_to), p(d_target), p(d_ndisp),
+                                                  p(d_pick), out_cap, p(d_total), p(d_sub_off), p(d_sub_to),
+                                                  p(d_sub_id), sub_cap, p(d_sub_total), p(d_hdr), p(d_doff),
+                                                  p(d_deliv), deliv_cap, p(d_pairs), pair_cap, p(d_sub_deliver),
+                                                  p(d_pick_word_slots), p(d_pair_word), p(d_pick_word), st)
+        return self._check(rc, "tm_publish_pack_opts_device")
 
     # walk variants (A/B knobs of tm_walk_queue): one global dequeue head, or
     # per-XCD heads over contiguous ranges of the batch

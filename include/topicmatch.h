@@ -686,8 +686,9 @@ int tm_sub_get_opts(tm_engine* e, const uint8_t* topic, uint32_t tlen, uint32_t 
  *   bits 0-1 delivered QoS, bit 2 retain flag, bit 3 TM_DELIVER_DROP (dropped by
  *   no-local: the word is then exactly 8), bits 4-31 subid
  * A dropped pair stays in the pair arrays; every other output is element for
- * element what the call without options returns.  $share picks get no word
- * (the caller looks a picked member's options up itself).
+ * element what the call without options returns.  The $share picks get their
+ * words from a post-pass over the same planes (tm_share_pick_words, below) and
+ * from tm_publish_stream_opts_device.
  *
  * The struct lives on the host; its pointers are host pointers in the host
  * forms and device pointers in the *_device forms.  `reserved` must be 0. */
@@ -878,6 +879,58 @@ int tm_match_publish_batch_opts_device(tm_engine* e, const uint8_t* d_topic_byte
                                        uint64_t* d_sub_total, uint32_t strategy, const uint32_t* d_pub_key,
                                        uint32_t* d_out_pick, const tm_deliver* deliver, void* hip_stream);
 
+/* ---- the delivery word of a $share pick ---------------------------------------
+ * (emqx_amd/csrc/share.hip tm_share_pick_words)  emqx_shared_sub:dispatch/4
+ * sends the picked member the same {dispatch, Topic, Msg}
+ * (src/emqx_shared_sub.erl:121-140) and that member's session runs the same
+ * handle_dispatch/3 (src/emqx_session.erl:667-684).  A member id is the
+ * subscriber id, so the engine keeps, parallel to the member pool, the
+ * emqx_suboption entry of (set topic, member) -- written by tm_share_add, kept
+ * by tm_share_del / tm_share_member_down, and refreshed by tm_sub_add_opts,
+ * tm_sub_set_opts and tm_sub_del, in whichever order the two tables are fed --
+ * and this post-pass over the planes a publish call left (as tm_forward_plan is
+ * one) writes, for every live slot s of topic t (inside its topic's count and
+ * below min(total, out_cap)):
+ *   pick[s] == TM_NO_MEMBER  -> TM_NO_WORD
+ *   otherwise                -> tm_deliver_word(the entry of (To of s, pick[s]),
+ *                               pub_flags[t], pub_from[t] != TM_NO_SUBSCRIBER &&
+ *                               pick[s] == pub_from[t], flags)
+ * A valid word never equals TM_NO_WORD (its QoS field would be 3).  Holes and
+ * slots at or past the bound are not written.  The pass is stateless: it reads
+ * the picks, no cursor and no sticky entry, so it serves every strategy and may
+ * be run again.
+ *
+ * THE ONE CASE THE DEVICE DOES NOT ANSWER: the picked member is not in the
+ * slot's set.  That is a TM_SHARE_STICKY member that unsubscribed from its set
+ * and is still picked, as the reference allows (is_active_sub/2 tests no
+ * membership), or a set that a commit between the publish call and this one
+ * removed.  Its word is TM_NO_WORD and the caller falls back to
+ * tm_sub_get_opts + tm_deliver_word.
+ *
+ * deliver: pub_flags / pub_from / flags as in tm_deliver; sub_deliver is unused
+ * and must be NULL.  The pass reads the share image of the CURRENT epoch (it
+ * commits pending changes as every batch call does), so run it before a
+ * commit that follows the publish call.  TM_EINVAL: a null offset array or
+ * total, a null plane with out_cap > 0, a NULL deliver, a NULL pub_flags with
+ * n > 0, a non-NULL sub_deliver, an unknown flag; in the host form also a
+ * pub_flags entry whose QoS is 3 (the device form does not validate them).
+ * TM_EDEVICE on a host-only engine. */
+#define TM_NO_WORD 0xFFFFFFFFu
+/* over device planes, stream-ordered on hip_stream: no read-back, no host
+ * wait; on the replica that owns d_off */
+int tm_share_pick_words_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off, uint32_t n,
+                               const uint32_t* d_count, const uint64_t* d_off, const uint32_t* d_to,
+                               const uint32_t* d_target, const uint32_t* d_pick, uint64_t out_cap,
+                               const uint64_t* d_total, const tm_deliver* deliver, uint32_t* d_pick_word,
+                               void* hip_stream);
+/* the same over the host planes tm_match_publish_batch[_opts] returned (total =
+ * its *out_needed): uploads, runs, copies the words back; synchronous, on the
+ * engine's first replica */
+int tm_share_pick_words(tm_engine* e, const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n,
+                        const uint32_t* count, const uint64_t* off, const uint32_t* to, const uint32_t* target,
+                        const uint32_t* pick, uint64_t out_cap, uint64_t total, const tm_deliver* deliver,
+                        uint32_t* pick_word);
+
 /* A publish batch's results as one dense record stream (emqx_amd/csrc/pack.hip),
  * over what tm_match_publish_batch_device (or tm_match_dispatch_batch_device,
  * with d_pick NULL: every pick = TM_NO_MEMBER) left on the device: publish/1 up
@@ -911,6 +964,22 @@ int tm_publish_pack_device(tm_engine* e, uint32_t n, const uint32_t* d_count, co
                            uint64_t sub_cap, const uint64_t* d_sub_total, uint64_t* d_hdr, uint64_t* d_doff,
                            tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
                            void* hip_stream);
+/* tm_publish_pack_device plus two dense word planes beside the records, whose
+ * layouts stay what they are: d_pair_word[p] = d_sub_deliver[p] for p < P (the
+ * pair words of a *_opts publish call) and d_pick_word[d_doff[t] + k] =
+ * d_pick_word_slots[d_off[t] + k] (tm_share_pick_words_device's plane, holes
+ * removed).  Same capacities, same header, same rules: nothing is written at
+ * or past deliv_cap words of d_pick_word or pair_cap words of d_pair_word, and
+ * when the batch does not fit the word contents are unspecified.  TM_EINVAL
+ * besides the plain pack's: a null word plane with its capacities non-zero. */
+int tm_publish_pack_opts_device(tm_engine* e, uint32_t n, const uint32_t* d_count, const uint64_t* d_off,
+                                const uint32_t* d_to, const uint32_t* d_target, const uint32_t* d_ndisp,
+                                const uint32_t* d_pick, uint64_t out_cap, const uint64_t* d_total,
+                                const uint64_t* d_sub_off, const uint32_t* d_sub_to, const uint32_t* d_sub_id,
+                                uint64_t sub_cap, const uint64_t* d_sub_total, uint64_t* d_hdr, uint64_t* d_doff,
+                                tm_delivery* d_deliv, uint64_t deliv_cap, tm_pair* d_pairs, uint64_t pair_cap,
+                                const uint32_t* d_sub_deliver, const uint32_t* d_pick_word_slots,
+                                uint32_t* d_pair_word, uint32_t* d_pick_word, void* hip_stream);
 
 /* ---- forward/3: a batch's remote-node deliveries, one bundle per node ---------
  * (emqx_amd/csrc/forward.hip)  The second clause of route/2
@@ -1070,6 +1139,38 @@ int tm_publish_stream_device(tm_engine* e, const uint8_t* d_topic_bytes, const u
                              uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
                              tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream);
 
+/* tm_publish_stream_device with the delivery words: every send publish/1 makes
+ * for the batch comes with its session-side outcome (tm_deliver), the local
+ * pairs and the $share picks alike.
+ *   deliver->sub_deliver  the dense pair-word output, caps.pairs words parallel
+ *                         to d_pairs: word p is what
+ *                         tm_match_publish_batch_opts_device gives pair p
+ *   d_pick_word           the dense pick-word output, caps.routes words parallel
+ *                         to d_deliv: word d_doff[t] + k is tm_share_pick_words'
+ *                         value for that record (TM_NO_WORD without a pick and
+ *                         for a stuck member outside its set)
+ * In state 0, d_hdr, d_doff, d_sub_off, the records and the pairs are bit for
+ * bit what tm_publish_stream_device leaves for the same arguments, and so are
+ * the cursor and sticky effects.  With a state != 0 every guarantee of the
+ * plain call holds, nothing is written at or past caps.pairs / caps.routes
+ * words of the two planes and no cursor or sticky entry has changed.  The call
+ * enqueues only: the count pass stores each slot's publish index, the emit
+ * writes the pair words, the pick-word pass runs once the picks are final and
+ * before the pack, and the cursor or sticky store stays the last kernel.
+ * The workspace need is this call's own (two more planes of caps.routes + 1
+ * words); tm_publish_stream_workspace_bytes is unchanged.  TM_EINVAL: as the
+ * plain call, plus a NULL deliver, a NULL pub_flags with n > 0, a NULL
+ * sub_deliver with caps.pairs > 0, an unknown flag, and a NULL d_pick_word with
+ * caps.routes > 0.  pub_flags is not validated (see the device *_opts forms). */
+uint64_t tm_publish_stream_opts_workspace_bytes(tm_engine* e, uint32_t n, uint64_t topic_bytes,
+                                                const tm_publish_caps* caps);
+int tm_publish_stream_opts_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off, uint32_t n,
+                                  uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                                  tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                                  uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                                  tm_delivery* d_deliv, tm_pair* d_pairs, const tm_deliver* deliver,
+                                  uint32_t* d_pick_word, void* hip_stream);
+
 /* The retry of dispatch/4 (src/emqx_shared_sub.erl:92-111): after a nack, a
  * timeout or a 'DOWN' the broker picks again with the failed members removed.
  * out_pick[i] = pick(Strategy, _, Group_i, Topic_i, FailedSubs_i) of :211-249,
@@ -1187,6 +1288,25 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
 #define TM_BATCHER_ROUND_ROBIN 32u   /* publish mode: round-robin picks, one cursor context per lane */
 #define TM_BATCHER_STREAM 64u   /* publish mode: keyed picks through tm_publish_stream_device (A/B) */
 #define TM_BATCHER_STICKY 128u   /* publish mode: sticky picks, one context per lane */
+/* TM_BATCHER_OPTS (with TM_BATCHER_PUBLISH): the records and the pairs come
+ * with their delivery words (tm_deliver, tm_share_pick_words): every send
+ * publish/1 makes for the publish has its session-side outcome, so a NIF on
+ * the batcher owes no option lookup -- except for a TM_NO_WORD pick, a stuck
+ * member outside its set.  Submits go through tm_batcher_submit_publish_opts,
+ * which brings the publish's pub_flags and pub_from; they go up with the keys
+ * in the lane's one H2D copy.  A lane always runs tm_publish_stream_opts_device,
+ * for keyed picks too (TM_BATCHER_ROUND_ROBIN / TM_BATCHER_STICKY choose the
+ * strategy as before), and the two word planes come back in the same
+ * read-back block as the records, under the same rules (32768-topic
+ * threshold, running-mean capacities, a rerun sized from the header's state).
+ * TM_BATCHER_UPGRADE_QOS (with TM_BATCHER_OPTS): TM_DELIVER_UPGRADE_QOS for
+ * every batch.  tm_batcher_open: TM_EINVAL for TM_BATCHER_OPTS without
+ * TM_BATCHER_PUBLISH and for TM_BATCHER_UPGRADE_QOS without TM_BATCHER_OPTS.
+ * An options batcher refuses tm_batcher_submit and tm_batcher_submit_publish
+ * (TM_EINVAL, nothing queued); a batcher without the flag refuses the options
+ * submit, and behaves exactly as it did. */
+#define TM_BATCHER_OPTS         256u  /* with TM_BATCHER_PUBLISH: records and pairs come with their words */
+#define TM_BATCHER_UPGRADE_QOS  512u  /* with TM_BATCHER_OPTS: TM_DELIVER_UPGRADE_QOS for every batch */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {
@@ -1236,6 +1356,17 @@ int  tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_bat
 /* the same for a TM_BATCHER_PUBLISH batcher; pub_key picks the $share members of this publish */
 int  tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
                                tm_publish_done_fn done, void* ctx, uint64_t* ticket_out);
+/* TM_BATCHER_OPTS: the publish with its message's pub_flags (a QoS of 3:
+ * TM_EINVAL) and pub_from (TM_NO_SUBSCRIBER: none).  The callback gets
+ * pick_word[n_deliv] parallel to deliv and pair_word[n_pairs] parallel to
+ * pairs, valid during the call as the records are; on a failed batch (and on a
+ * host-only engine: TM_EDEVICE) every pointer is NULL and both counts are 0. */
+typedef void (*tm_publish_opts_done_fn)(void* ctx, uint64_t ticket, int status, const tm_delivery* deliv,
+                                        const uint32_t* pick_word, uint32_t n_deliv, const tm_pair* pairs,
+                                        const uint32_t* pair_word, uint32_t n_pairs);
+int  tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
+                                    uint32_t pub_flags, uint32_t pub_from, tm_publish_opts_done_fn done, void* ctx,
+                                    uint64_t* ticket_out);
 /* seal the open batch and wait until every submitted topic has completed */
 int  tm_batcher_flush(tm_batcher* b);
 /* the counters up to sync_ns (TM_BATCHER_STATS_V1_BYTES bytes; max_* untouched) */
