@@ -596,6 +596,12 @@ struct DevState {
     // prefixes, and the host-buffer call's planes and results
     DevBuf w_fflag, w_fpub, w_fpre, w_fscan, w_fpairs, w_fhead, w_fhpre, w_fcounts, w_foff, w_fsscan, w_fin, w_fout;
     DevBuf w_kin;     // pick words (share.hip tm_share_pick_words): the host-buffer call's planes and words
+    // inbox plan (inbox.hip): the pair and slot flags and their prefixes, the
+    // read-back words, the staging records, the (sub, index) pairs and their
+    // sort, the head / pick flags and their prefixes, and the host-buffer
+    // call's planes and results
+    DevBuf w_ipflag, w_ikflag, w_ippre, w_ikpre, w_iscan, w_ictl, w_irec, w_ipairs, w_ihead, w_ihpre, w_icounts,
+        w_ioff, w_isscan, w_iin, w_iout;
     // round-robin cursors, one per set index (0xFFFFFFFF = undefined): outside
     // the image epochs, so a batch continues where the one before it stopped
     // whichever image each was launched on
@@ -652,6 +658,8 @@ struct DevState {
                           &w_hoff, &w_hsscan, &w_hkey, &w_hpick, &w_pscan, &sh_cursor, &sh_sticky, &w_hkplane,
                           &w_htg, &w_hfail, &w_hfoff, &w_hdown, &w_fflag, &w_fpub, &w_fpre, &w_fscan, &w_fpairs,
                           &w_fhead, &w_fhpre, &w_fcounts, &w_foff, &w_fsscan, &w_fin, &w_fout, &w_kin,
+                          &w_ipflag, &w_ikflag, &w_ippre, &w_ikpre, &w_iscan, &w_ictl, &w_irec, &w_ipairs, &w_ihead,
+                          &w_ihpre, &w_icounts, &w_ioff, &w_isscan, &w_iin, &w_iout,
                           &hp_bytes[0], &hp_bytes[1], &hp_off[0], &hp_off[1], &hp_ids[0], &hp_ids[1], &hp_outoff[0],
                           &hp_outoff[1], &hp_total[0], &hp_total[1]})
             b->release();
@@ -3573,6 +3581,109 @@ struct tm_engine {
         d.rw_release(st);
     }
 
+    // the planes of an inbox plan (inbox.hip): the pairs of the local dispatch,
+    // and the picks over the deliveries CSR (pick == null: none, the rest unread)
+    struct InboxPlanes {
+        const uint64_t* sub_off;
+        const uint32_t *sub_to, *sub_id, *sub_word;
+        uint64_t sub_cap;
+        const uint64_t* sub_total;
+        const uint32_t* count;
+        const uint64_t* off;
+        const uint32_t *to, *pick, *pick_word;
+        uint64_t out_cap;
+        const uint64_t* total;
+    };
+    // A batch's local sends grouped per subscriber.  The caps are the planes'
+    // capacities (the flag scans run over them).  One 24 B read-back, the send
+    // counts and the largest id among the sends, sizes the sort.  No image is
+    // read: no pin, no note_use.
+    static void inbox_plan(DevState& d, uint32_t n, const InboxPlanes& a, uint64_t* hdr, void* inbox,
+                           uint64_t inbox_cap, uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word,
+                           uint64_t ent_cap, hipStream_t st) {
+        const uint64_t pcap = a.sub_cap, kcap = a.pick ? a.out_cap : 0;
+        if (n == 0 || (pcap == 0 && kcap == 0)) {
+            HIPCHK(hipMemsetAsync(hdr, 0, TM_INBOX_HDR_WORDS * 8, st));
+            return;
+        }
+        d.rw_drain();
+        d.w_ictl.ensure(32);
+        d.w_ipflag.ensure((size_t)pcap * 4 + 4);
+        d.w_ikflag.ensure((size_t)kcap * 4 + 4);
+        d.w_ippre.ensure((size_t)(pcap + 1) * 8);
+        d.w_ikpre.ensure((size_t)(kcap + 1) * 8);
+        d.w_iscan.ensure(scan_tmp_elems((uint32_t)std::max(pcap, kcap)) * 8 + 8);
+        uint64_t* ctl = d.w_ictl.as<uint64_t>();   // {pair sends, pick sends, largest id}
+        uint32_t* pflag = d.w_ipflag.as<uint32_t>();
+        uint32_t* kflag = d.w_ikflag.as<uint32_t>();
+        uint64_t* PP = d.w_ippre.as<uint64_t>();
+        uint64_t* PK = d.w_ikpre.as<uint64_t>();
+        uint32_t* maxid = reinterpret_cast<uint32_t*>(ctl + 2);
+        HIPCHK(hipMemsetAsync(ctl, 0, 24, st));
+        if (pcap) {
+            HIPCHK(hipMemsetAsync(pflag, 0, (size_t)pcap * 4, st));   // the pairs the flag pass does not reach
+            HIPCHK(launch_inbox_flag(false, n, a.sub_off, nullptr, a.sub_id, a.sub_word, pcap, a.sub_total, pflag,
+                                     maxid, st));
+            HIPCHK(launch_scan0(pflag, (uint32_t)pcap, PP, PP + pcap, d.w_iscan.as<uint64_t>(), st));
+            HIPCHK(hipMemcpyAsync(ctl, PP + pcap, 8, hipMemcpyDeviceToDevice, st));
+        }
+        if (kcap) {
+            HIPCHK(hipMemsetAsync(kflag, 0, (size_t)kcap * 4, st));
+            HIPCHK(launch_inbox_flag(true, n, a.off, a.count, a.pick, a.pick_word, kcap, a.total, kflag, maxid, st));
+            HIPCHK(launch_scan0(kflag, (uint32_t)kcap, PK, PK + kcap, d.w_iscan.as<uint64_t>(), st));
+            HIPCHK(hipMemcpyAsync(ctl + 1, PK + kcap, 8, hipMemcpyDeviceToDevice, st));
+        }
+        uint64_t back[3] = {0, 0, 0};
+        HIPCHK(hipMemcpyAsync(back, ctl, 24, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t m64 = back[0] + back[1];
+        if (m64 == 0) {
+            HIPCHK(hipMemsetAsync(hdr, 0, TM_INBOX_HDR_WORDS * 8, st));
+            d.rw_release(st);
+            return;
+        }
+        if (m64 >= 0xFFFFFFFEull) {
+            d.rw_release(st);
+            throw RangeError("inbox: more than 2^32 - 2 sends in one batch");
+        }
+        const uint32_t m = (uint32_t)m64, top = (uint32_t)back[2];
+        uint32_t bits = 0;
+        while (bits < 32 && ((uint64_t)1 << bits) <= top) ++bits;   // keys 0 .. top
+        const uint32_t passes = std::max(1u, (bits + 7) / 8), pc = presort_counts(m);
+        d.w_irec.ensure((size_t)m * 16);
+        d.w_ipairs.ensure((size_t)m * 16);
+        d.w_ihead.ensure((size_t)m * 8);
+        d.w_ihpre.ensure((size_t)(m + 1) * 16);
+        d.w_icounts.ensure((size_t)pc * 4);
+        d.w_ioff.ensure((size_t)(pc + 1) * 8);
+        d.w_isscan.ensure(std::max(scan_tmp_elems(pc), scan_tmp_elems(m)) * 8 + 8);
+        void* rec = d.w_irec.p;
+        uint32_t* k0 = d.w_ipairs.as<uint32_t>();
+        uint32_t *v0 = k0 + m, *k1 = v0 + m, *v1 = k1 + m;
+        uint64_t* stmp = d.w_isscan.as<uint64_t>();
+        if (back[0])
+            HIPCHK(launch_inbox_emit(false, n, a.sub_off, a.sub_id, a.sub_to, a.sub_word, pcap, a.sub_total, pflag, PP,
+                                     kcap ? PK : nullptr, a.off, kcap, rec, k0, v0, st));
+        if (back[1])
+            HIPCHK(launch_inbox_emit(true, n, a.off, a.pick, a.to, a.pick_word, kcap, a.total, kflag, PK,
+                                     pcap ? PP : nullptr, a.sub_off, pcap, rec, k0, v0, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, m, passes, d.w_icounts.as<uint32_t>(), d.w_ioff.as<uint64_t>(), stmp,
+                                 st));
+        if (passes & 1u) {   // an odd number of passes left the pairs in (k1, v1)
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        uint32_t* head = d.w_ihead.as<uint32_t>();
+        uint32_t* pk = head + m;
+        uint64_t* H = d.w_ihpre.as<uint64_t>();
+        uint64_t* K = H + m + 1;
+        HIPCHK(launch_inbox_gather(k0, v0, rec, m, ent_pub, ent_to, ent_word, ent_cap, head, pk, st));
+        HIPCHK(launch_scan0(head, m, H, H + m, stmp, st));
+        HIPCHK(launch_scan0(pk, m, K, K + m, stmp, st));
+        HIPCHK(launch_inbox_records(k0, head, H, K, m, hdr, inbox, inbox_cap, st));
+        d.rw_release(st);
+    }
+
     // ---- tm_publish_stream_device: publish/1 up to the sends without a host wait ----
     // Every intermediate of run_dispatch + the pack lives in the caller's
     // workspace, cut up here (256 B aligned pieces, each a monotone function of
@@ -3988,6 +4099,21 @@ int batch_call(tm_engine* e, const std::vector<DevState*>& reps, W&& work, P&& p
         post();
         return rc;
     });
+}
+// a call on replica d that reads no image (the inbox plan): the replica's batch
+// lock for its workspaces, no commit and no pin
+template <class W>
+int plane_call(tm_engine* e, DevState& d, W&& work) {
+    std::unique_lock<std::mutex> held(d.bmu);
+    std::string err;
+    const int rc = catching(err, work);
+    held.unlock();
+    if (!err.empty())
+        return guarded(e, [&] {
+            e->last_error = err;
+            return rc;
+        });
+    return rc;
 }
 int no_device(tm_engine* e, const char* what) {
     return guarded(e, [&] {
@@ -5606,6 +5732,135 @@ int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint6
         HIPCHK(hipStreamSynchronize(s));
         return (M > pub_cap || G > group_cap) ? TM_ENOSPC : TM_OK;
     }, [] {});
+}
+
+static_assert(sizeof(tm_inbox) == 16, "inbox.hip stores 16 B subscriber records");
+static_assert(TM_INBOX_PICK == 0x80000000u && TM_DELIVER_DROP == tmx::DELIVER_DROP && TM_NO_MEMBER == 0xFFFFFFFFu,
+              "inbox.hip's kind bit, drop word and no-pick value");
+
+// what both forms of the inbox plan refuse before they look for a device
+static int inbox_args(tm_engine* e, uint32_t n, const void* hdr, const void* sub_off, const void* sub_to, const void* sub_id,
+               uint64_t sub_cap, const void* count, const void* off, const void* to, const void* pick,
+               const void* pick_word, uint64_t out_cap, bool total_ok, const void* inbox, uint64_t inbox_cap,
+               const void* ent_pub, const void* ent_to, uint64_t ent_cap) {
+    if (!hdr || !sub_off || (sub_cap && (!sub_to || !sub_id)) || (pick_word && !pick) ||
+        (pick && (!off || !total_ok || (n && !count) || (out_cap && !to))) || (inbox_cap && !inbox) ||
+        (ent_cap && (!ent_pub || !ent_to)))
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (sub_cap >= 0xFFFFFFFEull || (pick && out_cap >= 0xFFFFFFFEull) || n >= 0x80000000u)
+        return guarded(e, [&]() -> int {
+            throw RangeError("inbox: a capacity of 2^32 - 2 positions or more, or 2^31 topics or more, in one batch");
+        });
+    if (e->devs.empty()) return no_device(e, "inbox plan");
+    return TM_OK;
+}
+
+int tm_inbox_plan_device(tm_engine* e, uint32_t n, const uint64_t* d_sub_off, const uint32_t* d_sub_to,
+                         const uint32_t* d_sub_id, const uint32_t* d_sub_deliver, uint64_t sub_cap,
+                         const uint64_t* d_sub_total, const uint32_t* d_count, const uint64_t* d_off,
+                         const uint32_t* d_to, const uint32_t* d_pick, const uint32_t* d_pick_word, uint64_t out_cap,
+                         const uint64_t* d_total, uint64_t* d_hdr, tm_inbox* d_inbox, uint64_t inbox_cap,
+                         uint32_t* d_ent_pub, uint32_t* d_ent_to, uint32_t* d_ent_word, uint64_t ent_cap,
+                         void* hip_stream) {
+    if (!d_sub_total) return TM_EINVAL;
+    if (int rc = inbox_args(e, n, d_hdr, d_sub_off, d_sub_to, d_sub_id, sub_cap, d_count, d_off, d_to, d_pick,
+                            d_pick_word, out_cap, d_total != nullptr, d_inbox, inbox_cap, d_ent_pub, d_ent_to, ent_cap))
+        return rc;
+    DevState& d = *e->replica_for(d_sub_off);
+    return plane_call(e, d, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        const tm_engine::InboxPlanes a{d_sub_off, d_sub_to, d_sub_id, d_sub_deliver, sub_cap, d_sub_total, d_count,
+                                       d_off,     d_to,     d_pick,   d_pick_word,   out_cap, d_total};
+        tm_engine::inbox_plan(d, n, a, d_hdr, d_inbox, inbox_cap, d_ent_pub, d_ent_to, d_ent_word, ent_cap, st);
+        return TM_OK;
+    });
+}
+
+int tm_inbox_plan(tm_engine* e, uint32_t n, const uint64_t* sub_off, const uint32_t* sub_to, const uint32_t* sub_id,
+                  const uint32_t* sub_deliver, uint64_t sub_cap, uint64_t sub_total, const uint32_t* count,
+                  const uint64_t* off, const uint32_t* to, const uint32_t* pick, const uint32_t* pick_word,
+                  uint64_t out_cap, uint64_t total, uint64_t hdr[TM_INBOX_HDR_WORDS], tm_inbox* inbox,
+                  uint64_t inbox_cap, uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word, uint64_t ent_cap) {
+    if (int rc = inbox_args(e, n, hdr, sub_off, sub_to, sub_id, sub_cap, count, off, to, pick, pick_word, out_cap, true,
+                            inbox, inbox_cap, ent_pub, ent_to, ent_cap))
+        return rc;
+    DevState& d = *e->devs[0];
+    return plane_call(e, d, [&]() -> int {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (sub_off[i + 1] < sub_off[i]) throw ArgError("pair offsets not monotone");
+            if (pick && off[i + 1] < off[i]) throw ArgError("delivery offsets not monotone");
+        }
+        std::memset(hdr, 0, TM_INBOX_HDR_WORDS * 8);
+        // the live positions: what the planes hold
+        const uint64_t pc = std::min(sub_total, sub_cap), kc = pick ? std::min(total, out_cap) : 0;
+        if (n == 0 || (pc == 0 && kc == 0)) return TM_OK;
+        tm_engine::Guard g(d.device);
+        hipStream_t s = d.stream;
+        d.rw_drain();
+        // [sub_off][off][sub_total][total][count][sub_to][sub_id][sub_word][to][pick][pick_word] and
+        // [hdr][inbox][ent_pub][ent_to][ent_word]; no plan has more subscribers or entries than positions
+        const uint64_t all = pc + kc, ic = std::min(inbox_cap, all), ec = std::min(ent_cap, all);
+        const size_t n1 = (size_t)n + 1, o_off = n1 * 8, o_stot = o_off * 2, o_tot = o_stot + 8, o_count = o_tot + 8,
+                     o_sto = o_count + (size_t)n * 4, o_sid = o_sto + (size_t)pc * 4, o_sw = o_sid + (size_t)pc * 4,
+                     o_to = o_sw + (size_t)pc * 4, o_pick = o_to + (size_t)kc * 4, o_pw = o_pick + (size_t)kc * 4;
+        d.w_iin.ensure(o_pw + (size_t)kc * 4 + 16);
+        const size_t q_inbox = TM_INBOX_HDR_WORDS * 8, q_pub = q_inbox + (size_t)ic * 16, q_to = q_pub + (size_t)ec * 4,
+                     q_word = q_to + (size_t)ec * 4;
+        d.w_iout.ensure(q_word + (size_t)ec * 4 + 16);
+        uint8_t* in = d.w_iin.as<uint8_t>();
+        uint8_t* out = d.w_iout.as<uint8_t>();
+        auto up = [&](size_t o, const void* src, size_t bytes) {
+            if (src && bytes) HIPCHK(hipMemcpyAsync(in + o, src, bytes, hipMemcpyHostToDevice, s));
+        };
+        auto u32 = [&](size_t o, const void* given) {
+            return given ? reinterpret_cast<const uint32_t*>(in + o) : nullptr;
+        };
+        up(0, sub_off, n1 * 8);
+        up(o_stot, &pc, 8);
+        up(o_sto, sub_to, (size_t)pc * 4);
+        up(o_sid, sub_id, (size_t)pc * 4);
+        up(o_sw, sub_deliver, (size_t)pc * 4);
+        if (kc) {
+            up(o_off, off, n1 * 8);
+            up(o_tot, &kc, 8);
+            up(o_count, count, (size_t)n * 4);
+            up(o_to, to, (size_t)kc * 4);
+            up(o_pick, pick, (size_t)kc * 4);
+            up(o_pw, pick_word, (size_t)kc * 4);
+        }
+        const tm_engine::InboxPlanes a{reinterpret_cast<const uint64_t*>(in),
+                                       u32(o_sto, sub_to),
+                                       u32(o_sid, sub_id),
+                                       u32(o_sw, sub_deliver),
+                                       pc,
+                                       reinterpret_cast<const uint64_t*>(in + o_stot),
+                                       u32(o_count, kc ? count : nullptr),
+                                       reinterpret_cast<const uint64_t*>(in + o_off),
+                                       u32(o_to, kc ? to : nullptr),
+                                       u32(o_pick, kc ? pick : nullptr),
+                                       u32(o_pw, kc ? pick_word : nullptr),
+                                       kc,
+                                       reinterpret_cast<const uint64_t*>(in + o_tot)};
+        uint64_t* d_hdr = reinterpret_cast<uint64_t*>(out);
+        uint32_t* d_word = ent_word ? reinterpret_cast<uint32_t*>(out + q_word) : nullptr;
+        tm_engine::inbox_plan(d, n, a, d_hdr, out + q_inbox, ic, reinterpret_cast<uint32_t*>(out + q_pub),
+                              reinterpret_cast<uint32_t*>(out + q_to), d_word, ec, s);
+        HIPCHK(hipMemcpyAsync(hdr, d_hdr, TM_INBOX_HDR_WORDS * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t E = hdr[0], S = hdr[1];
+        const uint64_t in_n = std::min(S, ic), en = std::min(E, ec);
+        if (in_n) HIPCHK(hipMemcpyAsync(inbox, out + q_inbox, (size_t)in_n * 16, hipMemcpyDeviceToHost, s));
+        if (en) {
+            HIPCHK(hipMemcpyAsync(ent_pub, out + q_pub, (size_t)en * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(ent_to, out + q_to, (size_t)en * 4, hipMemcpyDeviceToHost, s));
+            if (ent_word) HIPCHK(hipMemcpyAsync(ent_word, out + q_word, (size_t)en * 4, hipMemcpyDeviceToHost, s));
+        }
+        d.rw_release(s);
+        HIPCHK(hipStreamSynchronize(s));
+        return (E > ent_cap || S > inbox_cap) ? TM_ENOSPC : TM_OK;
+    });
 }
 
 static_assert(TM_NO_WORD == 0xFFFFFFFFu && (TM_NO_WORD & 3u) == tmx::SUBOPT_NONE, "a delivery word's QoS is never 3");

@@ -304,6 +304,37 @@ hipError_t launch_forward_groups(const uint32_t* keys, const uint32_t* vals, con
                                  uint32_t m, uint64_t* hdr, void* groups, uint64_t group_cap, uint32_t* pub,
                                  uint64_t pub_cap, hipStream_t st);
 
+// The local sends of a batch regrouped per receiving subscriber (inbox.hip),
+// over the pair planes of the local dispatch and the pick plane over the
+// deliveries CSR (slot geometry as launch_dispatch_count).  Capacities at most
+// 2^32 - 2; the live positions are min(*total, cap).  No image is read.
+//   launch_inbox_flag     picks = false: flag[p] = pair p is a send (word plane given:
+//                         its word is not DELIVER_DROP); picks = true: flag[s] = slot s is
+//                         live, picked, and its word is not DELIVER_DROP.  The caller
+//                         zeroes flag[0, cap) and *maxid first; *maxid = the largest live id
+//   launch_scan0 x 2      PP (sub_cap + 1) and PK (out_cap + 1): the flags' prefixes
+//   launch_inbox_emit     rec[i] = {sub, pub | kind bit 31, to, word} (16 B), keys[i] = sub,
+//                         vals[i] = i, at i = P[position] + Q[the other kind's offset of
+//                         the topic]: topic order, a topic's pairs before its picks
+//   launch_sort_pairs     stable by sub (the bits of *maxid)
+//   launch_inbox_gather   ent_pub / ent_to / ent_word[p] of sorted entry p (p < ent_cap;
+//                         ent_word may be null), head[p], pk[p] (entry p is a pick)
+//   launch_scan0 x 2      H, K (m + 1 u64 each)
+//   launch_inbox_records  hdr[4] = {m, S, pairs, picks}; inbox[g] = {sub, first, count,
+//                         picks} (16 B records, g < inbox_cap)
+hipError_t launch_inbox_flag(bool picks, uint32_t n, const uint64_t* off, const uint32_t* count, const uint32_t* id,
+                             const uint32_t* word, uint64_t cap, const uint64_t* total, uint32_t* flag,
+                             uint32_t* maxid, hipStream_t st);
+hipError_t launch_inbox_emit(bool picks, uint32_t n, const uint64_t* off, const uint32_t* id, const uint32_t* to,
+                             const uint32_t* word, uint64_t cap, const uint64_t* total, const uint32_t* flag,
+                             const uint64_t* P, const uint64_t* Q, const uint64_t* qoff, uint64_t qcap, void* rec,
+                             uint32_t* keys, uint32_t* vals, hipStream_t st);
+hipError_t launch_inbox_gather(const uint32_t* keys, const uint32_t* vals, const void* rec, uint32_t m,
+                               uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word, uint64_t ent_cap,
+                               uint32_t* head, uint32_t* pk, hipStream_t st);
+hipError_t launch_inbox_records(const uint32_t* keys, const uint32_t* head, const uint64_t* H, const uint64_t* K,
+                                uint32_t m, uint64_t* hdr, void* inbox, uint64_t inbox_cap, hipStream_t st);
+
 // A publish batch's results as dense records (pack.hip) over what
 // tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:
 // scan_tmp_elems(n)), deliv[doff[t] + k] = {to, tg, ndisp, pick} of slot

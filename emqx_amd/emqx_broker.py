@@ -252,6 +252,46 @@ class Broker:
                                     [int(x) for x in pub[first:first + count]]))
         return self._published(topics, out, None), forwards
 
+    # dispatch/2's SubPid ! {dispatch, Topic, Msg} and the $share send — :225-236, emqx_shared_sub:121-140
+    def publish_inbox_many(self, topics, msgs=None, strategy=None, keys=None, upgrade_qos=False):
+        """the batch's local sends, one bundle per receiving subscriber ->
+        {subscriber: [(publish index, To bytes | None, word | None, is_pick)]}
+        ordered as the plan is (tm_inbox_plan: publish index, a publish's plain
+        sends before its $share picks, then position).  To None = the publish's
+        own topic.  msgs / upgrade_qos: as publish_many; word is then the
+        delivery word (tm_deliver_word's layout) and the sends no-local drops
+        are left out; without msgs word is None.  strategy / keys: as
+        publish_shared_many.  The one word the device does not answer -- a
+        stuck member that left its set -- is looked up here."""
+        topics = list(topics)
+        buf, off = pack(topics)
+        dv = self._deliver(msgs, len(topics), upgrade_qos)
+        out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys,
+                                              deliver=dv, pick_words=dv is not None)
+        _hdr, inbox, ent_pub, ent_to, ent_word = self.engine.inbox_plan(
+            out[6], out[7], out[8], out[10] if dv else None, out[0], out[1], out[2], out[9],
+            out[11] if dv else None)
+        ids = sorted({int(x) for x in ent_to.tolist()} - {Engine.TOPIC_ROUTE})
+        names = dict(zip(ids, self.engine.filters_bytes(ids))) if ids else {}
+        res = {}
+        for sub, first, count, _picks in inbox.tolist():
+            ents = []
+            for e in range(first, first + count):
+                t, is_pick = int(ent_pub[e]) & ~Engine.INBOX_PICK, bool(int(ent_pub[e]) & Engine.INBOX_PICK)
+                to = int(ent_to[e])
+                word = None if dv is None else int(ent_word[e])
+                if word == Engine.NO_WORD:               # the caller's fallback
+                    opts = self.engine.sub_get_opts(topics[t] if to == Engine.TOPIC_ROUTE else names[to], sub)
+                    pf, fr, fl = dv
+                    word = self.engine.deliver_word(Engine.SUBOPT_NONE if opts is None else opts, int(pf[t]),
+                                                    int(fr[t]) != Engine.NO_SUBSCRIBER and int(fr[t]) == sub, fl)
+                    if word == Engine.DELIVER_DROP:
+                        continue
+                ents.append((t, None if to == Engine.TOPIC_ROUTE else names[to], word, is_pick))
+            if ents:
+                res[sub] = ents
+        return res
+
     def dispatch_forwarded(self, groups, topics):
         """the receiving end of forward/3 (the RPC replaced by a call): groups =
         one bundle of publish_forward_many, topics = that batch's topics (a

@@ -733,6 +733,81 @@ class Engine:
                                              p(d_total), p(d_hdr), p(d_groups), group_cap, p(d_pub), pub_cap, st)
         return self._check(rc, "tm_forward_plan_device")
 
+    # -- the inbox plan: a batch's local sends per subscriber (inbox.hip) -----------
+    INBOX_HDR_WORDS = 4
+    INBOX_PICK = 0x80000000           # ent_pub bit 31: the entry is a pick send
+
+    def inbox_plan(self, sub_off, sub_to, sub_id, sub_deliver=None, counts=None, offs=None, to=None, pick=None,
+                   pick_word=None, sub_total=None, sub_cap=None, total=None, out_cap=None, inbox_cap=None,
+                   ent_cap=None, words=None):
+        """tm_inbox_plan over the host planes match_dispatch_batch /
+        match_publish_batch (+ share_pick_words) returned -> (hdr u64[4] = {E,
+        S, pair sends, pick sends}, inbox u32[S, 4] = rows {sub, first, count,
+        picks}, ent_pub u32[E] (bit 31 = INBOX_PICK on a pick send), ent_to
+        u32[E], ent_word u32[E] | None): the batch's local sends grouped per
+        subscriber.  sub_deliver / pick_word None: no words for that kind;
+        pick None: no pick sends (counts / offs / to unused).  words: whether
+        ent_word is produced (default: when a word plane is given).  sub_total
+        / total: the totals the publish call reported (default the planes'
+        lengths); sub_cap / out_cap: the planes' capacities (default their
+        lengths).  inbox_cap / ent_cap None: retried at the sizes the header
+        reports; given: one call (TopicMatchError TM_ENOSPC when short, with
+        .hdr)."""
+        u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)   # noqa: E731
+        u64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64)   # noqa: E731
+        sub_off, offs = u64(sub_off), u64(offs)
+        sub_to, sub_id, sub_deliver, counts, to, pick, pick_word = (u32(a) for a in (sub_to, sub_id, sub_deliver,
+                                                                                     counts, to, pick, pick_word))
+        n = len(sub_off) - 1
+        plen = 0 if sub_id is None else len(sub_id)
+        klen = 0 if pick is None else len(pick)
+        sub_total = plen if sub_total is None else sub_total
+        sub_cap = plen if sub_cap is None else sub_cap
+        total = klen if total is None else total
+        out_cap = klen if out_cap is None else out_cap
+        if words is None:
+            words = sub_deliver is not None or pick_word is not None
+        ic = 1 << 12 if inbox_cap is None else inbox_cap
+        ec = 1 << 14 if ent_cap is None else ent_cap
+        hdr = np.zeros(self.INBOX_HDR_WORDS, dtype=np.uint64)
+        while True:
+            inbox = np.zeros((max(ic, 1), 4), dtype=np.uint32)
+            ent_pub, ent_to = (np.zeros(max(ec, 1), dtype=np.uint32) for _ in range(2))
+            ent_word = np.zeros(max(ec, 1), dtype=np.uint32) if words else None
+            rc = self.lib.tm_inbox_plan(self.h, n, _ptr(sub_off), _ptr(sub_to), _ptr(sub_id), _ptr(sub_deliver),
+                                        sub_cap, sub_total, _ptr(counts), _ptr(offs), _ptr(to), _ptr(pick),
+                                        _ptr(pick_word), out_cap, total, _ptr(hdr), _ptr(inbox), ic, _ptr(ent_pub),
+                                        _ptr(ent_to), _ptr(ent_word), ec)
+            if rc == L.TM_ENOSPC and (inbox_cap is None or int(hdr[1]) <= ic) and \
+                    (ent_cap is None or int(hdr[0]) <= ec):
+                ic, ec = max(ic, int(hdr[1])), max(ec, int(hdr[0]))
+                continue
+            if rc == L.TM_ENOSPC:
+                e = L.TopicMatchError(rc, "tm_inbox_plan: needs %d subscribers, %d entries" % (hdr[1], hdr[0]))
+                e.hdr = hdr.copy()
+                raise e
+            self._check(rc, "tm_inbox_plan")
+            E, S = int(hdr[0]), int(hdr[1])
+            return hdr, inbox[:S], ent_pub[:E], ent_to[:E], (ent_word[:E] if words else None)
+
+    def inbox_plan_device(self, n, d_sub_off, d_sub_to, d_sub_id, d_sub_deliver, sub_cap, d_sub_total, d_counts,
+                          d_offs, d_to, d_pick, d_pick_word, out_cap, d_total, d_hdr, d_inbox, inbox_cap, d_ent_pub,
+                          d_ent_to, d_ent_word, ent_cap, stream=None):
+        """tm_inbox_plan_device over device pointers (tensors or ints; None =
+        NULL): the plan of the planes a *_batch_device publish call left"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_inbox_plan_device(self.h, n, p(d_sub_off), p(d_sub_to), p(d_sub_id), p(d_sub_deliver),
+                                           sub_cap, p(d_sub_total), p(d_counts), p(d_offs), p(d_to), p(d_pick),
+                                           p(d_pick_word), out_cap, p(d_total), p(d_hdr), p(d_inbox), inbox_cap,
+                                           p(d_ent_pub), p(d_ent_to), p(d_ent_word), ent_cap, st)
+        return self._check(rc, "tm_inbox_plan_device")
+
     # -- emqx_shared_sub: the $share member table and the pick (share.hip) ---------
     NO_MEMBER = 0xFFFFFFFF            # pick: `false`, or not a $share delivery
     SHARE_KEYED, SHARE_ROUND_ROBIN, SHARE_STICKY = 1, 2, 3

@@ -1032,6 +1032,95 @@ int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint6
                     uint64_t hdr[TM_FORWARD_HDR_WORDS], tm_forward_group* groups, uint64_t group_cap,
                     uint32_t* pub, uint64_t pub_cap);
 
+/* ---- the inbox plan: a batch's local sends, one bundle per subscriber ---------
+ * (emqx_amd/csrc/inbox.hip)  dispatch/2 ends in SubPid ! {dispatch, Topic, Msg},
+ * once per subscriber of every delivery (src/emqx_broker.erl:225-236), and
+ * emqx_shared_sub sends the same message to the picked member
+ * (src/emqx_shared_sub.erl:121-140).  Over a batch of publishes one bundle per
+ * receiving session carries the same sends; these two entries regroup what a
+ * dispatch or publish call left (and tm_share_pick_words, when the words are
+ * wanted) into that shape, as tm_forward_plan does for the node side.
+ *
+ * A LOCAL SEND of a batch is one of
+ *   pair send  a pair p < min(*sub_total, sub_cap) of topic t (sub_off[t] <= p <
+ *              sub_off[t+1]): (sub_id[p], t, sub_to[p], word).  With a pair-word
+ *              plane (sub_deliver) word = sub_deliver[p], and a pair whose word
+ *              is exactly TM_DELIVER_DROP (8) is no send.  With a NULL plane
+ *              every pair is a send and no word is reported for pairs.
+ *   pick send  a live slot s of topic t (inside the topic's count[t] and below
+ *              min(*total, out_cap)) with pick[s] != TM_NO_MEMBER: (pick[s], t,
+ *              to[s], word).  With a pick-word plane (the slot plane of
+ *              tm_share_pick_words[_device]) word = pick_word[s]; a pick whose
+ *              word is exactly 8 is no send; a pick whose word is TM_NO_WORD IS
+ *              a send and keeps that word (the sticky member outside its set:
+ *              the caller resolves it as documented there).  With a NULL pick
+ *              plane there are no pick sends, and off / count / to / total and
+ *              out_cap are not read.
+ * The plan is the batch's sends sorted, ascending, by
+ *   1. subscriber id   2. publish index t   3. kind, pair sends before pick sends
+ *   4. position, p of a pair send and s of a pick send:
+ *   hdr[4]      {E sends, S distinct subscribers, pair sends kept, pick sends kept}
+ *   inbox[S]    one record per subscriber, ascending sub: its entries are
+ *               [first, first + count); `picks` of them are pick sends
+ *   ent_pub[E]  the publish index; bit 31 (TM_INBOX_PICK) set on a pick send
+ *   ent_to[E]   To (a filter id, or TM_ROUTE_TOPIC: the publish's own topic)
+ *   ent_word[E] the delivery word (may be NULL: not written).  Without a word
+ *               plane for its kind an entry's word is 0.
+ * The kind of an entry is bit 31 of ent_pub[e]; the publish index is
+ * ent_pub[e] & ~TM_INBOX_PICK, so a batch has fewer than 2^31 topics
+ * (TM_ERANGE).  `picks` is a count only: it cannot place the picks of a run
+ * that spans several publishes.
+ *
+ * ONE DEVIATION FROM THE REFERENCE'S ORDER.  Within one (subscriber, publish)
+ * the reference interleaves a pick with the pairs by delivery slot, because
+ * route/2 folds left over the deliveries (src/emqx_broker.erl:175-192); the
+ * plan puts the publish's pairs first.  The entries concerned are copies of ONE
+ * message under different subscriptions, so no per-subscription order is
+ * affected.  Across publishes every subscriber's entries are in batch order,
+ * which is the order MQTT needs per publisher and topic.
+ *
+ * Nothing is written at or past inbox_cap records or ent_cap entries, and hdr
+ * is exact even when the plan does not fit, so a second call can be sized from
+ * it.  n == 0 or no send: a zero header, nothing else written.
+ *
+ * Device form: device pointers, ordered on hip_stream, on the replica that owns
+ * d_sub_off.  It makes one read-back, a single 24 B copy (one host wait) that
+ * carries the send counts and the largest subscriber id among the sends, to
+ * size the sort: ceil(bits(largest id) / 8) stable radix passes, 1 to 4; ids up
+ * to 0xFFFFFFFE are legal.  The width comes from the planes, not from engine
+ * state: the plan reads no image, pins no epoch, commits nothing, needs no
+ * tm_set_local_node and is correct for any planes, synthetic ones included; a
+ * tm_commit between the publish call and the plan changes nothing.  It is
+ * stateless and may be run again.  sub_cap / out_cap are the planes'
+ * capacities: the scans run over them, so pass what the planes hold.
+ * TM_EINVAL: a null hdr, sub_off or sub_total; a null plane or result array
+ * with its capacity non-zero (ent_word excepted); a pick-word plane without a
+ * pick plane; with a pick plane a null off or total, a null count with n, or a
+ * null to with out_cap.  TM_ERANGE: sub_cap or out_cap at or above 2^32 - 2, n
+ * at or above 2^31, or 2^32 - 2 sends or more.  TM_EDEVICE on a host-only
+ * engine. */
+#define TM_INBOX_HDR_WORDS 4
+#define TM_INBOX_PICK 0x80000000u
+typedef struct tm_inbox { uint32_t sub, first, count, picks; } tm_inbox;   /* 16 B */
+int tm_inbox_plan_device(tm_engine* e, uint32_t n, const uint64_t* d_sub_off, const uint32_t* d_sub_to,
+                         const uint32_t* d_sub_id, const uint32_t* d_sub_deliver, uint64_t sub_cap,
+                         const uint64_t* d_sub_total, const uint32_t* d_count, const uint64_t* d_off,
+                         const uint32_t* d_to, const uint32_t* d_pick, const uint32_t* d_pick_word, uint64_t out_cap,
+                         const uint64_t* d_total, uint64_t* d_hdr, tm_inbox* d_inbox, uint64_t inbox_cap,
+                         uint32_t* d_ent_pub, uint32_t* d_ent_to, uint32_t* d_ent_word, uint64_t ent_cap,
+                         void* hip_stream);
+/* The same over host planes, those tm_match_dispatch_batch[_opts] /
+ * tm_match_publish_batch[_opts] (+ tm_share_pick_words) returned (sub_total =
+ * their *sub_needed, total = their *out_needed; the planes hold min(total, cap)
+ * positions): uploads them, runs the same passes on the engine's first replica
+ * and copies the plan back.  Synchronous.  TM_ENOSPC when E > ent_cap or S >
+ * inbox_cap, hdr exact.  TM_EINVAL also for offsets that are not monotone. */
+int tm_inbox_plan(tm_engine* e, uint32_t n, const uint64_t* sub_off, const uint32_t* sub_to, const uint32_t* sub_id,
+                  const uint32_t* sub_deliver, uint64_t sub_cap, uint64_t sub_total, const uint32_t* count,
+                  const uint64_t* off, const uint32_t* to, const uint32_t* pick, const uint32_t* pick_word,
+                  uint64_t out_cap, uint64_t total, uint64_t hdr[TM_INBOX_HDR_WORDS], tm_inbox* inbox,
+                  uint64_t inbox_cap, uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word, uint64_t ent_cap);
+
 /* ---- publisher contexts: round-robin cursors and sticky entries --------------
  * do_pick_subscriber(Group, Topic, round_robin, _ClientId, Count) keeps its
  * counter in the PUBLISHER's process dictionary, under {shared_sub_round_robin,
