@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libtopicmatch.so")
 TM_OK, TM_EINVAL, TM_ENOSPC, TM_EDEVICE, TM_ENOMEM, TM_ENOENT, TM_ERANGE = 0, -1, -2, -3, -4, -5, -6
 TM_NO_FILTER = 0xFFFFFFFF
 TM_NO_RULE = 0xFFFFFFFF
+TM_ACL_WHO_STACK_MAX = 64   # results a who may hold at once; tm_acl_who returns TM_ERANGE past it
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)

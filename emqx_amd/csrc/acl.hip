@@ -141,7 +141,11 @@ __device__ bool filter_match(const AclView& v, const AclFilter& f, const uint8_t
 __device__ bool who_match(const AclView& v, uint32_t hb, uint32_t he, const uint8_t* cid, uint32_t cid_len,
                           bool cid_def, const uint8_t* usr, uint32_t usr_len, bool usr_def, uint32_t fam,
                           const uint8_t* ip) {
-    uint32_t st = 0, depth = 0;   // bool stack as bits
+    // bool stack as bits: the builder refuses a rule whose live entries would pass
+    // TM_ACL_WHO_STACK_MAX (tm_acl_who), so no result is ever shifted out
+    static_assert(TM_ACL_WHO_STACK_MAX == 64, "who_match's stack is one 64-bit word");
+    uint64_t st = 0;
+    uint32_t depth = 0;
     for (uint32_t k = hb; k < he; ++k) {
         const AclWho& h = v.who[k];
         bool r;
@@ -160,19 +164,19 @@ __device__ bool who_match(const AclView& v, uint32_t hb, uint32_t he, const uint
             }
             case H_AND:
             case H_OR: {
-                const uint32_t mask = h.n >= 32 ? ~0u : ((1u << h.n) - 1u);
-                const uint32_t kids = st & mask;
-                st = h.n >= 32 ? 0 : st >> h.n;
+                const uint64_t mask = h.n >= 64 ? ~0ull : ((1ull << h.n) - 1ull);   // a flat group of 64 fills the word
+                const uint64_t kids = st & mask;
+                st = h.n >= 64 ? 0 : st >> h.n;
                 depth -= h.n;
                 r = h.kind == H_AND ? kids == mask : kids != 0;
                 break;
             }
             default: r = false;
         }
-        st = (st << 1) | (r ? 1u : 0u);
+        st = (st << 1) | (r ? 1ull : 0ull);
         ++depth;
     }
-    return depth > 0 && (st & 1u);
+    return depth > 0 && (st & 1ull);
 }
 
 __global__ void __launch_bounds__(256)
@@ -243,6 +247,7 @@ struct tm_acl {
     bool open_rule = false, dirty = true;
     std::vector<uint32_t> groups;   // open AND/OR groups: index of the group's first child count slot
     std::vector<uint32_t> group_kind, group_count;
+    uint32_t live = 0;              // entries who_match's stack holds after the open rule's nodes so far
     DVec<AclRule> d_rules;
     DVec<AclFilter> d_filters;
     DVec<AclWord> d_words;
@@ -256,6 +261,17 @@ struct tm_acl {
     }
     void bump_group() {
         if (!group_count.empty()) group_count.back()++;
+    }
+    // drop the rule under construction (a who the kernel's stack cannot hold)
+    void abandon_rule() {
+        const AclRule& r = rules.back();
+        who.resize(r.hbeg);
+        while (!filters.empty() && filters.size() > r.fbeg) filters.pop_back();
+        rules.pop_back();
+        group_kind.clear();
+        group_count.clear();
+        live = 0;
+        open_rule = false;
     }
 };
 
@@ -282,6 +298,7 @@ int tm_acl_rule_begin(tm_acl* a, int allow, uint32_t access) {
     r.hbeg = r.hend = (uint32_t)a->who.size();
     r.fbeg = r.fend = (uint32_t)a->filters.size();
     a->rules.push_back(r);
+    a->live = 0;
     a->open_rule = true;
     a->dirty = true;
     return TM_OK;
@@ -303,16 +320,28 @@ int tm_acl_who(tm_acl* a, uint32_t kind, const uint8_t* arg, uint32_t len, uint3
             h.n = len;
             h.off = a->put_bytes(arg, len);
             break;
-        case TM_ACL_WHO_IPADDR: {   // arg: "a.b.c.d" or IPv6 text; prefix: mask bits (0 = full)
+        case TM_ACL_WHO_IPADDR: {   // arg: "a.b.c.d[/n]" or IPv6 text; prefix: mask bits of a bare address (0 = host)
             std::string s(reinterpret_cast<const char*>(arg), len);
+            bool cidr = false;           // "/n" given: n is the prefix, 0 included
+            uint32_t bits = 0;
+            const size_t slash = s.find('/');
+            if (slash != std::string::npos) {
+                if (slash + 1 >= s.size() || s.size() - slash - 1 > 3) return TM_EINVAL;
+                for (size_t i = slash + 1; i < s.size(); ++i) {
+                    if (s[i] < '0' || s[i] > '9') return TM_EINVAL;
+                    bits = bits * 10 + (uint32_t)(s[i] - '0');
+                }
+                cidr = true;
+                s.resize(slash);
+            }
             uint8_t buf[16] = {0};
             if (inet_pton(AF_INET, s.c_str(), buf) == 1) {
                 h.family = 4;
-                h.n = prefix ? prefix : 32;
+                h.n = cidr ? bits : prefix ? prefix : 32;
                 if (h.n > 32) return TM_EINVAL;
             } else if (inet_pton(AF_INET6, s.c_str(), buf) == 1) {
                 h.family = 6;
-                h.n = prefix ? prefix : 128;
+                h.n = cidr ? bits : prefix ? prefix : 128;
                 if (h.n > 128) return TM_EINVAL;
             } else {
                 return TM_EINVAL;
@@ -331,8 +360,12 @@ int tm_acl_who(tm_acl* a, uint32_t kind, const uint8_t* arg, uint32_t len, uint3
         case TM_ACL_WHO_END: {
             if (a->group_kind.empty()) return TM_EINVAL;
             h.kind = a->group_kind.back() == TM_ACL_WHO_AND ? H_AND : H_OR;
-            h.n = a->group_count.back();
-            if (h.n > 31) return TM_EINVAL;
+            h.n = a->group_count.back();            // <= live <= TM_ACL_WHO_STACK_MAX
+            if (h.n == 0 && a->live >= TM_ACL_WHO_STACK_MAX) {   // an empty group pushes its own result
+                a->abandon_rule();
+                return TM_ERANGE;
+            }
+            a->live = a->live - h.n + 1;
             a->group_kind.pop_back();
             a->group_count.pop_back();
             a->who.push_back(h);
@@ -342,6 +375,11 @@ int tm_acl_who(tm_acl* a, uint32_t kind, const uint8_t* arg, uint32_t len, uint3
         default:
             return TM_EINVAL;
     }
+    if (a->live >= TM_ACL_WHO_STACK_MAX) {   // one more live entry than who_match's stack holds
+        a->abandon_rule();
+        return TM_ERANGE;
+    }
+    a->live++;
     a->bump_group();
     a->who.push_back(h);
     a->rules.back().hend = (uint32_t)a->who.size();
@@ -402,8 +440,12 @@ int tm_acl_check_batch(tm_acl* a, uint32_t n, const uint8_t* access, const uint8
                        const uint8_t* usernames, const uint64_t* user_off, const uint8_t* user_defined,
                        const uint8_t* peers, const uint8_t* peer_family, int8_t* out_result, uint32_t* out_rule) {
     if (!a || a->open_rule || (n && (!access || !topics || !topic_off || !client_ids || !client_off ||
-                                     !client_defined || !usernames || !user_off || !user_defined || !out_result)))
+                                     !client_defined || !usernames || !user_off || !user_defined || !out_result)) ||
+        (peer_family && !peers))   // a family says "read the address"
         return TM_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if (topic_off[i + 1] < topic_off[i] || client_off[i + 1] < client_off[i] || user_off[i + 1] < user_off[i])
+            return TM_EINVAL;
     std::lock_guard<std::mutex> lk(a->mu);
     if (a->device < 0) return TM_EDEVICE;   // the check runs on the GPU only
     if (n == 0) return TM_OK;
@@ -458,7 +500,8 @@ int tm_acl_check_batch_device(tm_acl* a, uint32_t n, const uint8_t* d_access, co
                               const uint8_t* d_user_defined, const uint8_t* d_peers, const uint8_t* d_peer_family,
                               int8_t* d_out_result, uint32_t* d_out_rule, void* hip_stream) {
     if (!a || a->open_rule || (n && (!d_access || !d_topic_off || !d_client_off || !d_client_defined ||
-                                     !d_user_off || !d_user_defined || !d_out_result)))
+                                     !d_user_off || !d_user_defined || !d_out_result)) ||
+        (d_peer_family && !d_peers))
         return TM_EINVAL;
     std::lock_guard<std::mutex> lk(a->mu);
     if (a->device < 0) return TM_EDEVICE;

@@ -59,11 +59,8 @@ class AclRules:
             a = _b(arg)
             return self._ck(self.lib.tm_acl_who(self.h, WHO[kind], a, len(a), 0), "who")
         if kind == "ipaddr":
-            addr, _, bits = str(arg).partition("/")
-            net = ipaddress.ip_network(str(arg), strict=False)
-            a = addr.encode()
-            return self._ck(self.lib.tm_acl_who(self.h, WHO["ipaddr"], a, len(a),
-                                                int(bits) if bits else net.max_prefixlen), "who")
+            a = _b(arg)                  # "addr" or "addr/n": the library parses n (0 = the whole family)
+            return self._ck(self.lib.tm_acl_who(self.h, WHO["ipaddr"], a, len(a), 0), "who")
         if kind in ("and", "or"):
             self._ck(self.lib.tm_acl_who(self.h, WHO[kind], None, 0, 0), "who")
             for c in arg:
@@ -126,23 +123,25 @@ class AclRules:
     ARGS = ("access", "topics", "topic_off", "client_ids", "client_off", "client_defined", "usernames", "user_off",
             "user_defined", "peers", "peer_family")
 
-    def check_packed(self, n, arrs):
-        """host arrays from pack() -> (result int8[n], rule u32[n])"""
+    def check_packed(self, n, arrs, want_rule=True):
+        """host arrays from pack() -> (result int8[n], rule u32[n]); a missing
+        or None "peers" / "peer_family" goes as NULL, and so does the rule
+        output with want_rule=False (then rule is None)"""
         out = np.zeros(max(n, 1), dtype=np.int8)
-        rule = np.zeros(max(n, 1), dtype=np.uint32)
-        P = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
-        self._ck(self.lib.tm_acl_check_batch(self.h, n, *[P(arrs[k]) for k in self.ARGS], P(out), P(rule)),
+        rule = np.zeros(max(n, 1), dtype=np.uint32) if want_rule else None
+        P = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        self._ck(self.lib.tm_acl_check_batch(self.h, n, *[P(arrs.get(k)) for k in self.ARGS], P(out), P(rule)),
                  "tm_acl_check_batch")
-        return out[:n], rule[:n]
+        return out[:n], rule[:n] if want_rule else None
 
     def check_device(self, n, d, d_out, d_rule, stream=None):
         """device tensors (the pack() names) -> d_out / d_rule, stream-ordered
-        (tm_acl_check_batch_device)"""
-        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        (tm_acl_check_batch_device); None for "peers" / "peer_family" / d_rule goes as NULL"""
+        P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
         st = None
         if stream is not None:
             st = ctypes.c_void_p(L.stream_handle(stream))
-        self._ck(self.lib.tm_acl_check_batch_device(self.h, n, *[P(d[k]) for k in self.ARGS], P(d_out), P(d_rule),
+        self._ck(self.lib.tm_acl_check_batch_device(self.h, n, *[P(d.get(k)) for k in self.ARGS], P(d_out), P(d_rule),
                                                     st), "tm_acl_check_batch_device")
 
     def check_many(self, creds, pubsubs, topics):

@@ -1476,17 +1476,34 @@ void tm_batcher_close(tm_batcher* b);
  * (src/emqx_access_rule.erl:38-75):
  *   tm_acl_rule_begin(allow, access)   {allow|deny, Who, Access, Topics} / {allow|deny, all}
  *   tm_acl_who(kind, arg, len, prefix) Who: all | {client, C} | {user, U} | {client, all} |
- *                                      {user, all} | {ipaddr, "a.b.c.d[/n]"} (prefix = n, 0 = host);
- *                                      {'and' | 'or', [...]}: AND/OR, the conditions, END
+ *                                      {user, all} | {ipaddr, CIDR}; {'and' | 'or', [...]}: AND/OR,
+ *                                      the conditions, END
  *   tm_acl_topic(eq, topic, len)       a topic filter, or {eq, Topic}; "%c"/"%u" levels make a
  *                                      pattern (feed_var/3, :136-149)
  *   tm_acl_rule_end()
+ * {ipaddr, CIDR}: arg is the address text, IPv4 or IPv6.  With "/n" in arg
+ * ("10.0.0.0/8", "0.0.0.0/0", "::/0") n is the prefix, 0..32 / 0..128, 0 being
+ * the whole family as esockd_cidr:parse/2 has it, and `prefix` is ignored; for
+ * a bare address `prefix` gives the bits, 0 = the host (/32, /128).  Host bits
+ * of the network text are masked away.  TM_EINVAL for text that does not parse
+ * and for a prefix past the family's width.
+ * A Who is evaluated on a stack of TM_ACL_WHO_STACK_MAX results: a condition
+ * pushes one, END replaces its group's results by one.  The tm_acl_who call
+ * (a condition, or the END of an empty group) that would hold more than
+ * TM_ACL_WHO_STACK_MAX results at once returns TM_ERANGE and drops the rule
+ * under construction: the next call is tm_acl_rule_begin.  {and, [64
+ * conditions]} fits; {and, [C x 33, {or, [C x 32]}]} (65 at its peak) does not.
  * tm_acl_check_batch evaluates n checks on the GPU: out_result[i] = 1 allow,
  * 0 deny, -1 nomatch (the module's ignore); out_rule[i] = index of the
  * matching rule (or 0xFFFFFFFF).  Credentials: client id / username bytes
  * with a defined flag (undefined = the atom), peer address 16 B per check
- * with family 4 / 6 (0 = no peername); peers may be NULL.  Topics are
- * matched as word lists (emqx_access_rule:match_topic/2: no '$' rule). */
+ * with family 4 / 6 (0 = no peername).  peers and peer_family may both be
+ * NULL, and peers without peer_family reads the same way (no check has a
+ * peername); peer_family without peers is TM_EINVAL.  topic_off, client_off and user_off hold n + 1
+ * non-decreasing byte offsets (TM_EINVAL otherwise); they need not start at 0.
+ * Topics are matched as word lists (emqx_access_rule:match_topic/2: no '$'
+ * rule). */
+#define TM_ACL_WHO_STACK_MAX 64u   /* results a Who may hold at once (tm_acl_who: TM_ERANGE) */
 #define TM_ACL_ALL        0u   /* {allow|deny, all}: matches any check */
 #define TM_ACL_PUBLISH    1u
 #define TM_ACL_SUBSCRIBE  2u
@@ -1516,7 +1533,10 @@ int  tm_acl_check_batch(tm_acl* a, uint32_t n, const uint8_t* access, const uint
 
 /* Same with every buffer device-resident (HBM; byte offsets index topics /
  * client_ids / usernames directly), stream-ordered on hip_stream, no
- * synchronisation: the form a pipelined caller and the ACL bench use. */
+ * synchronisation: the form a pipelined caller and the ACL bench use.
+ * d_peer_family without d_peers is TM_EINVAL here too.  The offsets live in
+ * device memory and are not checked: the caller guarantees n + 1
+ * non-decreasing entries that stay inside their buffers. */
 int tm_acl_check_batch_device(tm_acl* a, uint32_t n, const uint8_t* d_access, const uint8_t* d_topics,
                               const uint64_t* d_topic_off, const uint8_t* d_client_ids, const uint64_t* d_client_off,
                               const uint8_t* d_client_defined, const uint8_t* d_usernames, const uint64_t* d_user_off,
