@@ -11,7 +11,10 @@ publisher process with its own cursors (sticky=True: `sticky` picks, a lane
 likewise a publisher with its own entries), and stream=True runs the keyed picks
 through tm_publish_stream_device too (an A/B switch); opts=True
 (submit_publish_opts) brings the delivery word of every pair and of every
-$share pick with the records.  This is the NIF's path: the callback there builds
+$share pick with the records; inbox=callable (with publish=True, opts=True)
+opens the inbox mode (tm_batcher_open_inbox): per batch the callable gets the
+batch's local sends grouped per receiving session before the per-publish
+callbacks run, which then carry no pairs.  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
 import itertools
@@ -24,19 +27,24 @@ from . import _lib as L
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
                  lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0, round_robin=False,
-                 stream=False, sticky=False, opts=False, upgrade_qos=False):
+                 stream=False, sticky=False, opts=False, upgrade_qos=False, inbox=None):
         self.engine = engine
         self.lib = engine.lib
         flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
             (L.TM_BATCHER_PUBLISH if publish else 0) | (L.TM_BATCHER_EAGER if eager else 0) | \
             (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0) | \
             (L.TM_BATCHER_STICKY if sticky else 0) | (L.TM_BATCHER_OPTS if opts else 0) | \
-            (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0)
+            (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0) | (L.TM_BATCHER_INBOX if inbox is not None else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
-        rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))
+        self.inbox = inbox
+        if inbox is not None:
+            self._idone = L.INBOX_DONE_FN(self._on_inbox_done)   # kept alive with the batcher
+            rc = self.lib.tm_batcher_open_inbox(engine.h, ctypes.byref(cfg), self._idone, None, ctypes.byref(h))
+        else:
+            rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))
         if rc != L.TM_OK:
-            raise L.TopicMatchError(rc, "tm_batcher_open")
+            raise L.TopicMatchError(rc, "tm_batcher_open_inbox" if inbox is not None else "tm_batcher_open")
         self.h = h
         self.routes = routes
         self._cbs = {}
@@ -93,10 +101,32 @@ class Batcher:
             raise L.TopicMatchError(rc, "tm_batcher_submit_publish")
         return t.value
 
+    def _on_inbox_done(self, _ctx, status, n_pub, tickets, hdr, inbox, n_inbox, ent_pub, ent_to, ent_word, n_ent):
+        """inbox(status, tickets, hdr, inbox, ent_pub, ent_to, ent_word) on the
+        lane's thread: numpy views of the lane's buffers, valid during the
+        call only (tickets u64[n_pub]; hdr u64[4]; inbox u32[S, 4] = rows {sub,
+        first, count, picks}; the entry planes u32[E]); on a failed batch
+        tickets is empty and everything else but status is None"""
+        def view(ptr, n, dtype):
+            if not n:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(ptr, shape=(n,)).view(dtype)
+        tk = view(tickets, n_pub, np.uint64)
+        if status != L.TM_OK:
+            self.inbox(status, tk, None, None, None, None, None)
+            return
+        self.inbox(status, tk, view(hdr, 4, np.uint64), view(inbox, n_inbox * 4, np.uint32).reshape(-1, 4),
+                   view(ent_pub, n_ent, np.uint32), view(ent_to, n_ent, np.uint32), view(ent_word, n_ent, np.uint32))
+
     def _on_publish_opts_done(self, ctx, ticket, status, deliv, pick_word, n_deliv, pairs, pair_word, n_pairs):
         cb = self._cbs.pop(ctx)
         if status != L.TM_OK:
             cb(status, None, None, None, None)
+            return
+        if self.inbox is not None:   # the plan carries the pairs: only their count comes here
+            raw = ctypes.string_at(ctypes.addressof(deliv.contents), n_deliv * 16) if n_deliv else b""
+            cb(status, list(map(tuple, np.frombuffer(raw, dtype=np.uint32).reshape(n_deliv, 4).tolist())),
+               [pick_word[i] for i in range(n_deliv)], None, n_pairs)
             return
         # records and words are valid only during the callback: copied out here
         def rows(ptr, n, width):
@@ -112,7 +142,8 @@ class Batcher:
         pair_words) runs on the worker thread; pick_words[i] is the delivery
         word of deliveries[i]'s pick (NO_WORD without one, and for a stuck
         member outside its set), pair_words[i] that of pairs[i]; all None on
-        error.  pub_flags / pub_from: the publish's words (tm_deliver)"""
+        error.  An inbox batcher calls callback(status, deliveries, pick_words,
+        None, n_pairs): the pairs are in the batch's plan.  pub_flags / pub_from: the publish's words (tm_deliver)"""
         t = ctypes.c_uint64()
         k = next(self._keys)
         self._cbs[k] = callback

@@ -42,6 +42,16 @@
 // tm_publish_stream_opts_device whatever the strategy, and the block that comes
 // back ends with the pick words and the pair words, which the callbacks read in
 // place beside the records.
+//
+// TM_BATCHER_INBOX (tm_batcher_open_inbox) regroups the batch's local sends per
+// receiving session on the device: behind tm_publish_stream_opts_device the
+// lane enqueues tm_inbox_plan_stream_device on the same stream, with no wait
+// between them, and the block that comes back carries the plan (header, one
+// record per subscriber, the entry planes) in place of the pairs and the pair
+// words, which stay on the device.  One callback per batch hands the plan over
+// before the per-publish callbacks run.  A plan that found an id wider than the
+// lane's sort width runs again ALONE over the outputs still on the device: the
+// publish call has stored its cursors, a second run would advance them twice.
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
@@ -208,6 +218,17 @@ struct Lane {
     double rr_per_topic = 16.0;
     tm_share_cursors* cursors = nullptr;
     uint64_t reruns = 0;
+    // TM_BATCHER_INBOX: the plan's workspace, the lane's bound on the width of a
+    // subscriber id (grows to what a plan reports), the batch's tickets in
+    // submission order and the plan as the batch callback reads it
+    Dev d_iws;
+    uint32_t sub_bits = 16;
+    std::vector<uint64_t> tickets;
+    const uint64_t* r_ihdr = nullptr;
+    const tm_inbox* r_inbox = nullptr;
+    const uint32_t* r_epub = nullptr;
+    const uint32_t* r_eto = nullptr;
+    const uint32_t* r_ewd = nullptr;
     clk::time_point sealed;           // when the batch was handed over
     uint64_t launch_ns = 0, sync_ns = 0;   // this batch: host time enqueueing the device work, waiting on it
 };
@@ -230,6 +251,9 @@ struct tm_batcher {
     bool sticky = false;    // TM_BATCHER_STICKY: sticky picks, a context per lane as with round robin
     bool opts = false;      // TM_BATCHER_OPTS: tm_publish_stream_opts_device, records and pairs with their words
     bool upgrade = false;   // TM_BATCHER_UPGRADE_QOS
+    bool inbox = false;     // TM_BATCHER_INBOX: the plan per batch through ifn, no pairs in the per-publish callbacks
+    tm_inbox_done_fn ifn = nullptr;
+    void* ictx = nullptr;
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -663,6 +687,37 @@ struct tm_batcher {
         return tm_publish_caps{cap_of(L.ids_per_topic, n), cap_of(L.deliv_per_topic, n), cap_of(L.pairs_per_topic, n),
                                (round_robin || sticky) ? cap_of(L.rr_per_topic, n) : 0};
     }
+    // The packed block of a stream batch.  Without TM_BATCHER_INBOX:
+    //   [hdr][doff][sub_off][deliveries cap x 16 B][pairs scap x 8 B][pick words cap x 4 B][pair words scap x 4 B]
+    // and all of it comes back (backb = outb).  With it the pairs and the pair
+    // words move behind what comes back, and the plan takes their place:
+    //   [hdr][doff][sub_off][deliveries][pick words][plan hdr 8 u64][records ecap x 16 B][ent_pub][ent_to]
+    //   [ent_word] | [pairs][pair words],   ecap = cap + scap (every send fits: no plan state 3 or 4)
+    struct BlockLayout {
+        uint64_t o_pairs, o_pickw, o_pairw, o_ihdr, o_inbox, o_epub, o_eto, o_ewd, backb, outb, ecap;
+    };
+    BlockLayout block_layout(uint32_t n, uint64_t cap, uint64_t scap) const {
+        BlockLayout B{};
+        const uint64_t head = ps_head(n), wb = opts ? 4 : 0;
+        if (!inbox) {
+            B.o_pairs = head + cap * 16;
+            B.o_pickw = B.o_pairs + scap * 8;
+            B.o_pairw = B.o_pickw + cap * wb;
+            B.outb = B.backb = B.o_pairw + scap * wb;
+            return B;
+        }
+        B.ecap = cap + scap;
+        B.o_pickw = head + cap * 16;
+        B.o_ihdr = (B.o_pickw + cap * 4 + 15) & ~15ull;
+        B.o_inbox = B.o_ihdr + 8 * TM_INBOX_STREAM_HDR_WORDS;
+        B.o_epub = B.o_inbox + B.ecap * 16;
+        B.o_eto = B.o_epub + B.ecap * 4;
+        B.o_ewd = B.o_eto + B.ecap * 4;
+        B.o_pairs = B.backb = (B.o_ewd + B.ecap * 4 + 15) & ~15ull;
+        B.o_pairw = B.o_pairs + scap * 8;
+        B.outb = B.o_pairw + scap * 4;
+        return B;
+    }
     int run_publish_stream(Lane& L, uint64_t& results) {
         auto chk = [](hipError_t e) { return e == hipSuccess; };
         const uint32_t n = L.n;
@@ -677,9 +732,7 @@ struct tm_batcher {
         const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
         const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + upb;
         // TM_BATCHER_OPTS: the publishes' words went up with the keys, and the block
-        // that comes back grows by the two word planes:
-        // [hdr][doff][sub_off][deliveries cap x 16 B][pairs scap x 8 B][pick words cap x 4 B][pair words scap x 4 B]
-        const uint64_t wb = opts ? 4 : 0;   // word bytes per record and per pair
+        // that comes back grows by the two word planes (block_layout)
         tm_deliver dv{};
         dv.pub_flags = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + keyb);
         dv.pub_from = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + 2 * keyb);
@@ -693,25 +746,44 @@ struct tm_batcher {
                 ++L.reruns;
             }
             const uint64_t cap = caps.routes, scap = caps.pairs;
-            const uint64_t o_pickw = head + cap * 16 + scap * 8, o_pairw = o_pickw + cap * wb;
-            const uint64_t outb = o_pairw + scap * wb;
+            const BlockLayout B = block_layout(n, cap, scap);
+            const uint64_t o_pairs = B.o_pairs, o_pickw = B.o_pickw, o_pairw = B.o_pairw, outb = B.outb;
+            const uint64_t backb = B.backb, ecap = B.ecap;
+            const uint64_t iwsb = inbox ? tm_inbox_plan_stream_workspace_bytes(n, cap, scap, ecap) : 0;
+            if (inbox && (!iwsb || !L.d_iws.ensure(iwsb) || !L.h_out.ensure(backb))) return iwsb ? TM_ENOMEM : TM_ERANGE;
             const uint64_t wsb = opts ? tm_publish_stream_opts_workspace_bytes(eng, n, nbytes, &caps)
                                       : tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
             if (!wsb) return TM_ERANGE;
-            if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? outb : head)) return TM_ENOMEM;
+            if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? backb : head)) return TM_ENOMEM;
             uint8_t* d = (uint8_t*)L.d_out.p;
             dv.sub_deliver = (uint32_t*)(d + o_pairw);
+            // the plan over the outputs on the device, behind the publish call on the lane's stream
+            auto plan = [&]() {
+                return tm_inbox_plan_stream_device(
+                    eng, n, (const uint64_t*)d, (const uint64_t*)(d + 64), (const uint64_t*)(d + 64 + offb),
+                    (const tm_delivery*)(d + head), (const uint32_t*)(d + o_pickw), cap, (const tm_pair*)(d + o_pairs),
+                    (const uint32_t*)(d + o_pairw), scap, L.sub_bits, L.d_iws.p, iwsb, (uint64_t*)(d + B.o_ihdr),
+                    (tm_inbox*)(d + B.o_inbox), ecap, (uint32_t*)(d + B.o_epub), (uint32_t*)(d + B.o_eto),
+                    (uint32_t*)(d + B.o_ewd), ecap, s);
+            };
             const int rc =
                 opts ? tm_publish_stream_opts_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
                                                      L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
                                                      (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                     (tm_pair*)(d + head + cap * 16), &dv, (uint32_t*)(d + o_pickw), s)
+                                                     (tm_pair*)(d + o_pairs), &dv, (uint32_t*)(d + o_pickw), s)
                      : tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
                                                 L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
                                                 (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                (tm_pair*)(d + head + cap * 16), s);
+                                                (tm_pair*)(d + o_pairs), s);
             if (rc != TM_OK) return rc;
-            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? outb : head, hipMemcpyDeviceToHost, s)))
+            if (inbox) {
+                const int prc = plan();
+                if (prc != TM_OK) return prc;
+            }
+            // a small batch: everything up to backb (without TM_BATCHER_INBOX the whole block) in one copy
+            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? backb : head, hipMemcpyDeviceToHost, s)) ||
+                (inbox && !eager &&
+                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, 64, hipMemcpyDeviceToHost, s))))
                 return TM_EDEVICE;
             L.launch_ns += ns_since(t0);
             t0 = clk::now();
@@ -727,27 +799,58 @@ struct tm_batcher {
             if (state == 0 || state >= 3) mean(L.pairs_per_topic, hdr[1]);
             if ((round_robin || sticky) && (state == 0 || state == 4)) mean(L.rr_per_topic, hdr[5]);
             if (state == 0) {
-                if (!eager) {   // exactly D deliveries and P pairs
-                    if (!L.h_out.ensure(outb)) return TM_ENOMEM;   // may move: the head is read again below
+                // TM_BATCHER_INBOX: a plan that met an id wider than the lane's sort width (plan state 2)
+                // runs again alone, at the width its header reports; the publish call is NOT repeated.
+                // ent_cap = inbox_cap = cap + scap: the plan states 3 and 4 cannot occur
+                for (int ipass = 0; inbox; ++ipass) {
+                    const uint64_t* ih = (const uint64_t*)(h + B.o_ihdr);
+                    if (ih[6] == 0) break;
+                    if (ih[6] != 2 || ipass) return TM_EDEVICE;
+                    uint32_t bits = 0;
+                    while (bits < 32 && (ih[4] >> bits)) ++bits;
+                    L.sub_bits = bits;
+                    ++L.reruns;
                     t0 = clk::now();
-                    if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, head + D * 16, hipMemcpyDeviceToHost, s)) ||
-                        (P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + head + cap * 16, d + head + cap * 16, P * 8,
-                                                  hipMemcpyDeviceToHost, s))) ||
-                        (opts && D && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o_pickw, d + o_pickw, D * 4,
-                                                          hipMemcpyDeviceToHost, s))) ||
-                        (opts && P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o_pairw, d + o_pairw, P * 4,
-                                                          hipMemcpyDeviceToHost, s))) ||
+                    const int prc = plan();
+                    if (prc != TM_OK) return prc;
+                    if (!chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, eager ? backb - B.o_ihdr : 64,
+                                            hipMemcpyDeviceToHost, s)))
+                        return TM_EDEVICE;
+                    L.launch_ns += ns_since(t0);
+                    t0 = clk::now();
+                    if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
+                    L.sync_ns += ns_since(t0);
+                }
+                if (!eager) {   // exactly D deliveries and P pairs (TM_BATCHER_INBOX: S records and E entries, no pairs)
+                    if (!L.h_out.ensure(backb)) return TM_ENOMEM;   // may move: the head is read again below
+                    const uint64_t* ih = inbox ? (const uint64_t*)((const uint8_t*)L.h_out.p + B.o_ihdr) : nullptr;
+                    const uint64_t E = inbox ? ih[0] : 0, S = inbox ? ih[1] : 0;
+                    auto down = [&](uint64_t o, uint64_t bytes) {
+                        return !bytes || chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o, d + o, bytes, hipMemcpyDeviceToHost, s));
+                    };
+                    t0 = clk::now();
+                    if (!down(0, head + D * 16) || (!inbox && !down(o_pairs, P * 8)) || (opts && !down(o_pickw, D * 4)) ||
+                        (opts && !inbox && !down(o_pairw, P * 4)) ||
+                        (inbox && (!down(B.o_ihdr, 64 + S * 16) || !down(B.o_epub, E * 4) || !down(B.o_eto, E * 4) ||
+                                   !down(B.o_ewd, E * 4))) ||
                         !chk(hipStreamSynchronize(s)))
                         return TM_EDEVICE;
                     L.sync_ns += ns_since(t0);
                     h = (const uint8_t*)L.h_out.p;
                 }
                 L.r_pickw = (const uint32_t*)(h + o_pickw);
-                L.r_pairw = (const uint32_t*)(h + o_pairw);
+                L.r_pairw = inbox ? nullptr : (const uint32_t*)(h + o_pairw);
                 L.r_doff = (const uint64_t*)(h + 64);
                 L.r_soff = (const uint64_t*)(h + 64 + offb);
                 L.r_deliv = (const tm_delivery*)(h + head);
-                L.r_pairs = (const tm_pair*)(h + head + cap * 16);
+                L.r_pairs = inbox ? nullptr : (const tm_pair*)(h + o_pairs);
+                if (inbox) {
+                    L.r_ihdr = (const uint64_t*)(h + B.o_ihdr);
+                    L.r_inbox = (const tm_inbox*)(h + B.o_inbox);
+                    L.r_epub = (const uint32_t*)(h + B.o_epub);
+                    L.r_eto = (const uint32_t*)(h + B.o_eto);
+                    L.r_ewd = (const uint32_t*)(h + B.o_ewd);
+                }
                 results = D;
                 return TM_OK;
             }
@@ -786,8 +889,8 @@ struct tm_batcher {
                 if (opts) {
                     if (rc == TM_OK)
                         r.ofn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], L.r_pickw + L.r_doff[k],
-                              (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]), L.r_pairs + L.r_soff[k],
-                              L.r_pairw + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]));
+                              (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]), inbox ? nullptr : L.r_pairs + L.r_soff[k],
+                              inbox ? nullptr : L.r_pairw + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]));
                     else
                         r.ofn(r.ctx, r.ticket, rc, nullptr, nullptr, 0, nullptr, nullptr, 0);
                 } else if (publish) {
@@ -883,6 +986,17 @@ struct tm_batcher {
                     for (uint32_t i = 0; i < n; ++i) results += L.r_counts[i];
             }
             const uint32_t m = n;
+            if (inbox) {   // the batch's plan first, once, on this thread; then the per-publish callbacks
+                L.tickets.clear();
+                if (rc == TM_OK)
+                    for (const Chunk& c : L.chunks)
+                        for (size_t j = c.head; j < c.reqs.size(); ++j) L.tickets.push_back(c.reqs[j].ticket);
+                if (rc == TM_OK)
+                    ifn(ictx, TM_OK, m, L.tickets.data(), L.r_ihdr, L.r_inbox, (uint32_t)L.r_ihdr[1], L.r_epub, L.r_eto,
+                        L.r_ewd, (uint32_t)L.r_ihdr[0]);
+                else
+                    ifn(ictx, rc, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+            }
             run_callbacks(L, rc, routes, m);
             const clk::time_point t_cb = clk::now();
             if (leased) tm_lease_end(eng, lease);
@@ -1048,12 +1162,17 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
 
 extern "C" {
 
-int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out) {
+// ifn: the batch callback of tm_batcher_open_inbox (the caller checked the flags), else null
+static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn ifn, void* ictx,
+                        tm_batcher** out) {
     if (!e || !out) return TM_EINVAL;
     tm_batcher* b = new (std::nothrow) tm_batcher();
     if (!b) return TM_ENOMEM;
     b->eng = e;
     if (cfg) b->cfg = *cfg;
+    b->inbox = ifn != nullptr;
+    b->ifn = ifn;
+    b->ictx = ictx;
     if (b->cfg.max_topics == 0) b->cfg.max_topics = 65536;
     if (b->cfg.max_bytes == 0) b->cfg.max_bytes = 64ull << 20;
     if (b->cfg.deadline_us == 0) b->cfg.deadline_us = 200;
@@ -1144,9 +1263,10 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
             if (b->stream) {   // the first batch's four capacities
                 const tm_publish_caps c = b->stream_caps(*L, pre);
                 const uint64_t io = offb + b->upb_of((uint32_t)pre) + nbytes + 16;
-                const uint64_t wb = b->opts ? 4 : 0;
-                const uint64_t outb = tm_batcher::ps_head((uint32_t)pre) + c.routes * (16 + wb) + c.pairs * (8 + wb);
-                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(outb) && L->h_out.ensure(outb) &&
+                const tm_batcher::BlockLayout B = b->block_layout((uint32_t)pre, c.routes, c.pairs);
+                if (b->inbox)
+                    (void)L->d_iws.ensure(tm_inbox_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.pairs, B.ecap));
+                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(B.outb) && L->h_out.ensure(B.backb) &&
                        L->d_ws.ensure(b->opts ? tm_publish_stream_opts_workspace_bytes(e, (uint32_t)pre, nbytes, &c)
                                               : tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
                 continue;
@@ -1186,6 +1306,18 @@ int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out
     }
     *out = b;
     return TM_OK;
+}
+
+int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out) {
+    if (cfg && (cfg->flags & TM_BATCHER_INBOX)) return TM_EINVAL;   // the mode needs its batch callback
+    return batcher_open(e, cfg, nullptr, nullptr, out);
+}
+
+int tm_batcher_open_inbox(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn fn, void* ctx,
+                          tm_batcher** out) {
+    const uint32_t need = TM_BATCHER_INBOX | TM_BATCHER_PUBLISH | TM_BATCHER_OPTS;
+    if (!cfg || !fn || (cfg->flags & need) != need) return TM_EINVAL;
+    return batcher_open(e, cfg, fn, ctx, out);
 }
 
 int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn fn, void* ctx,

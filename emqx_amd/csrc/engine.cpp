@@ -5863,6 +5863,120 @@ int tm_inbox_plan(tm_engine* e, uint32_t n, const uint64_t* sub_off, const uint3
     });
 }
 
+// ---- tm_inbox_plan_stream_device: the plan without a host wait ----
+// Every intermediate lives in the caller's workspace, cut up here (256 B
+// aligned pieces, each a monotone function of the capacities; n sizes nothing).
+namespace {
+struct InboxStreamLayout {
+    uint64_t ctl, flag, pf, scan, rec, kv, head, hk, counts, off, sscan, bytes;
+};
+bool inbox_stream_caps_ok(uint32_t n, uint64_t deliv_cap, uint64_t pair_cap, uint64_t ent_cap) {
+    const uint64_t lim = 0xFFFFFFFEull;   // positions and entries are u32 indices on the device
+    return n < 0x80000000u && deliv_cap < lim && pair_cap < lim && ent_cap < lim && deliv_cap + pair_cap < lim;
+}
+InboxStreamLayout inbox_stream_layout(uint64_t deliv_cap, uint64_t pair_cap, uint64_t ent_cap) {
+    InboxStreamLayout L{};
+    uint64_t at = 0;
+    auto take = [&](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    };
+    const uint64_t pos = deliv_cap + pair_cap;
+    const uint32_t pc = tmx::presort_counts((uint32_t)ent_cap);
+    L.ctl = take(64);
+    L.flag = take(pos * 4 + 4);
+    L.pf = take((pos + 1) * 8);
+    L.scan = take(tmx::scan_tmp_elems((uint32_t)std::max(pos, ent_cap)) * 8 + 8);
+    L.rec = take(ent_cap * 16);
+    L.kv = take(ent_cap * 16);
+    L.head = take(ent_cap * 8);
+    L.hk = take((ent_cap + 1) * 16);
+    L.counts = take((uint64_t)pc * 4);
+    L.off = take(((uint64_t)pc + 1) * 8);
+    L.sscan = take(tmx::scan_tmp_elems(pc) * 8 + 8);
+    L.bytes = at;
+    return L;
+}
+}  // namespace
+
+uint64_t tm_inbox_plan_stream_workspace_bytes(uint32_t n, uint64_t deliv_cap, uint64_t pair_cap, uint64_t ent_cap) {
+    if (!inbox_stream_caps_ok(n, deliv_cap, pair_cap, ent_cap)) return 0;
+    return inbox_stream_layout(deliv_cap, pair_cap, ent_cap).bytes;
+}
+
+int tm_inbox_plan_stream_device(tm_engine* e, uint32_t n, const uint64_t* d_pub_hdr, const uint64_t* d_doff,
+                                const uint64_t* d_sub_off, const tm_delivery* d_deliv, const uint32_t* d_pick_word,
+                                uint64_t deliv_cap, const tm_pair* d_pairs, const uint32_t* d_pair_word,
+                                uint64_t pair_cap, uint32_t sub_bits, void* d_workspace, uint64_t workspace_bytes,
+                                uint64_t* d_hdr, tm_inbox* d_inbox, uint64_t inbox_cap, uint32_t* d_ent_pub,
+                                uint32_t* d_ent_to, uint32_t* d_ent_word, uint64_t ent_cap, void* hip_stream) {
+    if (!d_pub_hdr || !d_doff || !d_sub_off || !d_hdr || !d_workspace) return TM_EINVAL;
+    if ((deliv_cap && !d_deliv) || (pair_cap && !d_pairs) || (inbox_cap && !d_inbox) ||
+        (ent_cap && (!d_ent_pub || !d_ent_to)) || sub_bits > 32)
+        return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (!inbox_stream_caps_ok(n, deliv_cap, pair_cap, ent_cap) || inbox_cap >= 0xFFFFFFFEull)
+        return guarded(e, [&]() -> int {
+            throw RangeError("inbox: a capacity of 2^32 - 2 or more (the pair and record capacities together too), "
+                             "or 2^31 topics or more, in one batch");
+        });
+    const InboxStreamLayout L = inbox_stream_layout(deliv_cap, pair_cap, ent_cap);
+    if (workspace_bytes < L.bytes) return TM_EINVAL;
+    if (e->devs.empty()) return no_device(e, "inbox plan");
+    DevState& d = *e->replica_for(d_pub_hdr);
+    // no replica workspace is touched, so no batch lock: the call only enqueues
+    std::string err;
+    const int rc = catching(err, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (n == 0) {
+            HIPCHK(hipMemsetAsync(d_hdr, 0, TM_INBOX_STREAM_HDR_WORDS * 8, st));
+            return TM_OK;
+        }
+        using namespace tmx;
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        auto u32 = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(ws + o); };
+        auto u64 = [&](uint64_t o) { return reinterpret_cast<uint64_t*>(ws + o); };
+        const uint32_t bits = sub_bits ? sub_bits : 32u, passes = (bits + 7) / 8;
+        const uint64_t pos = pair_cap + deliv_cap;
+        uint64_t* ctl = u64(L.ctl);
+        uint32_t* flag = u32(L.flag);
+        uint64_t* PF = u64(L.pf);
+        HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+        HIPCHK(launch_inbox_stream_flag(n, d_pub_hdr, d_doff, d_sub_off, d_deliv, d_pick_word, deliv_cap, d_pairs,
+                                        d_pair_word, pair_cap, flag, reinterpret_cast<uint32_t*>(ctl + 2), st));
+        HIPCHK(launch_scan0(flag, (uint32_t)pos, PF, PF + pos, u64(L.scan), st));
+        HIPCHK(launch_inbox_stream_check(d_pub_hdr, PF, pair_cap, deliv_cap, bits, ent_cap, ctl, d_hdr, st));
+        if (ent_cap == 0) return TM_OK;   // any send is state 3
+        void* rec = ws + L.rec;
+        uint32_t *k0 = u32(L.kv), *v0 = k0 + ent_cap, *k1 = v0 + ent_cap, *v1 = k1 + ent_cap;
+        HIPCHK(launch_inbox_stream_emit(n, d_pub_hdr, d_doff, d_sub_off, d_deliv, d_pick_word, deliv_cap, d_pairs,
+                                        d_pair_word, pair_cap, flag, PF, ctl, ent_cap, rec, k0, v0, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, (uint32_t)ent_cap, passes, u32(L.counts), u64(L.off), u64(L.sscan), st,
+                                 ctl + 1));
+        if (passes & 1u) {   // an odd number of passes left the pairs in (k1, v1)
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        uint32_t* head = u32(L.head);
+        uint32_t* pk = head + ent_cap;
+        uint64_t* H = u64(L.hk);
+        uint64_t* K = H + ent_cap + 1;
+        HIPCHK(launch_inbox_stream_gather(ctl, k0, v0, rec, d_ent_pub, d_ent_to, d_ent_word, ent_cap, head, pk, st));
+        HIPCHK(launch_scan0(head, (uint32_t)ent_cap, H, H + ent_cap, u64(L.scan), st));
+        HIPCHK(launch_scan0(pk, (uint32_t)ent_cap, K, K + ent_cap, u64(L.scan), st));
+        HIPCHK(launch_inbox_stream_records(ctl, k0, head, H, K, ent_cap, d_hdr, d_inbox, inbox_cap, st));
+        return TM_OK;
+    });
+    if (!err.empty())
+        return guarded(e, [&] {
+            e->last_error = err;
+            return rc;
+        });
+    return rc;
+}
+
 static_assert(TM_NO_WORD == 0xFFFFFFFFu && (TM_NO_WORD & 3u) == tmx::SUBOPT_NONE, "a delivery word's QoS is never 3");
 
 // the descriptor of the pick-word pass: tm_deliver's per-publish arrays and flag, no pair words

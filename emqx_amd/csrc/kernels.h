@@ -334,6 +334,40 @@ hipError_t launch_inbox_gather(const uint32_t* keys, const uint32_t* vals, const
                                uint32_t* head, uint32_t* pk, hipStream_t st);
 hipError_t launch_inbox_records(const uint32_t* keys, const uint32_t* head, const uint64_t* H, const uint64_t* K,
                                 uint32_t m, uint64_t* hdr, void* inbox, uint64_t inbox_cap, hipStream_t st);
+// The same plan from the packed outputs of the stream-ordered publish call
+// (pub_hdr, doff, sub_off, 16 B deliv records, 8 B pairs, the two word planes),
+// enqueued only: ctl is 8 zeroed u64 ({state, m, largest id}), every kernel
+// leaves when the state is set, bounds are device words, grids come from n and
+// the capacities.  pair_cap + deliv_cap below 2^32 - 2.
+//   launch_inbox_stream_flag     flag[pair_cap + deliv_cap]: position is a send (pairs,
+//                                then records: both kinds in one launch); *maxid
+//   launch_scan0                 PF (pair_cap + deliv_cap + 1)
+//   launch_inbox_stream_check    the state (1 publish state, 2 id wider than sub_bits,
+//                                3 E > ent_cap), ctl[1] = m, hdr[0], hdr[2..5], hdr[7]
+//   launch_inbox_stream_emit     staging records and (key, value) of both kinds, and the
+//                                padding keys 0xFFFFFFFF of [m, ent_cap)
+//   launch_sort_pairs            over ent_cap, live = &ctl[1]
+//   launch_inbox_stream_gather   entry planes, head / pk over ent_cap (0 from m on)
+//   launch_scan0 x 2             H, K (ent_cap + 1 u64 each)
+//   launch_inbox_stream_records  the records; hdr[1] = S, hdr[6] = 0 or 4 (S > inbox_cap)
+hipError_t launch_inbox_stream_flag(uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff, const uint64_t* sub_off,
+                                    const void* deliv, const uint32_t* pick_word, uint64_t deliv_cap,
+                                    const void* pairs, const uint32_t* pair_word, uint64_t pair_cap, uint32_t* flag,
+                                    uint32_t* maxid, hipStream_t st);
+hipError_t launch_inbox_stream_check(const uint64_t* pub_hdr, const uint64_t* PF, uint64_t pair_cap,
+                                     uint64_t deliv_cap, uint32_t sub_bits, uint64_t ent_cap, uint64_t* ctl,
+                                     uint64_t* hdr, hipStream_t st);
+hipError_t launch_inbox_stream_emit(uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff, const uint64_t* sub_off,
+                                    const void* deliv, const uint32_t* pick_word, uint64_t deliv_cap,
+                                    const void* pairs, const uint32_t* pair_word, uint64_t pair_cap,
+                                    const uint32_t* flag, const uint64_t* PF, const uint64_t* ctl, uint64_t ent_cap,
+                                    void* rec, uint32_t* keys, uint32_t* vals, hipStream_t st);
+hipError_t launch_inbox_stream_gather(const uint64_t* ctl, const uint32_t* keys, const uint32_t* vals, const void* rec,
+                                      uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word, uint64_t ent_cap,
+                                      uint32_t* head, uint32_t* pk, hipStream_t st);
+hipError_t launch_inbox_stream_records(const uint64_t* ctl, const uint32_t* keys, const uint32_t* head,
+                                       const uint64_t* H, const uint64_t* K, uint64_t ent_cap, uint64_t* hdr,
+                                       void* inbox, uint64_t inbox_cap, hipStream_t st);
 
 // A publish batch's results as dense records (pack.hip) over what
 // tm_match_publish_batch_device left: doff[n + 1] = scan of count (scan_tmp:

@@ -808,6 +808,33 @@ class Engine:
                                            p(d_ent_pub), p(d_ent_to), p(d_ent_word), ent_cap, st)
         return self._check(rc, "tm_inbox_plan_device")
 
+    INBOX_STREAM_HDR_WORDS = 8
+
+    def inbox_plan_stream_workspace_bytes(self, n, deliv_cap, pair_cap, ent_cap):
+        """tm_inbox_plan_stream_workspace_bytes (0: an argument out of range)"""
+        return int(self.lib.tm_inbox_plan_stream_workspace_bytes(n, deliv_cap, pair_cap, ent_cap))
+
+    def inbox_plan_stream_device(self, n, d_pub_hdr, d_doff, d_sub_off, d_deliv, d_pick_word, deliv_cap, d_pairs,
+                                 d_pair_word, pair_cap, sub_bits, d_workspace, workspace_bytes, d_hdr, d_inbox,
+                                 inbox_cap, d_ent_pub, d_ent_to, d_ent_word, ent_cap, stream=None):
+        """tm_inbox_plan_stream_device over device pointers (tensors or ints;
+        None = NULL): the plan of the packed outputs publish_stream[_opts]_device
+        left, enqueued on `stream` without a host wait.  d_hdr: 8 u64, [6] the
+        state (0 complete, 1 the publish did not fit, 2 an id wider than
+        sub_bits, 3 E > ent_cap, 4 S > inbox_cap)."""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_inbox_plan_stream_device(self.h, n, p(d_pub_hdr), p(d_doff), p(d_sub_off), p(d_deliv),
+                                                  p(d_pick_word), deliv_cap, p(d_pairs), p(d_pair_word), pair_cap,
+                                                  sub_bits, p(d_workspace), workspace_bytes, p(d_hdr), p(d_inbox),
+                                                  inbox_cap, p(d_ent_pub), p(d_ent_to), p(d_ent_word), ent_cap, st)
+        return self._check(rc, "tm_inbox_plan_stream_device")
+
     # -- emqx_shared_sub: the $share member table and the pick (share.hip) ---------
     NO_MEMBER = 0xFFFFFFFF            # pick: `false`, or not a $share delivery
     SHARE_KEYED, SHARE_ROUND_ROBIN, SHARE_STICKY = 1, 2, 3

@@ -1121,6 +1121,71 @@ int tm_inbox_plan(tm_engine* e, uint32_t n, const uint64_t* sub_off, const uint3
                   uint64_t out_cap, uint64_t total, uint64_t hdr[TM_INBOX_HDR_WORDS], tm_inbox* inbox,
                   uint64_t inbox_cap, uint32_t* ent_pub, uint32_t* ent_to, uint32_t* ent_word, uint64_t ent_cap);
 
+/* The plan, stream-ordered: the same sends, the same four sort keys, the same
+ * tm_inbox records and entry planes (and the same one deviation from the
+ * reference's order, above), computed from the PACKED outputs of
+ * tm_publish_stream[_opts]_device (below) instead of the planes.  Between entry
+ * and return the call only enqueues work on hip_stream: no synchronisation, no
+ * read-back, no allocation, no image read -- a tm_commit between the publish
+ * call and the plan changes nothing, and the call may be run again over the
+ * same outputs.  With it the whole of publish/1 up to the sends is ordered on
+ * one stream without a host wait.
+ *   d_pub_hdr   the publish call's d_hdr[TM_PUBLISH_HDR_WORDS]: P = [3], D = [2]
+ *               and the publish state [6] are read on the device
+ *   pair send   pair p < min(P, pair_cap) of topic t (d_sub_off[t] <= p <
+ *               d_sub_off[t+1]): (d_pairs[p].sub, t, d_pairs[p].to, d_pair_word[p])
+ *   pick send   record d < min(D, deliv_cap) of topic t (d_doff[t] <= d <
+ *               d_doff[t+1]) with d_deliv[d].pick != TM_NO_MEMBER:
+ *               (pick, t, d_deliv[d].to, d_pick_word[d])
+ * A word equal to TM_DELIVER_DROP is no send; TM_NO_WORD on a pick is a send
+ * and keeps its word; a NULL word plane makes every position of its kind a send
+ * with word 0.  Packed records have no holes, so no count[] is read.
+ * d_hdr[TM_INBOX_STREAM_HDR_WORDS]:
+ *   [0..3] {E, S, pair sends, pick sends} as tm_inbox_plan
+ *   [4]    the largest subscriber id among the sends (0 without sends)
+ *   [5], [7]  0
+ *   [6]    state, the first that applies:
+ *          0  complete: the records, the entry planes and [0..3] are bit for bit
+ *             what tm_inbox_plan_device writes for the equivalent planes
+ *          1  the publish call's own state was not 0: nothing is computed,
+ *             [0..5] are 0 and nothing else is written
+ *          2  the largest id needs more than sub_bits bits: [0], [2], [3], [4]
+ *             exact, [1] = 0, no record and no entry written
+ *          3  E > ent_cap: the header as in state 2, no record and no entry
+ *          4  S > inbox_cap: the header exact, the entry planes complete,
+ *             exactly the first inbox_cap records written
+ * In every state nothing is written at or past inbox_cap records, ent_cap
+ * entries or workspace_bytes.  E <= min(P, pair_cap) + min(D, deliv_cap), so
+ * ent_cap = pair_cap + deliv_cap cannot reach state 3 (and inbox_cap = ent_cap
+ * not state 4).
+ * sub_bits (1..32, 0 = 32) is the caller's upper bound on the width of a
+ * subscriber id and replaces the read-back of tm_inbox_plan_device: the sort
+ * runs ceil(sub_bits / 8) stable passes over ent_cap pairs, the m live ones
+ * padded with key 0xFFFFFFFF (all digits 255, staged last, stable sort: the
+ * padding stays behind a live id whose low bits are all ones).  Ids up to
+ * 0xFFFFFFFE stay legal; a sub_bits that is too small is detected (state 2,
+ * rerun with the width of [4]) and never mis-sorts.
+ * Every kernel tests a state word in the workspace first and leaves when it is
+ * set; it is set once the totals are known.  Launches for up to 32768
+ * positions and entries: 9 + 3 per sort pass (15 with sub_bits = 16).
+ * d_workspace: tm_inbox_plan_stream_workspace_bytes(n, deliv_cap, pair_cap,
+ * ent_cap) bytes (non-decreasing in each argument; 0 when out of range).
+ * n == 0: a zero header.  TM_EINVAL, before anything is enqueued: a null
+ * d_pub_hdr, d_doff, d_sub_off, d_hdr or d_workspace; a null record or result
+ * array with its capacity non-zero (d_ent_word and the two word planes
+ * excepted); sub_bits > 32; workspace_bytes below the need.  TM_ERANGE: a
+ * capacity, or pair_cap + deliv_cap, at or above 2^32 - 2, or n at or above
+ * 2^31.  TM_EDEVICE on a host-only engine.  Runs on the replica that owns
+ * d_pub_hdr. */
+#define TM_INBOX_STREAM_HDR_WORDS 8
+uint64_t tm_inbox_plan_stream_workspace_bytes(uint32_t n, uint64_t deliv_cap, uint64_t pair_cap, uint64_t ent_cap);
+int tm_inbox_plan_stream_device(tm_engine* e, uint32_t n, const uint64_t* d_pub_hdr, const uint64_t* d_doff,
+                                const uint64_t* d_sub_off, const tm_delivery* d_deliv, const uint32_t* d_pick_word,
+                                uint64_t deliv_cap, const tm_pair* d_pairs, const uint32_t* d_pair_word,
+                                uint64_t pair_cap, uint32_t sub_bits, void* d_workspace, uint64_t workspace_bytes,
+                                uint64_t* d_hdr, tm_inbox* d_inbox, uint64_t inbox_cap, uint32_t* d_ent_pub,
+                                uint32_t* d_ent_to, uint32_t* d_ent_word, uint64_t ent_cap, void* hip_stream);
+
 /* ---- publisher contexts: round-robin cursors and sticky entries --------------
  * do_pick_subscriber(Group, Topic, round_robin, _ClientId, Count) keeps its
  * counter in the PUBLISHER's process dictionary, under {shared_sub_round_robin,
@@ -1396,6 +1461,30 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
  * submit, and behaves exactly as it did. */
 #define TM_BATCHER_OPTS         256u  /* with TM_BATCHER_PUBLISH: records and pairs come with their words */
 #define TM_BATCHER_UPGRADE_QOS  512u  /* with TM_BATCHER_OPTS: TM_DELIVER_UPGRADE_QOS for every batch */
+/* TM_BATCHER_INBOX (with TM_BATCHER_PUBLISH | TM_BATCHER_OPTS, through
+ * tm_batcher_open_inbox only): the batch's local sends reach the caller grouped
+ * per receiving session.  A lane runs tm_publish_stream_opts_device and then
+ * tm_inbox_plan_stream_device on the same stream with no wait between them,
+ * and reads back the publish header, the offsets, the delivery records and the
+ * pick words, and the plan's header, records and entry planes -- not the pairs
+ * and the pair words, which the plan replaces (one copy and one wait for
+ * batches of up to 32768 topics, exact sizes after the headers for larger
+ * ones).  Per batch the tm_inbox_done_fn is called first, once, from the
+ * lane's thread; then the per-publish tm_publish_opts_done_fn callbacks run as
+ * without the flag, except that pairs and pair_word are NULL and n_pairs is the
+ * publish's pair count: they still carry deliv and pick_word, which a
+ * publisher needs for its {dispatch, To, Count} results, for the TM_NOT_LOCAL
+ * forwards and for the TM_NO_WORD picks.  The flag combines with
+ * TM_BATCHER_ROUND_ROBIN, TM_BATCHER_STICKY, TM_BATCHER_UPGRADE_QOS and
+ * TM_BATCHER_EAGER.
+ * Reruns: a publish state other than 0 runs both calls again, as without the
+ * flag.  A plan state of 2 (publish state 0) reruns ONLY THE PLAN, over the
+ * outputs still on the device: with round robin or sticky the publish call has
+ * stored its cursors, and a second run would advance them twice.  Each lane
+ * keeps its own sub_bits, 16 at first, raised to the width of the id a state 2
+ * reports; ent_cap = inbox_cap = caps.pairs + caps.routes, so the plan states 3
+ * and 4 do not occur.  Plan reruns count in tm_batcher_stats.reruns. */
+#define TM_BATCHER_INBOX        1024u /* with TM_BATCHER_OPTS: one plan per batch, tm_batcher_open_inbox */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {
@@ -1456,6 +1545,22 @@ typedef void (*tm_publish_opts_done_fn)(void* ctx, uint64_t ticket, int status, 
 int  tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
                                     uint32_t pub_flags, uint32_t pub_from, tm_publish_opts_done_fn done, void* ctx,
                                     uint64_t* ticket_out);
+/* TM_BATCHER_INBOX: the plan of one batch (tm_inbox_plan: hdr {E, S, pair
+ * sends, pick sends}, inbox[n_inbox = S], the entry planes[n_ent = E]), valid
+ * during the call.  tickets[n_pub] are the batch's tickets in submission order,
+ * and ent_pub[e] & ~TM_INBOX_PICK indexes them.  A failed batch (and a
+ * host-only engine: TM_EDEVICE) calls it with the status, every array NULL and
+ * every count 0, and then the batch's per-publish callbacks with the same
+ * status.  tm_batcher_open with the flag set: TM_EINVAL;
+ * tm_batcher_open_inbox without the flag, without TM_BATCHER_PUBLISH |
+ * TM_BATCHER_OPTS, with a NULL cfg or a NULL fn: TM_EINVAL; otherwise as
+ * tm_batcher_open.  Submits go through tm_batcher_submit_publish_opts. */
+typedef void (*tm_inbox_done_fn)(void* ctx, int status, uint32_t n_pub, const uint64_t* tickets,
+                                 const uint64_t hdr[TM_INBOX_HDR_WORDS], const tm_inbox* inbox, uint32_t n_inbox,
+                                 const uint32_t* ent_pub, const uint32_t* ent_to, const uint32_t* ent_word,
+                                 uint32_t n_ent);
+int  tm_batcher_open_inbox(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn fn, void* ctx,
+                           tm_batcher** out);
 /* seal the open batch and wait until every submitted topic has completed */
 int  tm_batcher_flush(tm_batcher* b);
 /* the counters up to sync_ns (TM_BATCHER_STATS_V1_BYTES bytes; max_* untouched) */

@@ -6,7 +6,9 @@
 // nothing queued); partial takes (max_topics 64, one lane, producers far
 // ahead, so seals take a stripe's oldest topics and their keys and advance its
 // head); a close with requests in flight; the flag combinations
-// tm_batcher_open refuses; tm_publish_pack_device's argument checks.  Build
+// tm_batcher_open refuses; tm_publish_pack_device's argument checks; the inbox
+// mode (tm_batcher_open_inbox: per batch the batch callback with TM_EDEVICE,
+// null arrays and zero counts, then that batch's per-publish callbacks) and the flag combinations its two open calls refuse.  Build
 // and run: make san_batcher (host code under -fsanitize=address,undefined; the
 // kernels are linked as built, never run).
 #include <atomic>
@@ -44,6 +46,73 @@ static void on_publish(void* ctx, uint64_t, int status, const tm_delivery* deliv
 }
 static void on_plain(void* ctx, uint64_t, int, const uint32_t*, const uint32_t*, uint32_t) {
     static_cast<Tally*>(ctx)->plain.fetch_add(1, std::memory_order_relaxed);
+}
+
+// the inbox mode on one lane: a batch callback, then that batch's 1 .. max_topics
+// publishes, then the next batch callback
+struct InboxTally {
+    std::atomic<uint64_t> bad{0}, batches{0}, pubs{0};
+    uint64_t since = 0;   // publishes completed since the last batch callback (one lane: no lock)
+};
+static void on_inbox(void* ctx, int status, uint32_t n_pub, const uint64_t* tickets, const uint64_t* hdr,
+                     const tm_inbox* inbox, uint32_t n_inbox, const uint32_t* ent_pub, const uint32_t* ent_to,
+                     const uint32_t* ent_word, uint32_t n_ent) {
+    InboxTally* t = static_cast<InboxTally*>(ctx);
+    if (status != TM_EDEVICE || n_pub || tickets || hdr || inbox || n_inbox || ent_pub || ent_to || ent_word || n_ent ||
+        (t->batches.load() && !t->since))
+        t->bad.fetch_add(1, std::memory_order_relaxed);
+    t->since = 0;
+    t->batches.fetch_add(1, std::memory_order_relaxed);
+}
+static void on_inbox_publish(void* ctx, uint64_t, int status, const tm_delivery* deliv, const uint32_t* pick_word,
+                             uint32_t n_deliv, const tm_pair* pairs, const uint32_t* pair_word, uint32_t n_pairs) {
+    InboxTally* t = static_cast<InboxTally*>(ctx);
+    if (status != TM_EDEVICE || deliv || pick_word || n_deliv || pairs || pair_word || n_pairs || !t->batches.load() ||
+        ++t->since > 64)
+        t->bad.fetch_add(1, std::memory_order_relaxed);
+    t->pubs.fetch_add(1, std::memory_order_relaxed);
+}
+static void inbox_phase() {
+    const uint32_t need = TM_BATCHER_PUBLISH | TM_BATCHER_OPTS | TM_BATCHER_INBOX;
+    tm_batcher_config cfg{};
+    cfg.max_topics = 64;
+    cfg.deadline_us = 50;
+    cfg.lanes_per_replica = 1;
+    InboxTally tally;
+    tm_batcher* b = nullptr;
+    cfg.flags = need;
+    expect(tm_batcher_open(E, &cfg, &b) == TM_EINVAL && !b, "tm_batcher_open with TM_BATCHER_INBOX");
+    expect(tm_batcher_open_inbox(E, &cfg, nullptr, &tally, &b) == TM_EINVAL && !b, "open_inbox: null fn");
+    expect(tm_batcher_open_inbox(E, nullptr, on_inbox, &tally, &b) == TM_EINVAL && !b, "open_inbox: null cfg");
+    for (uint32_t missing : {TM_BATCHER_PUBLISH, TM_BATCHER_OPTS, TM_BATCHER_INBOX}) {
+        cfg.flags = need & ~missing;
+        expect(tm_batcher_open_inbox(E, &cfg, on_inbox, &tally, &b) == TM_EINVAL && !b, "open_inbox: a flag missing");
+    }
+    cfg.flags = need | TM_BATCHER_ROUND_ROBIN | TM_BATCHER_UPGRADE_QOS | TM_BATCHER_EAGER;
+    expect(tm_batcher_open_inbox(E, &cfg, on_inbox, &tally, &b) == TM_OK && b, "tm_batcher_open_inbox");
+    const int threads = 3;
+    const uint32_t per = 4000;
+    std::vector<std::thread> th;
+    for (int k = 0; k < threads; ++k)
+        th.emplace_back([&, k] {
+            for (uint32_t i = 0; i < per; ++i) {
+                const std::string t = "q/" + std::to_string(k) + "/" + std::to_string(i);
+                if (tm_batcher_submit_publish_opts(b, reinterpret_cast<const uint8_t*>(t.data()), (uint32_t)t.size(), i,
+                                                   i % 3, TM_NO_SUBSCRIBER, on_inbox_publish, &tally, nullptr) != TM_OK)
+                    tally.bad.fetch_add(1, std::memory_order_relaxed);
+            }
+        });
+    for (auto& t : th) t.join();
+    expect(tm_batcher_flush(b) == TM_OK, "tm_batcher_flush");
+    tm_batcher_stats st{};
+    expect(tm_batcher_get_stats2(b, &st, sizeof(st), 0) == TM_OK, "tm_batcher_get_stats2");
+    tm_batcher_close(b);
+    expect(st.topics == (uint64_t)threads * per && st.failed_batches == st.batches, "inbox stats");
+    expect(tally.batches.load() == st.batches && tally.pubs.load() == st.topics && tally.since > 0,
+           "one batch callback per batch, before its publishes");
+    expect(tally.bad.load() == 0, "every inbox callback carries TM_EDEVICE and no arrays");
+    std::printf("%-28s ok: %llu submits, %llu batches\n", "inbox mode", (unsigned long long)st.topics,
+                (unsigned long long)st.batches);
 }
 
 // `threads` producers submit `per` topics each; close_early: tm_batcher_close
@@ -148,6 +217,7 @@ int main() {
         expect(call(p, p, p, p) == TM_EDEVICE, "pack: host-only engine");
         std::printf("%-28s ok\n", "pack argument checks");
     }
+    inbox_phase();
     tm_close(E);
     std::printf("san_batcher: all phases ok\n");
     return 0;
