@@ -10,7 +10,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-result 
 BUILD   ?= build
 LIBOUT  ?= emqx_amd/libtopicmatch.so
 
-all: $(LIBOUT) emqx_amd/libtmwork.so oracle/liboracle.so tools/ubench/batcher_bench tools/ubench/libbatchdrive.so tools/ubench/libpubdrive.so tools/ubench/libinboxdrive.so
+all: $(LIBOUT) emqx_amd/libtmwork.so oracle/liboracle.so tools/ubench/batcher_bench tools/ubench/libbatchdrive.so tools/ubench/libpubdrive.so tools/ubench/libinboxdrive.so tools/ubench/libfwddrive.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -72,6 +72,10 @@ tools/ubench/libpubdrive.so: tools/ubench/pubdrive.cpp emqx_amd/libtopicmatch.so
 
 # options batcher flood, host regrouping against the inbox mode (tools/bench_inbox_stream.py; measurement helper, ctypes)
 tools/ubench/libinboxdrive.so: tools/ubench/inboxdrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
+
+# publish batcher flood, host regrouping per node against the forward mode (tools/bench_forward_stream.py; measurement helper, ctypes)
+tools/ubench/libfwddrive.so: tools/ubench/fwddrive.cpp emqx_amd/libtopicmatch.so include/topicmatch.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -pthread $< -Lemqx_amd -ltopicmatch -Wl,-rpath,'$$ORIGIN/../../emqx_amd' -o $@
 
 # tm_route_* / tm_sub_* / tm_share_* host calls under AddressSanitizer + UBSan on a host-only engine:

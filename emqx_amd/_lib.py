@@ -122,6 +122,7 @@ TM_BATCHER_STICKY = 128
 TM_BATCHER_OPTS = 256
 TM_BATCHER_UPGRADE_QOS = 512
 TM_BATCHER_INBOX = 1024
+TM_BATCHER_FORWARD = 2048
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
 
@@ -144,6 +145,9 @@ PUBLISH_OPTS_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, 
 # ent_word, n_ent)
 INBOX_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, c_u64p, c_u64p, c_u32p,
                                  ctypes.c_uint32, c_u32p, c_u32p, c_u32p, ctypes.c_uint32)
+# tm_forward_done_fn: (ctx, status, n_pub, tickets, hdr, groups (16 B records as u32), n_groups, pub, n_fwd)
+FORWARD_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, c_u64p, c_u64p, c_u32p,
+                                   ctypes.c_uint32, c_u32p, ctypes.c_uint32)
 
 # (name, restype, argtypes) — every symbol include/topicmatch.h declares
 SIGNATURES = [
@@ -367,6 +371,12 @@ SIGNATURES = [
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                        ctypes.c_uint64]),
+    ("tm_forward_plan_stream_workspace_bytes", ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]),
+    ("tm_forward_plan_stream_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                     ctypes.c_uint64, ctypes.c_void_p]),
     ("tm_inbox_plan_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -430,6 +440,8 @@ SIGNATURES = [
                                        ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_open_inbox", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig), INBOX_DONE_FN,
                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("tm_batcher_open_plans", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig), INBOX_DONE_FN,
+                                             FORWARD_DONE_FN, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_batcher_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, DONE_FN, ctypes.c_void_p,
                                          c_u64p]),
     ("tm_batcher_submit_publish", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,

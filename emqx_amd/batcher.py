@@ -14,7 +14,10 @@ through tm_publish_stream_device too (an A/B switch); opts=True
 $share pick with the records; inbox=callable (with publish=True, opts=True)
 opens the inbox mode (tm_batcher_open_inbox): per batch the callable gets the
 batch's local sends grouped per receiving session before the per-publish
-callbacks run, which then carry no pairs.  This is the NIF's path: the callback there builds
+callbacks run, which then carry no pairs; forward=callable (with publish=True;
+tm_batcher_open_plans, combines with inbox=) likewise hands over the batch's
+remote-node deliveries grouped per (node, To), after the inbox callback and
+before the per-publish callbacks, which are unchanged.  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
 import itertools
@@ -27,24 +30,35 @@ from . import _lib as L
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
                  lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0, round_robin=False,
-                 stream=False, sticky=False, opts=False, upgrade_qos=False, inbox=None):
+                 stream=False, sticky=False, opts=False, upgrade_qos=False, inbox=None, forward=None):
         self.engine = engine
         self.lib = engine.lib
         flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
             (L.TM_BATCHER_PUBLISH if publish else 0) | (L.TM_BATCHER_EAGER if eager else 0) | \
             (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0) | \
             (L.TM_BATCHER_STICKY if sticky else 0) | (L.TM_BATCHER_OPTS if opts else 0) | \
-            (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0) | (L.TM_BATCHER_INBOX if inbox is not None else 0)
+            (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0) | (L.TM_BATCHER_INBOX if inbox is not None else 0) | \
+            (L.TM_BATCHER_FORWARD if forward is not None else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
         self.inbox = inbox
-        if inbox is not None:
+        self.forward = forward
+        if forward is not None:
+            what = "tm_batcher_open_plans"
+            self._idone = L.INBOX_DONE_FN(self._on_inbox_done) if inbox is not None else \
+                ctypes.cast(None, L.INBOX_DONE_FN)
+            self._fdone = L.FORWARD_DONE_FN(self._on_forward_done)   # kept alive with the batcher
+            rc = self.lib.tm_batcher_open_plans(engine.h, ctypes.byref(cfg), self._idone, self._fdone, None,
+                                                ctypes.byref(h))
+        elif inbox is not None:
+            what = "tm_batcher_open_inbox"
             self._idone = L.INBOX_DONE_FN(self._on_inbox_done)   # kept alive with the batcher
             rc = self.lib.tm_batcher_open_inbox(engine.h, ctypes.byref(cfg), self._idone, None, ctypes.byref(h))
         else:
+            what = "tm_batcher_open"
             rc = self.lib.tm_batcher_open(engine.h, ctypes.byref(cfg), ctypes.byref(h))
         if rc != L.TM_OK:
-            raise L.TopicMatchError(rc, "tm_batcher_open_inbox" if inbox is not None else "tm_batcher_open")
+            raise L.TopicMatchError(rc, what)
         self.h = h
         self.routes = routes
         self._cbs = {}
@@ -117,6 +131,24 @@ class Batcher:
             return
         self.inbox(status, tk, view(hdr, 4, np.uint64), view(inbox, n_inbox * 4, np.uint32).reshape(-1, 4),
                    view(ent_pub, n_ent, np.uint32), view(ent_to, n_ent, np.uint32), view(ent_word, n_ent, np.uint32))
+
+    def _on_forward_done(self, _ctx, status, n_pub, tickets, hdr, groups, n_groups, pub, n_fwd):
+        """forward(status, tickets, hdr, groups, pub) on the lane's thread, after
+        the batch's inbox callback and before its per-publish callbacks: numpy
+        views of the lane's buffers, valid during the call only (tickets
+        u64[n_pub]; hdr u64[4] = {M, G, targets, 0}; groups u32[G, 4] = rows
+        {node target, To, first, count}; pub u32[M], indices into tickets); on a
+        failed batch tickets is empty and everything else but status is None"""
+        def view(ptr, n, dtype):
+            if not n:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(ptr, shape=(n,)).view(dtype)
+        tk = view(tickets, n_pub, np.uint64)
+        if status != L.TM_OK:
+            self.forward(status, tk, None, None, None)
+            return
+        self.forward(status, tk, view(hdr, 4, np.uint64), view(groups, n_groups * 4, np.uint32).reshape(-1, 4),
+                     view(pub, n_fwd, np.uint32))
 
     def _on_publish_opts_done(self, ctx, ticket, status, deliv, pick_word, n_deliv, pairs, pair_word, n_pairs):
         cb = self._cbs.pop(ctx)

@@ -52,6 +52,15 @@
 // before the per-publish callbacks run.  A plan that found an id wider than the
 // lane's sort width runs again ALONE over the outputs still on the device: the
 // publish call has stored its cursors, a second run would advance them twice.
+//
+// TM_BATCHER_FORWARD (tm_batcher_open_plans) regroups the batch's remote-node
+// deliveries per receiving node on the device: behind the stream-ordered publish
+// call (and the inbox plan, when there is one) the lane enqueues
+// tm_forward_plan_stream_device on the same stream, with no wait between them,
+// and the plan (header, one record per (node, To), the publish indices) comes
+// back with the rest of the block.  One callback per batch hands it over, after
+// the inbox plan's and before the per-publish callbacks, which are unchanged.
+// The forward plan is stateless, so it reruns only with the whole chain.
 #include <cstdlib>
 #include <hip/hip_runtime_api.h>
 
@@ -229,6 +238,11 @@ struct Lane {
     const uint32_t* r_epub = nullptr;
     const uint32_t* r_eto = nullptr;
     const uint32_t* r_ewd = nullptr;
+    // TM_BATCHER_FORWARD: the forward plan's workspace and the plan as the batch callback reads it
+    Dev d_fws;
+    const uint64_t* r_fhdr = nullptr;
+    const tm_forward_group* r_fgroups = nullptr;
+    const uint32_t* r_fpub = nullptr;
     clk::time_point sealed;           // when the batch was handed over
     uint64_t launch_ns = 0, sync_ns = 0;   // this batch: host time enqueueing the device work, waiting on it
 };
@@ -254,6 +268,8 @@ struct tm_batcher {
     bool inbox = false;     // TM_BATCHER_INBOX: the plan per batch through ifn, no pairs in the per-publish callbacks
     tm_inbox_done_fn ifn = nullptr;
     void* ictx = nullptr;
+    bool forward = false;   // TM_BATCHER_FORWARD: the forward plan per batch through ffn (ctx: ictx)
+    tm_forward_done_fn ffn = nullptr;
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -693,9 +709,20 @@ struct tm_batcher {
     // words move behind what comes back, and the plan takes their place:
     //   [hdr][doff][sub_off][deliveries][pick words][plan hdr 8 u64][records ecap x 16 B][ent_pub][ent_to]
     //   [ent_word] | [pairs][pair words],   ecap = cap + scap (every send fits: no plan state 3 or 4)
+    // TM_BATCHER_FORWARD adds the forward plan at the end of what comes back (before the `|`):
+    //   [plan hdr 8 u64][groups cap x 16 B][pub cap x 4 B]   (pub_cap = group_cap = cap: no plan state 3 or 4)
     struct BlockLayout {
         uint64_t o_pairs, o_pickw, o_pairw, o_ihdr, o_inbox, o_epub, o_eto, o_ewd, backb, outb, ecap;
+        uint64_t o_fhdr, o_fgroups, o_fpub;
     };
+    // the forward plan from `at` on; returns its end
+    uint64_t forward_layout(BlockLayout& B, uint64_t at, uint64_t cap) const {
+        if (!forward) return at;
+        B.o_fhdr = (at + 15) & ~15ull;
+        B.o_fgroups = B.o_fhdr + 8 * TM_FORWARD_STREAM_HDR_WORDS;
+        B.o_fpub = B.o_fgroups + cap * 16;
+        return B.o_fpub + cap * 4;
+    }
     BlockLayout block_layout(uint32_t n, uint64_t cap, uint64_t scap) const {
         BlockLayout B{};
         const uint64_t head = ps_head(n), wb = opts ? 4 : 0;
@@ -703,7 +730,7 @@ struct tm_batcher {
             B.o_pairs = head + cap * 16;
             B.o_pickw = B.o_pairs + scap * 8;
             B.o_pairw = B.o_pickw + cap * wb;
-            B.outb = B.backb = B.o_pairw + scap * wb;
+            B.outb = B.backb = forward_layout(B, B.o_pairw + scap * wb, cap);
             return B;
         }
         B.ecap = cap + scap;
@@ -713,7 +740,7 @@ struct tm_batcher {
         B.o_epub = B.o_inbox + B.ecap * 16;
         B.o_eto = B.o_epub + B.ecap * 4;
         B.o_ewd = B.o_eto + B.ecap * 4;
-        B.o_pairs = B.backb = (B.o_ewd + B.ecap * 4 + 15) & ~15ull;
+        B.o_pairs = B.backb = (forward_layout(B, B.o_ewd + B.ecap * 4, cap) + 15) & ~15ull;
         B.o_pairw = B.o_pairs + scap * 8;
         B.outb = B.o_pairw + scap * 4;
         return B;
@@ -754,6 +781,8 @@ struct tm_batcher {
             const uint64_t wsb = opts ? tm_publish_stream_opts_workspace_bytes(eng, n, nbytes, &caps)
                                       : tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
             if (!wsb) return TM_ERANGE;
+            const uint64_t fwsb = forward ? tm_forward_plan_stream_workspace_bytes(n, cap, cap) : 0;
+            if (forward && (!fwsb || !L.d_fws.ensure(fwsb))) return fwsb ? TM_ENOMEM : TM_ERANGE;
             if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? backb : head)) return TM_ENOMEM;
             uint8_t* d = (uint8_t*)L.d_out.p;
             dv.sub_deliver = (uint32_t*)(d + o_pairw);
@@ -780,10 +809,20 @@ struct tm_batcher {
                 const int prc = plan();
                 if (prc != TM_OK) return prc;
             }
+            if (forward) {   // behind the publish call and the inbox plan; never again without them
+                const int frc = tm_forward_plan_stream_device(
+                    eng, n, (const uint64_t*)d, (const uint64_t*)(d + 64), (const tm_delivery*)(d + head), cap,
+                    L.d_fws.p, fwsb, (uint64_t*)(d + B.o_fhdr), (tm_forward_group*)(d + B.o_fgroups), cap,
+                    (uint32_t*)(d + B.o_fpub), cap, s);
+                if (frc != TM_OK) return frc;
+            }
             // a small batch: everything up to backb (without TM_BATCHER_INBOX the whole block) in one copy
+            if (((inbox || forward) && !eager && !L.h_out.ensure(backb))) return TM_ENOMEM;
             if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? backb : head, hipMemcpyDeviceToHost, s)) ||
                 (inbox && !eager &&
-                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, 64, hipMemcpyDeviceToHost, s))))
+                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, 64, hipMemcpyDeviceToHost, s))) ||
+                (forward && !eager &&
+                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_fhdr, d + B.o_fhdr, 64, hipMemcpyDeviceToHost, s))))
                 return TM_EDEVICE;
             L.launch_ns += ns_since(t0);
             t0 = clk::now();
@@ -825,6 +864,8 @@ struct tm_batcher {
                     if (!L.h_out.ensure(backb)) return TM_ENOMEM;   // may move: the head is read again below
                     const uint64_t* ih = inbox ? (const uint64_t*)((const uint8_t*)L.h_out.p + B.o_ihdr) : nullptr;
                     const uint64_t E = inbox ? ih[0] : 0, S = inbox ? ih[1] : 0;
+                    const uint64_t* fh = forward ? (const uint64_t*)((const uint8_t*)L.h_out.p + B.o_fhdr) : nullptr;
+                    const uint64_t FM = forward ? fh[0] : 0, FG = forward ? fh[1] : 0;
                     auto down = [&](uint64_t o, uint64_t bytes) {
                         return !bytes || chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o, d + o, bytes, hipMemcpyDeviceToHost, s));
                     };
@@ -833,6 +874,7 @@ struct tm_batcher {
                         (opts && !inbox && !down(o_pairw, P * 4)) ||
                         (inbox && (!down(B.o_ihdr, 64 + S * 16) || !down(B.o_epub, E * 4) || !down(B.o_eto, E * 4) ||
                                    !down(B.o_ewd, E * 4))) ||
+                        (forward && (!down(B.o_fhdr, 64 + FG * 16) || !down(B.o_fpub, FM * 4))) ||
                         !chk(hipStreamSynchronize(s)))
                         return TM_EDEVICE;
                     L.sync_ns += ns_since(t0);
@@ -850,6 +892,12 @@ struct tm_batcher {
                     L.r_epub = (const uint32_t*)(h + B.o_epub);
                     L.r_eto = (const uint32_t*)(h + B.o_eto);
                     L.r_ewd = (const uint32_t*)(h + B.o_ewd);
+                }
+                if (forward) {
+                    L.r_fhdr = (const uint64_t*)(h + B.o_fhdr);
+                    if (L.r_fhdr[6] != 0) return TM_EDEVICE;   // pub_cap = group_cap = cap: a publish state of 0 leaves none
+                    L.r_fgroups = (const tm_forward_group*)(h + B.o_fgroups);
+                    L.r_fpub = (const uint32_t*)(h + B.o_fpub);
                 }
                 results = D;
                 return TM_OK;
@@ -986,16 +1034,25 @@ struct tm_batcher {
                     for (uint32_t i = 0; i < n; ++i) results += L.r_counts[i];
             }
             const uint32_t m = n;
-            if (inbox) {   // the batch's plan first, once, on this thread; then the per-publish callbacks
+            if (inbox || forward) {   // the batch's plans first, once each, on this thread; then the per-publish callbacks
                 L.tickets.clear();
                 if (rc == TM_OK)
                     for (const Chunk& c : L.chunks)
                         for (size_t j = c.head; j < c.reqs.size(); ++j) L.tickets.push_back(c.reqs[j].ticket);
+            }
+            if (inbox) {
                 if (rc == TM_OK)
                     ifn(ictx, TM_OK, m, L.tickets.data(), L.r_ihdr, L.r_inbox, (uint32_t)L.r_ihdr[1], L.r_epub, L.r_eto,
                         L.r_ewd, (uint32_t)L.r_ihdr[0]);
                 else
                     ifn(ictx, rc, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0);
+            }
+            if (forward) {
+                if (rc == TM_OK)
+                    ffn(ictx, TM_OK, m, L.tickets.data(), L.r_fhdr, L.r_fgroups, (uint32_t)L.r_fhdr[1], L.r_fpub,
+                        (uint32_t)L.r_fhdr[0]);
+                else
+                    ffn(ictx, rc, 0, nullptr, nullptr, nullptr, 0, nullptr, 0);
             }
             run_callbacks(L, rc, routes, m);
             const clk::time_point t_cb = clk::now();
@@ -1162,9 +1219,10 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
 
 extern "C" {
 
-// ifn: the batch callback of tm_batcher_open_inbox (the caller checked the flags), else null
-static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn ifn, void* ictx,
-                        tm_batcher** out) {
+// ifn / ffn: the batch callbacks of tm_batcher_open_inbox / tm_batcher_open_plans (the caller checked the
+// flags), else null
+static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn ifn, tm_forward_done_fn ffn,
+                        void* ictx, tm_batcher** out) {
     if (!e || !out) return TM_EINVAL;
     tm_batcher* b = new (std::nothrow) tm_batcher();
     if (!b) return TM_ENOMEM;
@@ -1173,6 +1231,8 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
     b->inbox = ifn != nullptr;
     b->ifn = ifn;
     b->ictx = ictx;
+    b->forward = ffn != nullptr;
+    b->ffn = ffn;
     if (b->cfg.max_topics == 0) b->cfg.max_topics = 65536;
     if (b->cfg.max_bytes == 0) b->cfg.max_bytes = 64ull << 20;
     if (b->cfg.deadline_us == 0) b->cfg.deadline_us = 200;
@@ -1200,7 +1260,8 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
     b->opts = (b->cfg.flags & TM_BATCHER_OPTS) != 0;
     b->upgrade = (b->cfg.flags & TM_BATCHER_UPGRADE_QOS) != 0;
     // an options lane takes one path, the stream-ordered call, for keyed picks too
-    b->stream = b->round_robin || b->sticky || b->opts || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
+    // (and a forward lane: its plan reads the stream-ordered call's packed records)
+    b->stream = b->round_robin || b->sticky || b->opts || b->forward || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
@@ -1266,6 +1327,8 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
                 const tm_batcher::BlockLayout B = b->block_layout((uint32_t)pre, c.routes, c.pairs);
                 if (b->inbox)
                     (void)L->d_iws.ensure(tm_inbox_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.pairs, B.ecap));
+                if (b->forward)
+                    (void)L->d_fws.ensure(tm_forward_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.routes));
                 (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(B.outb) && L->h_out.ensure(B.backb) &&
                        L->d_ws.ensure(b->opts ? tm_publish_stream_opts_workspace_bytes(e, (uint32_t)pre, nbytes, &c)
                                               : tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
@@ -1309,15 +1372,24 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
 }
 
 int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out) {
-    if (cfg && (cfg->flags & TM_BATCHER_INBOX)) return TM_EINVAL;   // the mode needs its batch callback
-    return batcher_open(e, cfg, nullptr, nullptr, out);
+    if (cfg && (cfg->flags & (TM_BATCHER_INBOX | TM_BATCHER_FORWARD))) return TM_EINVAL;   // the modes need their batch callbacks
+    return batcher_open(e, cfg, nullptr, nullptr, nullptr, out);
 }
 
 int tm_batcher_open_inbox(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn fn, void* ctx,
                           tm_batcher** out) {
     const uint32_t need = TM_BATCHER_INBOX | TM_BATCHER_PUBLISH | TM_BATCHER_OPTS;
-    if (!cfg || !fn || (cfg->flags & need) != need) return TM_EINVAL;
-    return batcher_open(e, cfg, fn, ctx, out);
+    if (!cfg || !fn || (cfg->flags & need) != need || (cfg->flags & TM_BATCHER_FORWARD)) return TM_EINVAL;
+    return batcher_open(e, cfg, fn, nullptr, ctx, out);
+}
+
+int tm_batcher_open_plans(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn inbox_fn,
+                          tm_forward_done_fn forward_fn, void* ctx, tm_batcher** out) {
+    if (!cfg) return TM_EINVAL;
+    const bool inbox = (cfg->flags & TM_BATCHER_INBOX) != 0, forward = (cfg->flags & TM_BATCHER_FORWARD) != 0;
+    if ((!inbox && !forward) || inbox != (inbox_fn != nullptr) || forward != (forward_fn != nullptr)) return TM_EINVAL;
+    if (!(cfg->flags & TM_BATCHER_PUBLISH) || (inbox && !(cfg->flags & TM_BATCHER_OPTS))) return TM_EINVAL;
+    return batcher_open(e, cfg, inbox_fn, forward_fn, ctx, out);
 }
 
 int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn fn, void* ctx,

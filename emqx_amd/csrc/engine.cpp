@@ -5977,6 +5977,123 @@ int tm_inbox_plan_stream_device(tm_engine* e, uint32_t n, const uint64_t* d_pub_
     return rc;
 }
 
+// ---- tm_forward_plan_stream_device: the forward plan without a host wait ----
+// As the inbox plan above: every intermediate in the caller's workspace, 256 B
+// aligned pieces, each a monotone function of the capacities; n sizes nothing.
+namespace {
+struct ForwardStreamLayout {
+    uint64_t ctl, flag, pubidx, pre, scan, kv, head, ht, counts, off, sscan, bytes;
+};
+bool forward_stream_caps_ok(uint32_t n, uint64_t deliv_cap, uint64_t pub_cap) {
+    const uint64_t lim = 0xFFFFFFFEull;   // records and pairs are u32 indices on the device
+    return n < 0x80000000u && deliv_cap < lim && pub_cap < lim;
+}
+ForwardStreamLayout forward_stream_layout(uint64_t deliv_cap, uint64_t pub_cap) {
+    ForwardStreamLayout L{};
+    uint64_t at = 0;
+    auto take = [&](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    };
+    const uint32_t pc = tmx::presort_counts((uint32_t)pub_cap);
+    L.ctl = take(64);
+    L.flag = take(deliv_cap * 4 + 4);
+    L.pubidx = take(deliv_cap * 4 + 4);
+    L.pre = take((deliv_cap + 1) * 8);
+    L.scan = take(tmx::scan_tmp_elems((uint32_t)std::max(deliv_cap, pub_cap)) * 8 + 8);
+    L.kv = take(pub_cap * 16);
+    L.head = take(pub_cap * 8);
+    L.ht = take((pub_cap + 1) * 16);
+    L.counts = take((uint64_t)pc * 4);
+    L.off = take(((uint64_t)pc + 1) * 8);
+    L.sscan = take(tmx::scan_tmp_elems(pc) * 8 + 8);
+    L.bytes = at;
+    return L;
+}
+}  // namespace
+
+uint64_t tm_forward_plan_stream_workspace_bytes(uint32_t n, uint64_t deliv_cap, uint64_t pub_cap) {
+    if (!forward_stream_caps_ok(n, deliv_cap, pub_cap)) return 0;
+    return forward_stream_layout(deliv_cap, pub_cap).bytes;
+}
+
+int tm_forward_plan_stream_device(tm_engine* e, uint32_t n, const uint64_t* d_pub_hdr, const uint64_t* d_doff,
+                                  const tm_delivery* d_deliv, uint64_t deliv_cap, void* d_workspace,
+                                  uint64_t workspace_bytes, uint64_t* d_hdr, tm_forward_group* d_groups,
+                                  uint64_t group_cap, uint32_t* d_pub, uint64_t pub_cap, void* hip_stream) {
+    if (!d_pub_hdr || !d_doff || !d_hdr || !d_workspace) return TM_EINVAL;
+    if ((deliv_cap && !d_deliv) || (group_cap && !d_groups) || (pub_cap && !d_pub)) return TM_EINVAL;
+    if (!e) return TM_EINVAL;
+    if (!forward_stream_caps_ok(n, deliv_cap, pub_cap) || group_cap >= 0xFFFFFFFEull)
+        return guarded(e, [&]() -> int {
+            throw RangeError("forward: a capacity of 2^32 - 2 or more, or 2^31 topics or more, in one batch");
+        });
+    const ForwardStreamLayout L = forward_stream_layout(deliv_cap, pub_cap);
+    if (workspace_bytes < L.bytes) return TM_EINVAL;
+    if (int rc = local_node_unset(e)) return rc;
+    if (e->devs.empty()) return no_device(e, "forward plan");
+    DevState& d = *e->replica_for(d_pub_hdr);
+    // the batch lock and the pin for the image's target table (as the publish
+    // call); no replica workspace is touched, so no rw_drain / rw_release
+    return batch_call(e, {&d}, [&]() -> int {
+        tm_engine::Guard g(d.device);
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : d.stream;
+        if (n == 0) {
+            HIPCHK(hipMemsetAsync(d_hdr, 0, TM_FORWARD_STREAM_HDR_WORDS * 8, st));
+            return TM_OK;
+        }
+        using namespace tmx;
+        const ForwardView& fv = tm_engine::forward_view(d);
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        auto u32 = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(ws + o); };
+        auto u64 = [&](uint64_t o) { return reinterpret_cast<uint64_t*>(ws + o); };
+        uint32_t to_bits = 0, tg_bits = 0;   // as forward_plan: the host knows both at enqueue time
+        while (to_bits < 32 && ((uint64_t)1 << to_bits) <= fv.n_filters) ++to_bits;   // keys 0 .. n_filters
+        while (tg_bits < 32 && ((uint64_t)1 << tg_bits) < fv.n_targets) ++tg_bits;    // keys below n_targets
+        const uint32_t to_passes = (to_bits + 7) / 8, tg_passes = (tg_bits + 7) / 8;
+        uint64_t* ctl = u64(L.ctl);
+        uint32_t* flag = u32(L.flag);
+        uint32_t* pubidx = u32(L.pubidx);
+        uint64_t* P = u64(L.pre);
+        HIPCHK(hipMemsetAsync(ctl, 0, 64, st));
+        HIPCHK(launch_forward_stream_flag(fv, n, d_pub_hdr, d_doff, d_deliv, deliv_cap, flag, st));
+        HIPCHK(launch_scan0(flag, (uint32_t)deliv_cap, P, P + deliv_cap, u64(L.scan), st));
+        HIPCHK(launch_forward_stream_check(d_pub_hdr, P, deliv_cap, pub_cap, ctl, d_hdr, st));
+        if (pub_cap == 0 || deliv_cap == 0) {   // any forward delivery is state 3; no record, none
+            d.note_use(st);
+            return TM_OK;
+        }
+        uint32_t *k0 = u32(L.kv), *v0 = k0 + pub_cap, *k1 = v0 + pub_cap, *v1 = k1 + pub_cap;
+        uint32_t* counts = u32(L.counts);
+        uint64_t* off = u64(L.off);
+        HIPCHK(launch_forward_stream_emit(fv, n, d_pub_hdr, d_doff, d_deliv, deliv_cap, flag, P, ctl, pub_cap, k0, v0,
+                                          pubidx, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, (uint32_t)pub_cap, to_passes, counts, off, u64(L.sscan), st, ctl + 1));
+        if (to_passes & 1u) {   // an odd number of passes left the pairs in (k1, v1)
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        HIPCHK(launch_forward_stream_retarget(ctl, k0, v0, d_deliv, pub_cap, st));
+        HIPCHK(launch_sort_pairs(k0, v0, k1, v1, (uint32_t)pub_cap, tg_passes, counts, off, u64(L.sscan), st, ctl + 1));
+        if (tg_passes & 1u) {
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+        uint32_t* head = u32(L.head);
+        uint32_t* thead = head + pub_cap;
+        uint64_t* H = u64(L.ht);
+        uint64_t* T = H + pub_cap + 1;
+        HIPCHK(launch_forward_stream_heads(ctl, k0, v0, d_deliv, pub_cap, head, thead, st));
+        HIPCHK(launch_scan0(head, (uint32_t)pub_cap, H, H + pub_cap, u64(L.scan), st));
+        HIPCHK(launch_scan0(thead, (uint32_t)pub_cap, T, T + pub_cap, u64(L.scan), st));
+        HIPCHK(launch_forward_stream_groups(ctl, k0, v0, d_deliv, pubidx, head, H, T, pub_cap, d_hdr, d_groups,
+                                            group_cap, d_pub, st));
+        d.note_use(st);   // the flag pass read the pinned image's target table
+        return TM_OK;
+    }, [] {});
+}
+
 static_assert(TM_NO_WORD == 0xFFFFFFFFu && (TM_NO_WORD & 3u) == tmx::SUBOPT_NONE, "a delivery word's QoS is never 3");
 
 // the descriptor of the pick-word pass: tm_deliver's per-publish arrays and flag, no pair words

@@ -194,4 +194,257 @@ hipError_t launch_forward_groups(const uint32_t* keys, const uint32_t* vals, con
     return hipGetLastError();
 }
 
+// ---- the stream-ordered plan (topicmatch.h tm_forward_plan_stream_device) ----
+// The same plan from the packed outputs of tm_publish_stream[_opts]_device
+// (pub_hdr, doff[n + 1], 16 B records {to, target, ndisp, pick}), enqueued
+// only: D and the publish state are read on the device, every grid comes from n
+// and the capacities (grid-stride loops), and the bounds are device words.  ctl
+// is 8 u64 of the caller's workspace, zeroed first:
+//   ctl[0] state (0 until tm_forward_scheck knows M)   ctl[1] m, the pairs the
+//   later kernels work on (0 unless the state is 0)
+// Packed records have no holes: record d is a candidate when doff[0] <= d <
+// min(doff[n], D, deliv_cap), so the flag pass needs no topic and runs one lane
+// per record.  The emit finds a record's topic as tm_forward_flag does (blocks
+// of 256 topics, span prefix in LDS; `split` thread blocks share a block of
+// topics as in pack.hip) and writes the pairs in record order.  It also pads the
+// sorts' keys from m to pub_cap with 0xFFFFFFFF: both sorts run over pub_cap
+// (host-known), the padding's digits are all 255, it is staged behind the live
+// pairs and both sorts are stable, so it stays last even against a live key
+// whose sorted digits are all ones; the retarget between them leaves it alone.
+// Launches for up to 32768 records and pairs: memset, flag, scan, check, emit,
+// 3 per sort pass, retarget, heads, 2 scans, groups: 10 + 3 x (To passes +
+// target passes); each larger scan adds 2.
+
+__global__ void __launch_bounds__(FBLOCK)
+tm_forward_sflag(ForwardView fv, uint32_t n, const uint64_t* __restrict__ pub_hdr, const uint64_t* __restrict__ doff,
+                 const uint4* __restrict__ deliv, uint64_t deliv_cap, uint32_t* __restrict__ flag) {
+    if (pub_hdr[6]) return;   // the publish call did not fit: tm_forward_scheck reports state 1
+    const uint64_t D = pub_hdr[2], dlo = doff[0];
+    uint64_t dhi = doff[n];
+    dhi = dhi < D ? dhi : D;
+    dhi = dhi < deliv_cap ? dhi : deliv_cap;
+    for (uint64_t d = (uint64_t)blockIdx.x * FBLOCK + threadIdx.x; d < deliv_cap; d += (uint64_t)gridDim.x * FBLOCK) {
+        uint32_t f = 0;
+        if (d >= dlo && d < dhi) {
+            const uint32_t x = deliv[d].y;
+            if (x < fv.n_targets) f = fv.fwd[x] != 0;
+        }
+        flag[d] = f;
+    }
+}
+
+// M is known: the state, the header words that do not depend on the sorts, and
+// m for the kernels behind
+__global__ void tm_forward_scheck(const uint64_t* __restrict__ pub_hdr, const uint64_t* __restrict__ P,
+                                  uint64_t deliv_cap, uint64_t pub_cap, uint64_t* __restrict__ ctl,
+                                  uint64_t* __restrict__ hdr) {
+    if (threadIdx.x != 0) return;
+    uint64_t state = 0, M = 0;
+    if (pub_hdr[6]) {
+        state = 1;
+    } else {
+        M = P[deliv_cap];
+        if (M > pub_cap) state = 3;
+    }
+    hdr[0] = M;
+    hdr[3] = 0;
+    hdr[4] = 0;
+    hdr[5] = 0;
+    hdr[7] = 0;
+    if (state || M == 0) {   // else tm_forward_sgroups writes G, the targets and the state
+        hdr[1] = 0;
+        hdr[2] = 0;
+        hdr[6] = state;
+    }
+    ctl[1] = state ? 0ull : M;
+    ctl[0] = state;
+}
+
+__global__ void __launch_bounds__(FBLOCK)
+tm_forward_semit(uint32_t n_filters, uint32_t n, const uint64_t* __restrict__ pub_hdr,
+                 const uint64_t* __restrict__ doff, const uint4* __restrict__ deliv, uint64_t deliv_cap,
+                 const uint32_t* __restrict__ flag, const uint64_t* __restrict__ P, const uint64_t* __restrict__ ctl,
+                 uint32_t split, uint64_t pub_cap, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                 uint32_t* __restrict__ pubidx) {
+    __shared__ uint64_t lds_inc[FBLOCK];   // inclusive prefix of the block's spans
+    __shared__ uint64_t lds_scan[FBLOCK / 64];
+    if (ctl[0]) return;
+    const uint64_t m = ctl[1];
+    if (m == 0) return;   // no forward delivery: the sorts and the passes behind leave too
+    uint64_t dhi = pub_hdr[2];
+    dhi = dhi < deliv_cap ? dhi : deliv_cap;
+    const uint32_t nblk = (n + FBLOCK - 1) / FBLOCK;
+    for (uint64_t v = blockIdx.x; v < (uint64_t)nblk * split; v += gridDim.x) {
+        const uint32_t t0 = (uint32_t)(v / split) * FBLOCK;
+        const uint32_t part = (uint32_t)(v % split);
+        const uint32_t tn = n - t0 < (uint32_t)FBLOCK ? n - t0 : (uint32_t)FBLOCK;
+        const uint32_t t = t0 + threadIdx.x;
+        uint64_t span = 0;
+        if (threadIdx.x < tn) {
+            const uint64_t a = doff[t], b = doff[t + 1];
+            span = b > a ? b - a : 0ull;
+        }
+        uint64_t agg;
+        const uint64_t ex = block_exclusive_scan<FBLOCK>(span, lds_scan, agg);
+        lds_inc[threadIdx.x] = ex + span;
+        __syncthreads();
+        const uint64_t base = doff[t0];
+        for (uint64_t j = (uint64_t)part * FBLOCK + threadIdx.x; j < agg; j += (uint64_t)split * FBLOCK) {
+            const uint64_t g = base + j;
+            if (g >= dhi) break;   // records at or past the bound are no deliveries
+            if (!flag[g]) continue;
+            const uint64_t p = P[g];
+            if (p >= m) continue;   // only with offsets that are not a packed batch's
+            uint32_t lo = 0, hi = tn - 1;   // local topic of record j: the first with inclusive prefix > j
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (lds_inc[mid] > j) hi = mid;
+                else lo = mid + 1;
+            }
+            const uint32_t id = deliv[g].x;
+            keys[p] = id < n_filters ? id : n_filters;   // TM_ROUTE_TOPIC_ID sorts after every filter id
+            vals[p] = (uint32_t)g;
+            pubidx[g] = t0 + lo;
+        }
+        __syncthreads();   // lds_inc is rewritten by the next round
+    }
+    // the sorts' padding, behind the live pairs
+    for (uint64_t p = m + (uint64_t)blockIdx.x * FBLOCK + threadIdx.x; p < pub_cap; p += (uint64_t)gridDim.x * FBLOCK) {
+        keys[p] = 0xFFFFFFFFu;
+        vals[p] = 0;
+    }
+}
+
+// tm_forward_retarget bounded by the device m: the padding keeps 0xFFFFFFFF
+__global__ void __launch_bounds__(FBLOCK)
+tm_forward_sretarget(const uint64_t* __restrict__ ctl, uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                     const uint4* __restrict__ deliv) {
+    if (ctl[0]) return;
+    const uint64_t m = ctl[1];
+    for (uint64_t p = (uint64_t)blockIdx.x * FBLOCK + threadIdx.x; p < m; p += (uint64_t)gridDim.x * FBLOCK)
+        keys[p] = deliv[vals[p]].y;
+}
+
+// tm_forward_heads bounded by the device m; head and thead are zeroed from m
+// to pub_cap (their scans run over pub_cap)
+__global__ void __launch_bounds__(FBLOCK)
+tm_forward_sheads(const uint64_t* __restrict__ ctl, const uint32_t* __restrict__ keys,
+                  const uint32_t* __restrict__ vals, const uint4* __restrict__ deliv, uint64_t pub_cap,
+                  uint32_t* __restrict__ head, uint32_t* __restrict__ thead) {
+    if (ctl[0]) return;
+    const uint64_t m = ctl[1];
+    if (m == 0) return;
+    for (uint64_t p = (uint64_t)blockIdx.x * FBLOCK + threadIdx.x; p < pub_cap; p += (uint64_t)gridDim.x * FBLOCK) {
+        uint32_t h = 0, th = 0;
+        if (p < m) {
+            h = th = 1;
+            if (p > 0) {
+                th = keys[p] != keys[p - 1];
+                h = th || deliv[vals[p]].x != deliv[vals[p - 1]].x;
+            }
+        }
+        head[p] = h;
+        thead[p] = th;
+    }
+}
+
+// tm_forward_groups bounded by the device m; H / T have pub_cap + 1 entries and
+// are constant from m on.  Lane 0 writes M, G, the targets and the state (4:
+// G > group_cap).
+__global__ void __launch_bounds__(FBLOCK)
+tm_forward_sgroups(const uint64_t* __restrict__ ctl, const uint32_t* __restrict__ keys,
+                   const uint32_t* __restrict__ vals, const uint4* __restrict__ deliv,
+                   const uint32_t* __restrict__ pubidx, const uint32_t* __restrict__ head,
+                   const uint64_t* __restrict__ H, const uint64_t* __restrict__ T, uint64_t* __restrict__ hdr,
+                   ForwardGroup* __restrict__ groups, uint64_t group_cap, uint32_t* __restrict__ pub) {
+    if (ctl[0]) return;
+    const uint32_t m = (uint32_t)ctl[1];
+    if (m == 0) return;
+    for (uint64_t q = (uint64_t)blockIdx.x * FBLOCK + threadIdx.x; q < m; q += (uint64_t)gridDim.x * FBLOCK) {
+        const uint32_t p = (uint32_t)q;
+        if (p == 0) {
+            const uint64_t G = H[m];
+            hdr[0] = m;
+            hdr[1] = G;
+            hdr[2] = T[m];
+            hdr[6] = G > group_cap ? 4ull : 0ull;
+        }
+        const uint32_t g = vals[p];
+        pub[p] = pubidx[g];   // m <= pub_cap (tm_forward_scheck)
+        if (!head[p]) continue;
+        const uint64_t gi = H[p];
+        if (gi >= group_cap) continue;
+        // the run's end, as in tm_forward_groups
+        uint32_t lo = p + 1, hi = m;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (H[mid + 1] > gi + 1) hi = mid;
+            else lo = mid + 1;
+        }
+        groups[gi] = ForwardGroup{keys[p], deliv[g].x, p, lo - p};
+    }
+}
+
+static inline uint32_t fstream_grid(uint64_t items) {
+    const uint64_t b = (items + FBLOCK - 1) / FBLOCK;
+    return (uint32_t)(b < 1 ? 1 : b > 1024 ? 1024 : b);
+}
+
+hipError_t launch_forward_stream_flag(const ForwardView& fv, uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff,
+                                      const void* deliv, uint64_t deliv_cap, uint32_t* flag, hipStream_t st) {
+    if (deliv_cap == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_forward_sflag, dim3(fstream_grid(deliv_cap)), dim3(FBLOCK), 0, st, fv, n, pub_hdr, doff,
+                       (const uint4*)deliv, deliv_cap, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_stream_check(const uint64_t* pub_hdr, const uint64_t* P, uint64_t deliv_cap,
+                                       uint64_t pub_cap, uint64_t* ctl, uint64_t* hdr, hipStream_t st) {
+    hipLaunchKernelGGL(tm_forward_scheck, dim3(1), dim3(64), 0, st, pub_hdr, P, deliv_cap, pub_cap, ctl, hdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_stream_emit(const ForwardView& fv, uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff,
+                                      const void* deliv, uint64_t deliv_cap, const uint32_t* flag, const uint64_t* P,
+                                      const uint64_t* ctl, uint64_t pub_cap, uint32_t* keys, uint32_t* vals,
+                                      uint32_t* pubidx, hipStream_t st) {
+    if (n == 0 || pub_cap == 0 || deliv_cap == 0) return hipSuccess;
+    // the grid of launch_publish_pack: `split` blocks per 256 topics for about four records a thread
+    const uint64_t nblk = ((uint64_t)n + FBLOCK - 1) / FBLOCK;
+    uint64_t split = (deliv_cap + nblk * 4 * FBLOCK - 1) / (nblk * 4 * FBLOCK);
+    split = split < 1 ? 1 : split > 64 ? 64 : split;
+    uint64_t grid = nblk * split;
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(tm_forward_semit, dim3((uint32_t)grid), dim3(FBLOCK), 0, st, fv.n_filters, n, pub_hdr, doff,
+                       (const uint4*)deliv, deliv_cap, flag, P, ctl, (uint32_t)split, pub_cap, keys, vals, pubidx);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_stream_retarget(const uint64_t* ctl, uint32_t* keys, const uint32_t* vals, const void* deliv,
+                                          uint64_t pub_cap, hipStream_t st) {
+    if (pub_cap == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_forward_sretarget, dim3(fstream_grid(pub_cap)), dim3(FBLOCK), 0, st, ctl, keys, vals,
+                       (const uint4*)deliv);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_stream_heads(const uint64_t* ctl, const uint32_t* keys, const uint32_t* vals,
+                                       const void* deliv, uint64_t pub_cap, uint32_t* head, uint32_t* thead,
+                                       hipStream_t st) {
+    if (pub_cap == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_forward_sheads, dim3(fstream_grid(pub_cap)), dim3(FBLOCK), 0, st, ctl, keys, vals,
+                       (const uint4*)deliv, pub_cap, head, thead);
+    return hipGetLastError();
+}
+
+hipError_t launch_forward_stream_groups(const uint64_t* ctl, const uint32_t* keys, const uint32_t* vals,
+                                        const void* deliv, const uint32_t* pubidx, const uint32_t* head,
+                                        const uint64_t* H, const uint64_t* T, uint64_t pub_cap, uint64_t* hdr,
+                                        void* groups, uint64_t group_cap, uint32_t* pub, hipStream_t st) {
+    if (pub_cap == 0) return hipSuccess;
+    hipLaunchKernelGGL(tm_forward_sgroups, dim3(fstream_grid(pub_cap)), dim3(FBLOCK), 0, st, ctl, keys, vals,
+                       (const uint4*)deliv, pubidx, head, H, T, hdr, (ForwardGroup*)groups, group_cap, pub);
+    return hipGetLastError();
+}
+
 }  // namespace tmx

@@ -303,6 +303,39 @@ hipError_t launch_forward_groups(const uint32_t* keys, const uint32_t* vals, con
                                  const uint32_t* pubidx, const uint32_t* head, const uint64_t* H, const uint64_t* T,
                                  uint32_t m, uint64_t* hdr, void* groups, uint64_t group_cap, uint32_t* pub,
                                  uint64_t pub_cap, hipStream_t st);
+// The same plan from the packed outputs of the stream-ordered publish call
+// (pub_hdr, doff, 16 B deliv records), enqueued only: ctl is 8 zeroed u64
+// ({state, m}), every kernel leaves when the state is set, bounds are device
+// words, grids come from n and the capacities.
+//   launch_forward_stream_flag      flag[deliv_cap]: record is a forward delivery
+//   launch_scan0                    P (deliv_cap + 1); P[deliv_cap] = M
+//   launch_forward_stream_check     the state (1 publish state, 3 M > pub_cap), ctl[1] = m,
+//                                   hdr[0], hdr[3..5], hdr[7]
+//   launch_forward_stream_emit      (To key, record) pairs in record order, pubidx of the
+//                                   flagged records, the padding keys 0xFFFFFFFF of [m, pub_cap)
+//   launch_sort_pairs               by To key over pub_cap, live = &ctl[1]
+//   launch_forward_stream_retarget  keys[p] = the record's target, p < m
+//   launch_sort_pairs               by target over pub_cap, live = &ctl[1]
+//   launch_forward_stream_heads     head / thead over pub_cap (0 from m on)
+//   launch_scan0 x 2                H, T (pub_cap + 1 u64 each)
+//   launch_forward_stream_groups    groups and pub; hdr[0..2], hdr[6] = 0 or 4 (G > group_cap)
+hipError_t launch_forward_stream_flag(const ForwardView& fv, uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff,
+                                      const void* deliv, uint64_t deliv_cap, uint32_t* flag, hipStream_t st);
+hipError_t launch_forward_stream_check(const uint64_t* pub_hdr, const uint64_t* P, uint64_t deliv_cap,
+                                       uint64_t pub_cap, uint64_t* ctl, uint64_t* hdr, hipStream_t st);
+hipError_t launch_forward_stream_emit(const ForwardView& fv, uint32_t n, const uint64_t* pub_hdr, const uint64_t* doff,
+                                      const void* deliv, uint64_t deliv_cap, const uint32_t* flag, const uint64_t* P,
+                                      const uint64_t* ctl, uint64_t pub_cap, uint32_t* keys, uint32_t* vals,
+                                      uint32_t* pubidx, hipStream_t st);
+hipError_t launch_forward_stream_retarget(const uint64_t* ctl, uint32_t* keys, const uint32_t* vals, const void* deliv,
+                                          uint64_t pub_cap, hipStream_t st);
+hipError_t launch_forward_stream_heads(const uint64_t* ctl, const uint32_t* keys, const uint32_t* vals,
+                                       const void* deliv, uint64_t pub_cap, uint32_t* head, uint32_t* thead,
+                                       hipStream_t st);
+hipError_t launch_forward_stream_groups(const uint64_t* ctl, const uint32_t* keys, const uint32_t* vals,
+                                        const void* deliv, const uint32_t* pubidx, const uint32_t* head,
+                                        const uint64_t* H, const uint64_t* T, uint64_t pub_cap, uint64_t* hdr,
+                                        void* groups, uint64_t group_cap, uint32_t* pub, hipStream_t st);
 
 // The local sends of a batch regrouped per receiving subscriber (inbox.hip),
 // over the pair planes of the local dispatch and the pick plane over the

@@ -733,6 +733,31 @@ class Engine:
                                              p(d_total), p(d_hdr), p(d_groups), group_cap, p(d_pub), pub_cap, st)
         return self._check(rc, "tm_forward_plan_device")
 
+    FORWARD_STREAM_HDR_WORDS = 8
+
+    def forward_plan_stream_workspace_bytes(self, n, deliv_cap, pub_cap):
+        """tm_forward_plan_stream_workspace_bytes (0: an argument out of range)"""
+        return int(self.lib.tm_forward_plan_stream_workspace_bytes(n, deliv_cap, pub_cap))
+
+    def forward_plan_stream_device(self, n, d_pub_hdr, d_doff, d_deliv, deliv_cap, d_workspace, workspace_bytes,
+                                   d_hdr, d_groups, group_cap, d_pub, pub_cap, stream=None):
+        """tm_forward_plan_stream_device over device pointers (tensors or ints;
+        None = NULL): the forward plan of the packed outputs
+        publish_stream[_opts]_device left, enqueued on `stream` without a host
+        wait.  d_hdr: 8 u64, [0..3] = {M, G, targets, 0}, [6] the state (0
+        complete, 1 the publish did not fit, 3 M > pub_cap, 4 G > group_cap)."""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        rc = self.lib.tm_forward_plan_stream_device(self.h, n, p(d_pub_hdr), p(d_doff), p(d_deliv), deliv_cap,
+                                                    p(d_workspace), workspace_bytes, p(d_hdr), p(d_groups), group_cap,
+                                                    p(d_pub), pub_cap, st)
+        return self._check(rc, "tm_forward_plan_stream_device")
+
     # -- the inbox plan: a batch's local sends per subscriber (inbox.hip) -----------
     INBOX_HDR_WORDS = 4
     INBOX_PICK = 0x80000000           # ent_pub bit 31: the entry is a pick send

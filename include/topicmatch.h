@@ -1032,6 +1032,75 @@ int tm_forward_plan(tm_engine* e, uint32_t n, const uint32_t* count, const uint6
                     uint64_t hdr[TM_FORWARD_HDR_WORDS], tm_forward_group* groups, uint64_t group_cap,
                     uint32_t* pub, uint64_t pub_cap);
 
+/* The plan, stream-ordered: the same forward deliveries, the same three sort
+ * keys, the same tm_forward_group records and pub entries, computed from the
+ * PACKED outputs of tm_publish_stream[_opts]_device (below) instead of the
+ * planes.  Between entry and return the call only enqueues work on hip_stream:
+ * no synchronisation, no read-back, no allocation; every intermediate lives in
+ * d_workspace.  With it (and tm_inbox_plan_stream_device) every outcome of
+ * publish/1 is ordered on one stream without a host wait.  The call may be run
+ * again over the same outputs and gives the same plan.
+ *   d_pub_hdr   the publish call's d_hdr[TM_PUBLISH_HDR_WORDS]: D = [2] and the
+ *               publish state [6] are read on the device
+ *   forward delivery   record d with d_doff[0] <= d < min(d_doff[n], D,
+ *               deliv_cap) whose target is below the image's target count, of
+ *               kind TM_TARGET_NODE and not the target of tm_set_local_node;
+ *               its publish index is the t with d_doff[t] <= d < d_doff[t+1].
+ *               Packed records have no holes, so no count[] is read.
+ * THE IMAGE.  Unlike the inbox plan this call reads the image: the target table
+ * (kind, and which target is node()) and the filter count of the epoch that is
+ * current when the call is made (it commits pending deltas and pins that epoch,
+ * as the publish call does, and records its use of it).  A tm_commit between
+ * the publish call and the plan does NOT change the plan: target ids are never
+ * reused and a target's kind never changes, so every record's flag is the
+ * same; and a newer filter count only moves the key TM_ROUTE_TOPIC sorts under,
+ * which still sorts after every filter id of the records.  A tm_set_local_node
+ * between the two calls DOES change it: the plan follows the node set when the
+ * plan is enqueued, as tm_forward_plan_device does.
+ * d_hdr[TM_FORWARD_STREAM_HDR_WORDS]:
+ *   [0..3] {M, G, distinct targets, 0} as tm_forward_plan
+ *   [4], [5], [7]  0
+ *   [6]    state, the first that applies:
+ *          0  complete: groups, pub and [0..3] are bit for bit what
+ *             tm_forward_plan_device writes for the equivalent planes (a dense
+ *             record is a slot without holes: count[t] = d_doff[t+1] -
+ *             d_doff[t], off = d_doff, out_cap = min(deliv_cap, D), *d_total = D)
+ *          1  the publish call's own state was not 0: nothing is computed,
+ *             [0..5] are 0 and nothing else is written
+ *          3  M > pub_cap: [0] exact, [1] = [2] = 0, no record and no entry
+ *             written
+ *          4  G > group_cap: the header exact, pub complete, exactly the first
+ *             group_cap records written
+ *          (2 is unused: the numbering is tm_inbox_plan_stream_device's)
+ * In every state nothing is written at or past group_cap records, pub_cap
+ * entries or workspace_bytes.  M <= min(D, deliv_cap), so pub_cap = group_cap =
+ * deliv_cap reaches neither state 3 nor state 4.
+ * The two stable sorts (by To key, then by target) run over pub_cap pairs, the
+ * m live ones padded with key 0xFFFFFFFF; their pass counts come from the
+ * image's filter and target counts, which the host knows when it enqueues.  The
+ * padding is staged last, its digits are all 255 and both sorts are stable, so
+ * it stays behind a live key whose sorted digits are all ones (the argument of
+ * tm_inbox_plan_stream_device); the retarget between the sorts is bounded by
+ * the device's m and leaves the padding keys as they are.  Every kernel tests a
+ * state word in the workspace first and leaves when it is set.  Launches for up
+ * to 32768 records and pairs: 10 + 3 per sort pass (16 with up to 255 filters
+ * and up to 256 targets).
+ * d_workspace: tm_forward_plan_stream_workspace_bytes(n, deliv_cap, pub_cap)
+ * bytes (a multiple of 256, non-decreasing in each argument, > 0 for all-zero
+ * arguments; 0 when out of range).
+ * n == 0: a zero header.  TM_EINVAL, before anything is enqueued: a null e,
+ * d_pub_hdr, d_doff, d_hdr or d_workspace; a null d_deliv, d_groups or d_pub
+ * with its capacity non-zero; workspace_bytes below the need; tm_set_local_node
+ * not called yet.  TM_ERANGE: a capacity at or above 2^32 - 2, or n at or above
+ * 2^31.  TM_EDEVICE on a host-only engine.  Runs on the replica that owns
+ * d_pub_hdr. */
+#define TM_FORWARD_STREAM_HDR_WORDS 8
+uint64_t tm_forward_plan_stream_workspace_bytes(uint32_t n, uint64_t deliv_cap, uint64_t pub_cap);
+int tm_forward_plan_stream_device(tm_engine* e, uint32_t n, const uint64_t* d_pub_hdr, const uint64_t* d_doff,
+                                  const tm_delivery* d_deliv, uint64_t deliv_cap, void* d_workspace,
+                                  uint64_t workspace_bytes, uint64_t* d_hdr, tm_forward_group* d_groups,
+                                  uint64_t group_cap, uint32_t* d_pub, uint64_t pub_cap, void* hip_stream);
+
 /* ---- the inbox plan: a batch's local sends, one bundle per subscriber ---------
  * (emqx_amd/csrc/inbox.hip)  dispatch/2 ends in SubPid ! {dispatch, Topic, Msg},
  * once per subscriber of every delivery (src/emqx_broker.erl:225-236), and
@@ -1485,6 +1554,26 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
  * reports; ent_cap = inbox_cap = caps.pairs + caps.routes, so the plan states 3
  * and 4 do not occur.  Plan reruns count in tm_batcher_stats.reruns. */
 #define TM_BATCHER_INBOX        1024u /* with TM_BATCHER_OPTS: one plan per batch, tm_batcher_open_inbox */
+/* TM_BATCHER_FORWARD (with TM_BATCHER_PUBLISH, through tm_batcher_open_plans
+ * only): the batch's remote-node deliveries reach the caller grouped per
+ * receiving node.  A lane runs the stream-ordered publish call whatever the
+ * strategy (keyed picks included, as TM_BATCHER_STREAM), then
+ * tm_inbox_plan_stream_device when TM_BATCHER_INBOX is set, then
+ * tm_forward_plan_stream_device, all on its stream with no wait between them,
+ * and reads the forward plan (header, groups, pub) back with the rest of the
+ * block: one copy and one wait for batches of up to 32768 topics, exact sizes
+ * after the headers for larger ones.  pub_cap = group_cap = caps.routes, so the
+ * plan states 3 and 4 do not occur.  Per batch, from the lane's thread: the
+ * tm_inbox_done_fn (if any), then the tm_forward_done_fn, once, then the
+ * per-publish callbacks, unchanged -- they keep carrying the TM_NOT_LOCAL
+ * records, which a publisher needs for its {route, Node, To} results.  The
+ * flag combines with TM_BATCHER_OPTS, TM_BATCHER_INBOX (which needs
+ * TM_BATCHER_OPTS as before), TM_BATCHER_ROUND_ROBIN, TM_BATCHER_STICKY,
+ * TM_BATCHER_UPGRADE_QOS and TM_BATCHER_EAGER.
+ * Reruns: a publish state other than 0 runs the whole chain again, as without
+ * the flag.  The forward plan never reruns alone, and a plan-only inbox rerun
+ * (inbox state 2) leaves the forward plan as it is. */
+#define TM_BATCHER_FORWARD      2048u /* with TM_BATCHER_PUBLISH: one forward plan per batch, tm_batcher_open_plans */
 
 typedef struct tm_batcher tm_batcher;
 typedef struct tm_batcher_config {
@@ -1561,6 +1650,25 @@ typedef void (*tm_inbox_done_fn)(void* ctx, int status, uint32_t n_pub, const ui
                                  uint32_t n_ent);
 int  tm_batcher_open_inbox(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn fn, void* ctx,
                            tm_batcher** out);
+/* TM_BATCHER_FORWARD: the forward plan of one batch (tm_forward_plan: hdr {M,
+ * G, distinct targets, 0}, groups[n_groups = G], pub[n_fwd = M]), valid during
+ * the call.  tickets[n_pub] are the batch's tickets in submission order, and
+ * pub[p] indexes them.  A failed batch (and a host-only engine: TM_EDEVICE)
+ * calls it with the status, every array NULL and every count 0, and then the
+ * batch's per-publish callbacks with the same status.
+ * tm_batcher_open_plans opens a batcher with either plan or both: forward_fn is
+ * non-NULL exactly when TM_BATCHER_FORWARD is set (which needs
+ * TM_BATCHER_PUBLISH), inbox_fn exactly when TM_BATCHER_INBOX is set (which
+ * needs TM_BATCHER_PUBLISH | TM_BATCHER_OPTS), at least one of the two flags is
+ * set and cfg is non-NULL; anything else is TM_EINVAL.  Both callbacks get ctx.
+ * tm_batcher_open and tm_batcher_open_inbox with TM_BATCHER_FORWARD set:
+ * TM_EINVAL.  Submits go through tm_batcher_submit_publish, or
+ * tm_batcher_submit_publish_opts with TM_BATCHER_OPTS. */
+typedef void (*tm_forward_done_fn)(void* ctx, int status, uint32_t n_pub, const uint64_t* tickets,
+                                   const uint64_t hdr[TM_FORWARD_HDR_WORDS], const tm_forward_group* groups,
+                                   uint32_t n_groups, const uint32_t* pub, uint32_t n_fwd);
+int  tm_batcher_open_plans(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn inbox_fn,
+                           tm_forward_done_fn forward_fn, void* ctx, tm_batcher** out);
 /* seal the open batch and wait until every submitted topic has completed */
 int  tm_batcher_flush(tm_batcher* b);
 /* the counters up to sync_ns (TM_BATCHER_STATS_V1_BYTES bytes; max_* untouched) */

@@ -8,7 +8,10 @@
 // head); a close with requests in flight; the flag combinations
 // tm_batcher_open refuses; tm_publish_pack_device's argument checks; the inbox
 // mode (tm_batcher_open_inbox: per batch the batch callback with TM_EDEVICE,
-// null arrays and zero counts, then that batch's per-publish callbacks) and the flag combinations its two open calls refuse.  Build
+// null arrays and zero counts, then that batch's per-publish callbacks) and the flag combinations its two open calls refuse;
+// the forward mode (tm_batcher_open_plans: the open-call rules of all three
+// open calls, and per batch the inbox callback if any, the forward callback,
+// then the per-publish callbacks, each with TM_EDEVICE and no arrays).  Build
 // and run: make san_batcher (host code under -fsanitize=address,undefined; the
 // kernels are linked as built, never run).
 #include <atomic>
@@ -115,6 +118,124 @@ static void inbox_phase() {
                 (unsigned long long)st.batches);
 }
 
+// the forward mode on one lane (tm_batcher_open_plans): per batch the inbox
+// callback (when the batcher has one), then the forward callback, then that
+// batch's 1 .. max_topics publishes
+struct PlansTally {
+    std::atomic<uint64_t> bad{0}, inboxes{0}, forwards{0}, pubs{0};
+    bool with_inbox = false;
+    int last = 2;         // 0 an inbox callback, 1 a forward callback, 2 a publish (one lane: no lock)
+    uint64_t since = 0;   // publishes completed since the last forward callback
+};
+static void on_plans_inbox(void* ctx, int status, uint32_t n_pub, const uint64_t* tickets, const uint64_t* hdr,
+                           const tm_inbox* inbox, uint32_t n_inbox, const uint32_t* ent_pub, const uint32_t* ent_to,
+                           const uint32_t* ent_word, uint32_t n_ent) {
+    PlansTally* t = static_cast<PlansTally*>(ctx);
+    if (status != TM_EDEVICE || n_pub || tickets || hdr || inbox || n_inbox || ent_pub || ent_to || ent_word || n_ent ||
+        !t->with_inbox || t->last != 2 || (t->forwards.load() && !t->since))
+        t->bad.fetch_add(1, std::memory_order_relaxed);
+    t->last = 0;
+    t->inboxes.fetch_add(1, std::memory_order_relaxed);
+}
+static void on_plans_forward(void* ctx, int status, uint32_t n_pub, const uint64_t* tickets, const uint64_t* hdr,
+                             const tm_forward_group* groups, uint32_t n_groups, const uint32_t* pub, uint32_t n_fwd) {
+    PlansTally* t = static_cast<PlansTally*>(ctx);
+    if (status != TM_EDEVICE || n_pub || tickets || hdr || groups || n_groups || pub || n_fwd ||
+        t->last != (t->with_inbox ? 0 : 2) || (t->forwards.load() && !t->since))
+        t->bad.fetch_add(1, std::memory_order_relaxed);
+    t->last = 1;
+    t->since = 0;
+    t->forwards.fetch_add(1, std::memory_order_relaxed);
+}
+static void plans_publish_done(PlansTally* t, bool clean) {
+    if (!clean || t->last == 0 || !t->forwards.load() || ++t->since > 64) t->bad.fetch_add(1, std::memory_order_relaxed);
+    t->last = 2;
+    t->pubs.fetch_add(1, std::memory_order_relaxed);
+}
+static void on_plans_publish(void* ctx, uint64_t, int status, const tm_delivery* deliv, uint32_t n_deliv,
+                             const tm_pair* pairs, uint32_t n_pairs) {
+    plans_publish_done(static_cast<PlansTally*>(ctx), status == TM_EDEVICE && !deliv && !n_deliv && !pairs && !n_pairs);
+}
+static void on_plans_publish_opts(void* ctx, uint64_t, int status, const tm_delivery* deliv, const uint32_t* pick_word,
+                                  uint32_t n_deliv, const tm_pair* pairs, const uint32_t* pair_word, uint32_t n_pairs) {
+    plans_publish_done(static_cast<PlansTally*>(ctx), status == TM_EDEVICE && !deliv && !pick_word && !n_deliv &&
+                                                          !pairs && !pair_word && !n_pairs);
+}
+static void forward_run(bool with_inbox) {
+    const uint32_t P = TM_BATCHER_PUBLISH, O = TM_BATCHER_OPTS, I = TM_BATCHER_INBOX, F = TM_BATCHER_FORWARD;
+    tm_batcher_config cfg{};
+    cfg.max_topics = 64;
+    cfg.deadline_us = 50;
+    cfg.lanes_per_replica = 1;
+    cfg.flags = with_inbox ? (P | O | I | F | TM_BATCHER_STICKY | TM_BATCHER_UPGRADE_QOS | TM_BATCHER_EAGER)
+                           : (P | F | TM_BATCHER_ROUND_ROBIN);
+    PlansTally tally;
+    tally.with_inbox = with_inbox;
+    tm_batcher* b = nullptr;
+    expect(tm_batcher_open_plans(E, &cfg, with_inbox ? on_plans_inbox : nullptr, on_plans_forward, &tally, &b) ==
+                   TM_OK && b,
+           "tm_batcher_open_plans");
+    const int threads = 3;
+    const uint32_t per = 4000;
+    std::vector<std::thread> th;
+    for (int k = 0; k < threads; ++k)
+        th.emplace_back([&, k] {
+            for (uint32_t i = 0; i < per; ++i) {
+                const std::string t = "r/" + std::to_string(k) + "/" + std::to_string(i);
+                const uint8_t* p = reinterpret_cast<const uint8_t*>(t.data());
+                const int rc = with_inbox ? tm_batcher_submit_publish_opts(b, p, (uint32_t)t.size(), i, i % 3,
+                                                                           TM_NO_SUBSCRIBER, on_plans_publish_opts,
+                                                                           &tally, nullptr)
+                                          : tm_batcher_submit_publish(b, p, (uint32_t)t.size(), i, on_plans_publish,
+                                                                      &tally, nullptr);
+                if (rc != TM_OK) tally.bad.fetch_add(1, std::memory_order_relaxed);
+            }
+        });
+    for (auto& t : th) t.join();
+    expect(tm_batcher_flush(b) == TM_OK, "tm_batcher_flush");
+    tm_batcher_stats st{};
+    expect(tm_batcher_get_stats2(b, &st, sizeof(st), 0) == TM_OK, "tm_batcher_get_stats2");
+    tm_batcher_close(b);
+    expect(st.topics == (uint64_t)threads * per && st.failed_batches == st.batches, "forward stats");
+    expect(tally.forwards.load() == st.batches && tally.inboxes.load() == (with_inbox ? st.batches : 0) &&
+               tally.pubs.load() == st.topics && tally.since > 0,
+           "one forward callback per batch, behind the inbox callback and before the publishes");
+    expect(tally.bad.load() == 0, "every plan callback carries TM_EDEVICE and no arrays, in order");
+    std::printf("%-28s ok: %llu submits, %llu batches\n", with_inbox ? "inbox + forward mode" : "forward mode",
+                (unsigned long long)st.topics, (unsigned long long)st.batches);
+}
+static void forward_phase() {
+    const uint32_t P = TM_BATCHER_PUBLISH, O = TM_BATCHER_OPTS, I = TM_BATCHER_INBOX, F = TM_BATCHER_FORWARD;
+    tm_batcher_config cfg{};
+    cfg.max_topics = 64;
+    cfg.lanes_per_replica = 1;
+    PlansTally tally;
+    tm_batcher* b = nullptr;
+    auto plans = [&](uint32_t flags, tm_inbox_done_fn ifn, tm_forward_done_fn ffn) {
+        cfg.flags = flags;
+        return tm_batcher_open_plans(E, &cfg, ifn, ffn, &tally, &b);
+    };
+    cfg.flags = P | F;
+    expect(tm_batcher_open(E, &cfg, &b) == TM_EINVAL && !b, "tm_batcher_open with TM_BATCHER_FORWARD");
+    cfg.flags = P | O | I | F;
+    expect(tm_batcher_open_inbox(E, &cfg, on_plans_inbox, &tally, &b) == TM_EINVAL && !b,
+           "tm_batcher_open_inbox with TM_BATCHER_FORWARD");
+    expect(tm_batcher_open_plans(E, nullptr, nullptr, on_plans_forward, &tally, &b) == TM_EINVAL && !b,
+           "open_plans: null cfg");
+    expect(plans(P | F, nullptr, nullptr) == TM_EINVAL && !b, "open_plans: the flag without its callback");
+    expect(plans(P, nullptr, on_plans_forward) == TM_EINVAL && !b, "open_plans: the callback without its flag");
+    expect(plans(P | F, on_plans_inbox, on_plans_forward) == TM_EINVAL && !b, "open_plans: inbox fn without its flag");
+    expect(plans(P | O | I | F, nullptr, on_plans_forward) == TM_EINVAL && !b, "open_plans: inbox flag without its fn");
+    expect(plans(P | O, nullptr, nullptr) == TM_EINVAL && !b, "open_plans: neither flag");
+    expect(plans(F, nullptr, on_plans_forward) == TM_EINVAL && !b, "open_plans: without TM_BATCHER_PUBLISH");
+    expect(plans(P | I | F, on_plans_inbox, on_plans_forward) == TM_EINVAL && !b, "open_plans: INBOX without OPTS");
+    expect(plans(P | O | I, on_plans_inbox, nullptr) == TM_OK && b, "open_plans: the inbox plan alone");
+    tm_batcher_close(b);
+    b = nullptr;
+    forward_run(false);
+    forward_run(true);
+}
+
 // `threads` producers submit `per` topics each; close_early: tm_batcher_close
 // with requests in flight instead of a flush (close completes them all)
 static void flood(const char* name, tm_batcher_config cfg, int threads, uint32_t per, bool close_early) {
@@ -218,6 +339,7 @@ int main() {
         std::printf("%-28s ok\n", "pack argument checks");
     }
     inbox_phase();
+    forward_phase();
     tm_close(E);
     std::printf("san_batcher: all phases ok\n");
     return 0;
