@@ -35,7 +35,7 @@ $(BUILD)/exchange.o: emqx_amd/csrc/exchange.cpp emqx_amd/csrc/kernels.h include/
 $(BUILD)/batcher.o: emqx_amd/csrc/batcher.cpp include/topicmatch.h | $(BUILD)
 	$(HIPCC) -O2 -fPIC -std=c++17 -Wall -pthread -c $< -o $@
 
-LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/forward.o $(BUILD)/inbox.o $(BUILD)/pack.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
+LIBOBJS = $(BUILD)/kernels.o $(BUILD)/shard.o $(BUILD)/route.o $(BUILD)/routes.o $(BUILD)/presort.o $(BUILD)/aggre.o $(BUILD)/dispatch.o $(BUILD)/share.o $(BUILD)/forward.o $(BUILD)/inbox.o $(BUILD)/pack.o $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/acl.o $(BUILD)/admit.o $(BUILD)/rewrite.o $(BUILD)/exchange.o
 $(LIBOUT): $(LIBOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -pthread $^ -L/opt/rocm/lib -lrccl -o $@
 
@@ -139,3 +139,18 @@ san_pickwords: $(LIBOUT)
 	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_pickwords_main.o $(BUILD)/san_engine.o $(SAN_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_pickwords
 	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_pickwords
 .PHONY: san_pickwords
+
+# the micro-batcher's admission mode (TM_BATCHER_ADMIT: the open and submit
+# checks, the credential records through threaded submits, partial takes,
+# both plans and a close with requests in flight) and the host admission
+# forms of admit.hip, under AddressSanitizer + UBSan on a host-only engine
+# (tools/san_admit.cpp); the kernels linked as built and never run.
+SAN_ADMIT_OBJS = $(filter-out $(BUILD)/engine.o $(BUILD)/batcher.o $(BUILD)/admit.o,$(filter %.o,$(LIBOBJS)))
+san_admit: $(LIBOUT)
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer $(TMDEFS) -c emqx_amd/csrc/engine.cpp -o $(BUILD)/san_engine.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -pthread -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c emqx_amd/csrc/batcher.cpp -o $(BUILD)/san_batcher_lib.o
+	$(HIPCC) --offload-arch=$(ARCH) -O1 -g -fPIC -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c emqx_amd/csrc/admit.hip -o $(BUILD)/san_admit_lib.o
+	$(HIPCC) -O1 -g -fPIC -std=c++17 -pthread -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -c tools/san_admit.cpp -o $(BUILD)/san_admit_main.o
+	$(HIPCC) --offload-arch=$(ARCH) $(SAN) $(BUILD)/san_admit_main.o $(BUILD)/san_engine.o $(BUILD)/san_batcher_lib.o $(BUILD)/san_admit_lib.o $(SAN_ADMIT_OBJS) -pthread -L/opt/rocm/lib -lrccl -o $(BUILD)/san_admit
+	LSAN_OPTIONS=suppressions=tools/san_share.supp $(BUILD)/san_admit
+.PHONY: san_admit

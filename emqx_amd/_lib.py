@@ -52,11 +52,32 @@ class TmBatcherStats(ctypes.Structure):
                                                "reruns")]
 
 
+class TmBatcherStatsAdmit(ctypes.Structure):
+    """tm_batcher_stats as the header has it now: TmBatcherStats (the layout up
+    to `reruns`, which callers built before the admission mode keep passing:
+    tm_batcher_get_stats2 writes no more than out_size) plus the trailing `refused`"""
+    _fields_ = TmBatcherStats._fields_ + [("refused", ctypes.c_uint64)]
+
+
 class TmPublishCaps(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint64) for k in ("ids", "routes", "pairs", "rr")]
 
 
 TM_PUBLISH_HDR_WORDS = 8
+
+
+class TmZoneCaps(ctypes.Structure):
+    """tm_zone_caps: one zone's publish caps and ACL switches (8 bytes)"""
+    _fields_ = [("max_qos_allowed", ctypes.c_uint8), ("retain_available", ctypes.c_uint8),
+                ("enable_acl", ctypes.c_uint8), ("acl_nomatch_allow", ctypes.c_uint8),
+                ("max_topic_alias", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+TM_ADMIT_MAX_ZONES = 256
+TM_ADMIT_OK, TM_ADMIT_TOPIC_NAME, TM_ADMIT_QOS, TM_ADMIT_TOPIC_ALIAS, TM_ADMIT_RETAIN, TM_ADMIT_ACL = range(6)
+TM_ADMIT_SUPER = 0x100
+TM_ADMIT_BAD_ARG = 0xFFFFFFFF   # tm_admit_code: a NULL zone or a QoS of 3
+TM_ADMIT_ALIAS_SHIFT = 16
 
 
 class TmExchangeIn(ctypes.Structure):
@@ -123,6 +144,7 @@ TM_BATCHER_OPTS = 256
 TM_BATCHER_UPGRADE_QOS = 512
 TM_BATCHER_INBOX = 1024
 TM_BATCHER_FORWARD = 2048
+TM_BATCHER_ADMIT = 4096
 TM_BATCHER_STATS_RESET_MAX = 1
 DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, c_u32p, c_u32p, ctypes.c_uint32)
 
@@ -141,6 +163,25 @@ PUBLISH_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctype
 PUBLISH_OPTS_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                         ctypes.POINTER(TmDelivery), c_u32p, ctypes.c_uint32, ctypes.POINTER(TmPair),
                                         c_u32p, ctypes.c_uint32)
+# tm_publish_admit_done_fn: the options callback's arguments plus admit_code and acl_rule
+PUBLISH_ADMIT_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                         ctypes.POINTER(TmDelivery), c_u32p, ctypes.c_uint32, ctypes.POINTER(TmPair),
+                                         c_u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32)
+
+
+class TmAdmitConfig(ctypes.Structure):
+    """tm_admit_config: the zone table and one tm_acl* per replica (NULL / 0: no rule set)"""
+    _fields_ = [("zones", ctypes.POINTER(TmZoneCaps)), ("n_zones", ctypes.c_uint32), ("n_acl", ctypes.c_uint32),
+                ("acl", ctypes.POINTER(ctypes.c_void_p))]
+
+
+class TmPubCreds(ctypes.Structure):
+    """tm_pub_creds: one publish's credentials as tm_acl_check_batch takes them per check"""
+    _fields_ = [("client_id", ctypes.c_char_p), ("username", ctypes.c_char_p), ("client_len", ctypes.c_uint32),
+                ("user_len", ctypes.c_uint32), ("client_defined", ctypes.c_uint8), ("user_defined", ctypes.c_uint8),
+                ("peer_family", ctypes.c_uint8), ("reserved", ctypes.c_uint8), ("peer", ctypes.c_uint8 * 16)]
+
+
 # tm_inbox_done_fn: (ctx, status, n_pub, tickets, hdr, inbox (16 B records as u32), n_inbox, ent_pub, ent_to,
 # ent_word, n_ent)
 INBOX_DONE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, c_u64p, c_u64p, c_u32p,
@@ -426,6 +467,22 @@ SIGNATURES = [
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_void_p, ctypes.POINTER(TmDeliver), ctypes.c_void_p,
                                                      ctypes.c_void_p]),
+    ("tm_publish_stream_gated_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TmPublishCaps),
+                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.POINTER(TmDeliver), ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_admit_code", ctypes.c_uint32, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.POINTER(TmZoneCaps), ctypes.c_int]),
+    ("tm_admit_batch", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TmZoneCaps), ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tm_admit_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(TmZoneCaps),
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     ("tm_publish_pack_opts_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -449,9 +506,17 @@ SIGNATURES = [
     ("tm_batcher_submit_publish_opts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                       PUBLISH_OPTS_DONE_FN, ctypes.c_void_p, c_u64p]),
+    ("tm_batcher_open_admit", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherConfig),
+                                             ctypes.POINTER(TmAdmitConfig), INBOX_DONE_FN, FORWARD_DONE_FN,
+                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("tm_batcher_submit_publish_admit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32,
+                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(TmPubCreds),
+                                                       PUBLISH_ADMIT_DONE_FN, ctypes.c_void_p, c_u64p]),
     ("tm_batcher_flush", ctypes.c_int, [ctypes.c_void_p]),
     ("tm_batcher_get_stats", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats)]),
-    ("tm_batcher_get_stats2", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TmBatcherStats), ctypes.c_uint32,
+    # (either layout of the struct: out_size says which)
+    ("tm_batcher_get_stats2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                              ctypes.c_uint32]),
     ("tm_batcher_close", None, [ctypes.c_void_p]),
     ("tm_acl_open", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),

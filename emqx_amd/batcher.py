@@ -17,7 +17,12 @@ batch's local sends grouped per receiving session before the per-publish
 callbacks run, which then carry no pairs; forward=callable (with publish=True;
 tm_batcher_open_plans, combines with inbox=) likewise hands over the batch's
 remote-node deliveries grouped per (node, To), after the inbox callback and
-before the per-publish callbacks, which are unchanged.  This is the NIF's path: the callback there builds
+before the per-publish callbacks, which are unchanged; admit=(zones, acl)
+(with publish=True, opts=True; tm_batcher_open_admit, combines with all of the
+above) puts the admission stage in front: submit_publish_admit carries the
+publish's mount length, admission word and credentials, a lane runs the ACL
+check, the admission and the gated publish call on its stream, and every
+callback ends with the publish's admission code and ACL rule index.  This is the NIF's path: the callback there builds
 the Erlang list and enif_send()s it to the waiting process."""
 import ctypes
 import itertools
@@ -30,7 +35,7 @@ from . import _lib as L
 class Batcher:
     def __init__(self, engine, max_topics=65536, deadline_us=200, max_bytes=0, routes=False, deliveries=False,
                  lanes_per_replica=0, callback_threads=0, publish=False, eager=False, flags=0, round_robin=False,
-                 stream=False, sticky=False, opts=False, upgrade_qos=False, inbox=None, forward=None):
+                 stream=False, sticky=False, opts=False, upgrade_qos=False, inbox=None, forward=None, admit=None):
         self.engine = engine
         self.lib = engine.lib
         flags |= (L.TM_BATCHER_ROUTES if routes else 0) | (L.TM_BATCHER_DELIVERIES if deliveries else 0) | \
@@ -38,12 +43,28 @@ class Batcher:
             (L.TM_BATCHER_ROUND_ROBIN if round_robin else 0) | (L.TM_BATCHER_STREAM if stream else 0) | \
             (L.TM_BATCHER_STICKY if sticky else 0) | (L.TM_BATCHER_OPTS if opts else 0) | \
             (L.TM_BATCHER_UPGRADE_QOS if upgrade_qos else 0) | (L.TM_BATCHER_INBOX if inbox is not None else 0) | \
-            (L.TM_BATCHER_FORWARD if forward is not None else 0)
+            (L.TM_BATCHER_FORWARD if forward is not None else 0) | (L.TM_BATCHER_ADMIT if admit is not None else 0)
         cfg = L.TmBatcherConfig(max_topics, deadline_us, max_bytes, flags, lanes_per_replica, callback_threads)
         h = ctypes.c_void_p()
         self.inbox = inbox
         self.forward = forward
-        if forward is not None:
+        self.admit = admit
+        if admit is not None:
+            # admit = (Zones, acl): acl None, one AclRules, or one per replica; kept alive with the batcher
+            what = "tm_batcher_open_admit"
+            zones, acl = admit
+            self._ztab, nz = zones.table()
+            acls = [] if acl is None else list(acl) if isinstance(acl, (list, tuple)) else [acl]
+            self._acls = acls
+            self._aclv = (ctypes.c_void_p * max(len(acls), 1))(*[a.h for a in acls])
+            ac = L.TmAdmitConfig(self._ztab, nz, len(acls), self._aclv if acls else None)
+            self._idone = L.INBOX_DONE_FN(self._on_inbox_done) if inbox is not None else \
+                ctypes.cast(None, L.INBOX_DONE_FN)
+            self._fdone = L.FORWARD_DONE_FN(self._on_forward_done) if forward is not None else \
+                ctypes.cast(None, L.FORWARD_DONE_FN)
+            rc = self.lib.tm_batcher_open_admit(engine.h, ctypes.byref(cfg), ctypes.byref(ac), self._idone,
+                                                self._fdone, None, ctypes.byref(h))
+        elif forward is not None:
             what = "tm_batcher_open_plans"
             self._idone = L.INBOX_DONE_FN(self._on_inbox_done) if inbox is not None else \
                 ctypes.cast(None, L.INBOX_DONE_FN)
@@ -66,6 +87,7 @@ class Batcher:
         self._done = L.DONE_FN(self._on_done)     # one trampoline, kept alive with the batcher
         self._pdone = L.PUBLISH_DONE_FN(self._on_publish_done)
         self._odone = L.PUBLISH_OPTS_DONE_FN(self._on_publish_opts_done)
+        self._adone = L.PUBLISH_ADMIT_DONE_FN(self._on_publish_admit_done)
 
     def _on_done(self, ctx, ticket, status, ids, dests, n):
         cb = self._cbs.pop(ctx)
@@ -186,6 +208,49 @@ class Batcher:
             raise L.TopicMatchError(rc, "tm_batcher_submit_publish_opts")
         return t.value
 
+    def _on_publish_admit_done(self, ctx, ticket, status, deliv, pick_word, n_deliv, pairs, pair_word, n_pairs,
+                               admit_code, acl_rule):
+        user = self._cbs[ctx]
+        rule = None if acl_rule == 0xFFFFFFFF else acl_rule
+        self._cbs[ctx] = lambda st, *rest: user(st, *rest, admit_code, rule)
+        self._on_publish_opts_done(ctx, ticket, status, deliv, pick_word, n_deliv, pairs, pair_word, n_pairs)
+
+    @staticmethod
+    def creds(c):
+        """a credentials dict as emqx_access.AclRules takes it (client_id,
+        username: str / bytes / None = undefined; peername: (ip text, port) or
+        None) -> tm_pub_creds"""
+        import ipaddress
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)   # noqa: E731
+        cid, usr, peer = c.get("client_id"), c.get("username"), c.get("peername")
+        cb, ub = b(cid or b""), b(usr or b"")
+        out = L.TmPubCreds(cb, ub, len(cb), len(ub), cid is not None, usr is not None, 0, 0)
+        if peer:
+            ip = ipaddress.ip_address(peer[0])
+            out.peer_family = 4 if ip.version == 4 else 6
+            out.peer[:len(ip.packed)] = list(ip.packed)
+        return out
+
+    def submit_publish_admit(self, topic: bytes, mount_len: int, key: int, pub_flags: int, pub_admit: int,
+                             pub_from: int, creds, callback):
+        """admit= batchers: topic = MountPoint ++ T, mount_len the mountpoint's
+        length, pub_admit the admission word (emqx_access.pub_admit), creds a
+        credentials dict or a TmPubCreds.  callback(status, deliveries,
+        pick_words, pairs, pair_words, admit_code, acl_rule) as
+        submit_publish_opts' (an inbox batcher: None, n_pairs for the pairs);
+        a refused publish gets empty lists and its code"""
+        t = ctypes.c_uint64()
+        k = next(self._keys)
+        self._cbs[k] = callback
+        cr = creds if isinstance(creds, L.TmPubCreds) else self.creds(creds)
+        rc = self.lib.tm_batcher_submit_publish_admit(self.h, topic, len(topic), mount_len, key & 0xFFFFFFFF, pub_flags,
+                                                      pub_admit, pub_from & 0xFFFFFFFF, ctypes.byref(cr), self._adone,
+                                                      k, ctypes.byref(t))
+        if rc != L.TM_OK:
+            del self._cbs[k]
+            raise L.TopicMatchError(rc, "tm_batcher_submit_publish_admit")
+        return t.value
+
     def flush(self):
         rc = self.lib.tm_batcher_flush(self.h)
         if rc != L.TM_OK:
@@ -194,7 +259,7 @@ class Batcher:
     def stats(self, reset_max=False):
         """tm_batcher_get_stats2: every counter; the max_* fields cover the
         batches since the open or the last read with reset_max=True"""
-        s = L.TmBatcherStats()
+        s = L.TmBatcherStatsAdmit()
         rc = self.lib.tm_batcher_get_stats2(self.h, ctypes.byref(s), ctypes.sizeof(s),
                                             L.TM_BATCHER_STATS_RESET_MAX if reset_max else 0)
         if rc != L.TM_OK:

@@ -92,6 +92,7 @@ struct Req {
         tm_batch_done_fn fn;
         tm_publish_done_fn pfn;   // TM_BATCHER_PUBLISH
         tm_publish_opts_done_fn ofn;   // TM_BATCHER_OPTS
+        tm_publish_admit_done_fn afn;  // TM_BATCHER_ADMIT
     };
     void* ctx;
     uint64_t ticket;
@@ -105,7 +106,11 @@ struct Chunk {
     std::vector<Req> reqs;
     std::vector<uint32_t> keys;   // TM_BATCHER_PUBLISH: the pick key of each topic (else empty)
     std::vector<uint32_t> pflags, pfrom;   // TM_BATCHER_OPTS: pub_flags and pub_from of each topic (else empty)
-    size_t head = 0, bhead = 0;   // topics / bytes already taken
+    // TM_BATCHER_ADMIT: each publish's mount length and admission word, and its credentials as
+    // one record of cred: CredHead, the client id's bytes, the username's bytes (crlen: the record's size)
+    std::vector<uint32_t> mlen, padmit, crlen;
+    std::vector<uint8_t> cred;
+    size_t head = 0, bhead = 0, chead = 0;   // topics / bytes / credential bytes already taken
     size_t size() const { return lens.size() - head; }
     size_t nbytes() const { return bytes.size() - bhead; }
     void reset() {
@@ -115,7 +120,11 @@ struct Chunk {
         keys.clear();
         pflags.clear();
         pfrom.clear();
-        head = bhead = 0;
+        mlen.clear();
+        padmit.clear();
+        crlen.clear();
+        cred.clear();
+        head = bhead = chead = 0;
     }
     void compact() {   // drop the taken prefix once it is the larger part
         if (head == 0 || head < lens.size() / 2) return;
@@ -127,9 +136,23 @@ struct Chunk {
             pflags.erase(pflags.begin(), pflags.begin() + head);
             pfrom.erase(pfrom.begin(), pfrom.begin() + head);
         }
-        head = bhead = 0;
+        if (!mlen.empty()) {
+            mlen.erase(mlen.begin(), mlen.begin() + head);
+            padmit.erase(padmit.begin(), padmit.begin() + head);
+            crlen.erase(crlen.begin(), crlen.begin() + head);
+            cred.erase(cred.begin(), cred.begin() + chead);
+        }
+        head = bhead = chead = 0;
     }
 };
+
+// the fixed part of a publish's credential record (Chunk::cred)
+struct CredHead {
+    uint32_t client_len, user_len;
+    uint8_t client_defined, user_defined, peer_family, reserved;
+    uint8_t peer[16];
+};
+static_assert(sizeof(CredHead) == 28, "CredHead is packed by hand");
 
 // A producer thread appends to its own stripe; everything a submit touches
 // lives in the stripe's cache lines (no shared counter is written per
@@ -243,6 +266,16 @@ struct Lane {
     const uint64_t* r_fhdr = nullptr;
     const tm_forward_group* r_fgroups = nullptr;
     const uint32_t* r_fpub = nullptr;
+    // TM_BATCHER_ADMIT: the lane's rule set (its replica's; null: none), where the admission planes sit in
+    // the block that goes up (offsets into h_io / d_io; a_utoff = 0: no publish has a mountpoint, the ACL
+    // kernel reads the topics themselves) and the codes and rule indices as the callbacks read them
+    tm_acl* acl = nullptr;
+    struct AdmitUp {
+        uint64_t mlen, padmit, coff, uoff, access, cdef, udef, fam, peers, cbytes, ubytes, utoff, utbytes, end;
+    } a_up{};
+    const uint64_t* r_ahdr = nullptr;
+    const uint32_t* r_rule = nullptr;
+    const uint8_t* r_code = nullptr;
     clk::time_point sealed;           // when the batch was handed over
     uint64_t launch_ns = 0, sync_ns = 0;   // this batch: host time enqueueing the device work, waiting on it
 };
@@ -270,6 +303,8 @@ struct tm_batcher {
     void* ictx = nullptr;
     bool forward = false;   // TM_BATCHER_FORWARD: the forward plan per batch through ffn (ctx: ictx)
     tm_forward_done_fn ffn = nullptr;
+    bool admit = false;     // TM_BATCHER_ADMIT: ACL check, admission and the gated call (tm_batcher_open_admit)
+    std::vector<tm_zone_caps> zones;
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -317,6 +352,12 @@ struct tm_batcher {
             if (cfg.flags & TM_BATCHER_OPTS) {
                 c.pflags.reserve(k);
                 c.pfrom.reserve(k);
+            }
+            if (cfg.flags & TM_BATCHER_ADMIT) {
+                c.mlen.reserve(k);
+                c.padmit.reserve(k);
+                c.crlen.reserve(k);
+                c.cred.reserve(k * 64);
             }
             c.bytes.reserve(k * 64);
             return c;
@@ -400,6 +441,16 @@ struct tm_batcher {
                 if (!x.cur.pflags.empty()) {
                     c.pflags.assign(x.cur.pflags.begin() + h, x.cur.pflags.begin() + h + k);
                     c.pfrom.assign(x.cur.pfrom.begin() + h, x.cur.pfrom.begin() + h + k);
+                }
+                if (!x.cur.mlen.empty()) {
+                    c.mlen.assign(x.cur.mlen.begin() + h, x.cur.mlen.begin() + h + k);
+                    c.padmit.assign(x.cur.padmit.begin() + h, x.cur.padmit.begin() + h + k);
+                    c.crlen.assign(x.cur.crlen.begin() + h, x.cur.crlen.begin() + h + k);
+                    size_t cb = 0;
+                    for (size_t j = 0; j < k; ++j) cb += x.cur.crlen[h + j];
+                    const uint8_t* c0 = x.cur.cred.data() + x.cur.chead;
+                    c.cred.assign(c0, c0 + cb);
+                    x.cur.chead += cb;
                 }
                 x.cur.head += k;
                 x.cur.bhead += kb;
@@ -582,7 +633,8 @@ struct tm_batcher {
         uint64_t nb = 0;
         for (const Chunk& c : L.chunks) nb += c.nbytes();
         const uint64_t offb = ((uint64_t)L.n + 1) * 8, keyb = keyb_of(L.n), upb = upb_of(L.n);
-        if (!L.h_io.ensure(offb + upb + nb + 16)) return false;
+        if (admit) admit_up_layout(L, offb + upb + nb + 16, nb);
+        if (!L.h_io.ensure(admit ? L.a_up.end : offb + upb + nb + 16)) return false;
         uint64_t* ho = (uint64_t*)L.h_io.p;
         uint32_t* hk = (uint32_t*)((uint8_t*)L.h_io.p + offb);
         uint32_t* hf = (uint32_t*)((uint8_t*)L.h_io.p + offb + keyb);
@@ -602,7 +654,85 @@ struct tm_batcher {
                 ho[++k] = o;
             }
         }
+        if (admit) pack_admit(L, ho, hb);
         return true;
+    }
+    // TM_BATCHER_ADMIT: the admission planes behind the topic bytes, in the same pinned block and the same
+    // copy.  [mount_len][pub_admit] n u32 each; [client_off][user_off] (n+1) u64; [access][client_defined]
+    // [user_defined][family] n u8 each; [peers 16 n]; the client ids' and usernames' bytes; and, only when
+    // some publish has a mountpoint, the unmounted topics as a CSR of their own for the ACL kernel.
+    // Every piece starts on 8 bytes and the byte pieces end with 8 spare bytes.
+    void admit_up_layout(Lane& L, uint64_t at, uint64_t topic_bytes) const {
+        const uint64_t n = L.n, offb = (n + 1) * 8, keyb = keyb_of(L.n), n8 = (n + 7) & ~7ull;
+        uint64_t cb = 0, ub = 0, mounted = 0;
+        for (const Chunk& c : L.chunks) {
+            const uint8_t* p = c.cred.data() + c.chead;
+            for (size_t j = c.head; j < c.lens.size(); ++j) {
+                CredHead h;
+                std::memcpy(&h, p, sizeof h);
+                cb += h.client_len;
+                ub += h.user_len;
+                mounted |= c.mlen[j];
+                p += c.crlen[j];
+            }
+        }
+        Lane::AdmitUp& A = L.a_up;
+        auto take = [&](uint64_t bytes) {
+            const uint64_t o = at;
+            at += (bytes + 7) & ~7ull;
+            return o;
+        };
+        at = (at + 7) & ~7ull;
+        A.mlen = take(keyb);
+        A.padmit = take(keyb);
+        A.coff = take(offb);
+        A.uoff = take(offb);
+        A.access = take(n8);
+        A.cdef = take(n8);
+        A.udef = take(n8);
+        A.fam = take(n8);
+        A.peers = take(16 * n);
+        A.cbytes = take(cb + 8);
+        A.ubytes = take(ub + 8);
+        A.utoff = mounted ? take(offb) : 0;
+        A.utbytes = mounted ? take(topic_bytes + 8) : 0;
+        A.end = at + 8;
+    }
+    void pack_admit(Lane& L, const uint64_t* ho, const uint8_t* hb) {
+        const Lane::AdmitUp& A = L.a_up;
+        uint8_t* base = (uint8_t*)L.h_io.p;
+        uint32_t* ml = (uint32_t*)(base + A.mlen);
+        uint32_t* pa = (uint32_t*)(base + A.padmit);
+        uint64_t* co = (uint64_t*)(base + A.coff);
+        uint64_t* uo = (uint64_t*)(base + A.uoff);
+        uint64_t* to = A.utoff ? (uint64_t*)(base + A.utoff) : nullptr;
+        uint64_t k = 0, c_at = 0, u_at = 0, t_at = 0;
+        co[0] = uo[0] = 0;
+        if (to) to[0] = 0;
+        for (const Chunk& c : L.chunks) {
+            const uint8_t* p = c.cred.data() + c.chead;
+            for (size_t j = c.head; j < c.lens.size(); ++j, ++k) {
+                CredHead h;
+                std::memcpy(&h, p, sizeof h);
+                ml[k] = c.mlen[j];
+                pa[k] = c.padmit[j];
+                base[A.access + k] = (uint8_t)TM_ACL_PUBLISH;
+                base[A.cdef + k] = h.client_defined;
+                base[A.udef + k] = h.user_defined;
+                base[A.fam + k] = h.peer_family;
+                std::memcpy(base + A.peers + 16 * k, h.peer, 16);
+                if (h.client_len) std::memcpy(base + A.cbytes + c_at, p + sizeof h, h.client_len);
+                if (h.user_len) std::memcpy(base + A.ubytes + u_at, p + sizeof h + h.client_len, h.user_len);
+                co[k + 1] = c_at += h.client_len;
+                uo[k + 1] = u_at += h.user_len;
+                if (to) {   // T as the client sent it: the topic behind its mountpoint
+                    const uint64_t len = ho[k + 1] - ho[k] - c.mlen[j];
+                    if (len) std::memcpy(base + A.utbytes + t_at, hb + ho[k] + c.mlen[j], len);
+                    to[k + 1] = t_at += len;
+                }
+                p += c.crlen[j];
+            }
+        }
     }
     // the packed block of a publish batch (device and pinned copies alike):
     // [hdr 4 u64][doff (n+1) u64][sub_off (n+1) u64][deliveries cap x 16 B][pairs scap x 8 B];
@@ -714,6 +844,7 @@ struct tm_batcher {
     struct BlockLayout {
         uint64_t o_pairs, o_pickw, o_pairw, o_ihdr, o_inbox, o_epub, o_eto, o_ewd, backb, outb, ecap;
         uint64_t o_fhdr, o_fgroups, o_fpub;
+        uint64_t o_ahdr, o_rule, o_code, o_aclres, a_back;   // TM_BATCHER_ADMIT; a_back: the bytes from o_ahdr that come back
     };
     // the forward plan from `at` on; returns its end
     uint64_t forward_layout(BlockLayout& B, uint64_t at, uint64_t cap) const {
@@ -723,6 +854,17 @@ struct tm_batcher {
         B.o_fpub = B.o_fgroups + cap * 16;
         return B.o_fpub + cap * 4;
     }
+    // the admission outputs from `at` on, in what comes back: [admit hdr 8 u64][rule n u32][code n u8], and
+    // the ACL results behind them; returns the end
+    uint64_t admit_layout(BlockLayout& B, uint64_t at, uint32_t n) const {
+        if (!admit) return at;
+        B.o_ahdr = (at + 15) & ~15ull;
+        B.o_rule = B.o_ahdr + 64;
+        B.o_code = B.o_rule + keyb_of(n);
+        B.o_aclres = B.o_code + (((uint64_t)n + 7) & ~7ull);
+        B.a_back = B.o_aclres - B.o_ahdr;
+        return B.o_aclres + (((uint64_t)n + 7) & ~7ull);
+    }
     BlockLayout block_layout(uint32_t n, uint64_t cap, uint64_t scap) const {
         BlockLayout B{};
         const uint64_t head = ps_head(n), wb = opts ? 4 : 0;
@@ -730,7 +872,7 @@ struct tm_batcher {
             B.o_pairs = head + cap * 16;
             B.o_pickw = B.o_pairs + scap * 8;
             B.o_pairw = B.o_pickw + cap * wb;
-            B.outb = B.backb = forward_layout(B, B.o_pairw + scap * wb, cap);
+            B.outb = B.backb = admit_layout(B, forward_layout(B, B.o_pairw + scap * wb, cap), n);
             return B;
         }
         B.ecap = cap + scap;
@@ -740,7 +882,7 @@ struct tm_batcher {
         B.o_epub = B.o_inbox + B.ecap * 16;
         B.o_eto = B.o_epub + B.ecap * 4;
         B.o_ewd = B.o_eto + B.ecap * 4;
-        B.o_pairs = B.backb = (forward_layout(B, B.o_ewd + B.ecap * 4, cap) + 15) & ~15ull;
+        B.o_pairs = B.backb = (admit_layout(B, forward_layout(B, B.o_ewd + B.ecap * 4, cap), n) + 15) & ~15ull;
         B.o_pairw = B.o_pairs + scap * 8;
         B.outb = B.o_pairw + scap * 4;
         return B;
@@ -750,10 +892,11 @@ struct tm_batcher {
         const uint32_t n = L.n;
         const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), upb = upb_of(n), head = ps_head(n);
         const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
-        if (!L.d_io.ensure(offb + upb + nbytes + 16)) return TM_ENOMEM;
+        const uint64_t upbytes = admit ? L.a_up.end : offb + upb + nbytes + 8;   // one block, one copy
+        if (!L.d_io.ensure(upbytes + 8)) return TM_ENOMEM;
         hipStream_t s = L.stream;
         clk::time_point t0 = clk::now();
-        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + upb + nbytes + 8, hipMemcpyHostToDevice, s)))
+        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, upbytes, hipMemcpyHostToDevice, s)))
             return TM_EDEVICE;
         const uint64_t* d_off = (const uint64_t*)L.d_io.p;
         const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
@@ -795,7 +938,32 @@ struct tm_batcher {
                     (tm_inbox*)(d + B.o_inbox), ecap, (uint32_t*)(d + B.o_epub), (uint32_t*)(d + B.o_eto),
                     (uint32_t*)(d + B.o_ewd), ecap, s);
             };
+            if (admit) {   // the ACL check and the admission in front of the publish call: pure, so a rerun repeats them
+                const Lane::AdmitUp& A = L.a_up;
+                const uint8_t* u = (const uint8_t*)L.d_io.p;
+                uint32_t* d_rule = (uint32_t*)(d + B.o_rule);
+                int8_t* d_acl = (int8_t*)(d + B.o_aclres);
+                int arc = TM_OK;
+                if (L.acl)
+                    arc = tm_acl_check_batch_device(
+                        L.acl, n, u + A.access, A.utoff ? u + A.utbytes : d_bytes,
+                        A.utoff ? (const uint64_t*)(u + A.utoff) : d_off, u + A.cbytes, (const uint64_t*)(u + A.coff),
+                        u + A.cdef, u + A.ubytes, (const uint64_t*)(u + A.uoff), u + A.udef, u + A.peers, u + A.fam,
+                        d_acl, d_rule, s);
+                else if (!chk(hipMemsetAsync(d_rule, 0xFF, (uint64_t)n * 4, s)))   // no rule set: no rule matched
+                    return TM_EDEVICE;
+                if (arc != TM_OK) return arc;
+                arc = tm_admit_batch_device(d_bytes, d_off, n, (const uint32_t*)(u + A.mlen), dv.pub_flags,
+                                            (const uint32_t*)(u + A.padmit), zones.data(), (uint32_t)zones.size(),
+                                            L.acl ? d_acl : nullptr, d + B.o_code, (uint64_t*)(d + B.o_ahdr), s);
+                if (arc != TM_OK) return arc;
+            }
             const int rc =
+                admit ? tm_publish_stream_gated_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
+                                                       L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
+                                                       (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
+                                                       (tm_pair*)(d + o_pairs), &dv, (uint32_t*)(d + o_pickw),
+                                                       d + B.o_code, s) :
                 opts ? tm_publish_stream_opts_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
                                                      L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
                                                      (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
@@ -875,7 +1043,7 @@ struct tm_batcher {
                         (inbox && (!down(B.o_ihdr, 64 + S * 16) || !down(B.o_epub, E * 4) || !down(B.o_eto, E * 4) ||
                                    !down(B.o_ewd, E * 4))) ||
                         (forward && (!down(B.o_fhdr, 64 + FG * 16) || !down(B.o_fpub, FM * 4))) ||
-                        !chk(hipStreamSynchronize(s)))
+                        (admit && !down(B.o_ahdr, B.a_back)) || !chk(hipStreamSynchronize(s)))
                         return TM_EDEVICE;
                     L.sync_ns += ns_since(t0);
                     h = (const uint8_t*)L.h_out.p;
@@ -898,6 +1066,11 @@ struct tm_batcher {
                     if (L.r_fhdr[6] != 0) return TM_EDEVICE;   // pub_cap = group_cap = cap: a publish state of 0 leaves none
                     L.r_fgroups = (const tm_forward_group*)(h + B.o_fgroups);
                     L.r_fpub = (const uint32_t*)(h + B.o_fpub);
+                }
+                if (admit) {
+                    L.r_ahdr = (const uint64_t*)(h + B.o_ahdr);
+                    L.r_rule = (const uint32_t*)(h + B.o_rule);
+                    L.r_code = h + B.o_code;
                 }
                 results = D;
                 return TM_OK;
@@ -934,7 +1107,17 @@ struct tm_batcher {
             for (size_t j = c.head + (lo > i ? lo - i : 0u); j < c.reqs.size() && i + (j - c.head) < hi; ++j) {
                 const uint32_t k = i + (uint32_t)(j - c.head);
                 const Req& r = c.reqs[j];
-                if (opts) {
+                if (admit) {
+                    if (rc != TM_OK)
+                        r.afn(r.ctx, r.ticket, rc, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0xFFFFFFFFu);
+                    else if (L.r_code[k])   // refused: its code and rule, nothing else
+                        r.afn(r.ctx, r.ticket, TM_OK, nullptr, nullptr, 0, nullptr, nullptr, 0, L.r_code[k], L.r_rule[k]);
+                    else
+                        r.afn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], L.r_pickw + L.r_doff[k],
+                              (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]), inbox ? nullptr : L.r_pairs + L.r_soff[k],
+                              inbox ? nullptr : L.r_pairw + L.r_soff[k], (uint32_t)(L.r_soff[k + 1] - L.r_soff[k]), 0,
+                              L.r_rule[k]);
+                } else if (opts) {
                     if (rc == TM_OK)
                         r.ofn(r.ctx, r.ticket, TM_OK, L.r_deliv + L.r_doff[k], L.r_pickw + L.r_doff[k],
                               (uint32_t)(L.r_doff[k + 1] - L.r_doff[k]), inbox ? nullptr : L.r_pairs + L.r_soff[k],
@@ -1083,6 +1266,7 @@ struct tm_batcher {
             if (m > st.max_batch) st.max_batch = m;
             if (rc == TM_OK) st.results += results;
             else st.failed_batches++;
+            if (rc == TM_OK && admit && m) st.refused += m - L.r_ahdr[0];
             free_lanes.push_back(idx);
             --in_flight;
             cv_lane.notify_all();
@@ -1131,7 +1315,8 @@ struct tm_batcher {
                 // until the deadline, or the eager age when a lane is free
                 // (a lane freed or a batch's worth arriving meanwhile wakes it)
                 const uint32_t us = eager_ready() ? std::min(cfg.eager_us, cfg.deadline_us) : cfg.deadline_us;
-                const int64_t left = oldest + (int64_t)us * 1000 - now_ns();
+                // (a stripe counted as pending stores its arrival time just after: look again in a microsecond)
+                const int64_t left = oldest == INT64_MAX ? 1000 : oldest + (int64_t)us * 1000 - now_ns();
                 if (left > 0) sleep_for(lk, std::chrono::nanoseconds(std::min<int64_t>(left, 1000000)));
             }
         }
@@ -1182,7 +1367,8 @@ namespace {
 inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_t* topic, uint32_t len, Req r,
                                                      bool publish, uint32_t pub_key, uint64_t* ticket_out,
                                                      bool opts = false, uint32_t pub_flags = 0,
-                                                     uint32_t pub_from = 0) {
+                                                     uint32_t pub_from = 0, const tm_pub_creds* creds = nullptr,
+                                                     uint32_t mount_len = 0, uint32_t pub_admit = 0) {
     if (t_stripe < 0) t_stripe = (int)(g_stripe_rr.fetch_add(1, std::memory_order_relaxed) % NSTRIPE);
     Stripe& s = b->stripes[t_stripe];
     uint64_t t, was;
@@ -1197,6 +1383,22 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
         if (opts) {   // TM_BATCHER_OPTS
             s.cur.pflags.push_back(pub_flags);
             s.cur.pfrom.push_back(pub_from);
+        }
+        if (creds) {   // TM_BATCHER_ADMIT: the credentials copied as one record
+            CredHead h{};
+            h.client_len = creds->client_len;
+            h.user_len = creds->user_len;
+            h.client_defined = creds->client_defined ? 1 : 0;
+            h.user_defined = creds->user_defined ? 1 : 0;
+            h.peer_family = creds->peer_family;
+            std::memcpy(h.peer, creds->peer, 16);
+            const uint8_t* hp = reinterpret_cast<const uint8_t*>(&h);
+            s.cur.cred.insert(s.cur.cred.end(), hp, hp + sizeof h);
+            if (h.client_len) s.cur.cred.insert(s.cur.cred.end(), creds->client_id, creds->client_id + h.client_len);
+            if (h.user_len) s.cur.cred.insert(s.cur.cred.end(), creds->username, creds->username + h.user_len);
+            s.cur.crlen.push_back((uint32_t)sizeof h + h.client_len + h.user_len);
+            s.cur.mlen.push_back(mount_len);
+            s.cur.padmit.push_back(pub_admit);
         }
         // the counters change only under the stripe lock: plain load + store
         // (no read-modify-write per publish); the 0 -> 1 step is seq_cst for
@@ -1222,8 +1424,9 @@ extern "C" {
 // ifn / ffn: the batch callbacks of tm_batcher_open_inbox / tm_batcher_open_plans (the caller checked the
 // flags), else null
 static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn ifn, tm_forward_done_fn ffn,
-                        void* ictx, tm_batcher** out) {
+                        void* ictx, tm_batcher** out, const tm_admit_config* ac = nullptr) {
     if (!e || !out) return TM_EINVAL;
+    if (ac && (ac->n_acl != 0 && (int)ac->n_acl != tm_engine_replicas(e)) && tm_engine_replicas(e) > 0) return TM_EINVAL;
     tm_batcher* b = new (std::nothrow) tm_batcher();
     if (!b) return TM_ENOMEM;
     b->eng = e;
@@ -1259,6 +1462,8 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
     b->sticky = (b->cfg.flags & TM_BATCHER_STICKY) != 0;
     b->opts = (b->cfg.flags & TM_BATCHER_OPTS) != 0;
     b->upgrade = (b->cfg.flags & TM_BATCHER_UPGRADE_QOS) != 0;
+    b->admit = ac != nullptr;
+    if (ac) b->zones.assign(ac->zones, ac->zones + ac->n_zones);
     // an options lane takes one path, the stream-ordered call, for keyed picks too
     // (and a forward lane: its plan reads the stream-ordered call's packed records)
     b->stream = b->round_robin || b->sticky || b->opts || b->forward || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
@@ -1279,6 +1484,7 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
             return TM_ENOMEM;
         }
         L->device = devs[k % devs.size()];
+        if (ac && ac->n_acl && ac->acl && R > 0) L->acl = ac->acl[k % devs.size()];   // its replica's rule set
         // normal priority (A/B: TM_BATCHER_PRIO=1 makes the lanes
         // high-priority streams, as bench.py's, each on a hardware queue of
         // its own; profiles/r05_y)
@@ -1323,7 +1529,7 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
             if (L->device < 0 || hipSetDevice(L->device) != hipSuccess) continue;
             if (b->stream) {   // the first batch's four capacities
                 const tm_publish_caps c = b->stream_caps(*L, pre);
-                const uint64_t io = offb + b->upb_of((uint32_t)pre) + nbytes + 16;
+                const uint64_t io = offb + b->upb_of((uint32_t)pre) + nbytes + 16 + (b->admit ? pre * 160 : 0);
                 const tm_batcher::BlockLayout B = b->block_layout((uint32_t)pre, c.routes, c.pairs);
                 if (b->inbox)
                     (void)L->d_iws.ensure(tm_inbox_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.pairs, B.ecap));
@@ -1372,24 +1578,37 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
 }
 
 int tm_batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_batcher** out) {
-    if (cfg && (cfg->flags & (TM_BATCHER_INBOX | TM_BATCHER_FORWARD))) return TM_EINVAL;   // the modes need their batch callbacks
+    // the modes need their batch callbacks, the admission mode its configuration
+    if (cfg && (cfg->flags & (TM_BATCHER_INBOX | TM_BATCHER_FORWARD | TM_BATCHER_ADMIT))) return TM_EINVAL;
     return batcher_open(e, cfg, nullptr, nullptr, nullptr, out);
 }
 
 int tm_batcher_open_inbox(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn fn, void* ctx,
                           tm_batcher** out) {
     const uint32_t need = TM_BATCHER_INBOX | TM_BATCHER_PUBLISH | TM_BATCHER_OPTS;
-    if (!cfg || !fn || (cfg->flags & need) != need || (cfg->flags & TM_BATCHER_FORWARD)) return TM_EINVAL;
+    if (!cfg || !fn || (cfg->flags & need) != need || (cfg->flags & (TM_BATCHER_FORWARD | TM_BATCHER_ADMIT)))
+        return TM_EINVAL;
     return batcher_open(e, cfg, fn, nullptr, ctx, out);
 }
 
 int tm_batcher_open_plans(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_done_fn inbox_fn,
                           tm_forward_done_fn forward_fn, void* ctx, tm_batcher** out) {
-    if (!cfg) return TM_EINVAL;
+    if (!cfg || (cfg->flags & TM_BATCHER_ADMIT)) return TM_EINVAL;
     const bool inbox = (cfg->flags & TM_BATCHER_INBOX) != 0, forward = (cfg->flags & TM_BATCHER_FORWARD) != 0;
     if ((!inbox && !forward) || inbox != (inbox_fn != nullptr) || forward != (forward_fn != nullptr)) return TM_EINVAL;
     if (!(cfg->flags & TM_BATCHER_PUBLISH) || (inbox && !(cfg->flags & TM_BATCHER_OPTS))) return TM_EINVAL;
     return batcher_open(e, cfg, inbox_fn, forward_fn, ctx, out);
+}
+
+int tm_batcher_open_admit(tm_engine* e, const tm_batcher_config* cfg, const tm_admit_config* ac,
+                          tm_inbox_done_fn inbox_fn, tm_forward_done_fn forward_fn, void* ctx, tm_batcher** out) {
+    const uint32_t need = TM_BATCHER_ADMIT | TM_BATCHER_PUBLISH | TM_BATCHER_OPTS;
+    if (!cfg || (cfg->flags & need) != need) return TM_EINVAL;
+    if (!ac || !ac->zones || ac->n_zones < 1 || ac->n_zones > TM_ADMIT_MAX_ZONES || (ac->n_acl && !ac->acl))
+        return TM_EINVAL;
+    const bool inbox = (cfg->flags & TM_BATCHER_INBOX) != 0, forward = (cfg->flags & TM_BATCHER_FORWARD) != 0;
+    if (inbox != (inbox_fn != nullptr) || forward != (forward_fn != nullptr)) return TM_EINVAL;
+    return batcher_open(e, cfg, inbox_fn, forward_fn, ctx, out, ac);
 }
 
 int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batch_done_fn fn, void* ctx,
@@ -1415,12 +1634,29 @@ int tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len,
 int tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
                                    uint32_t pub_flags, uint32_t pub_from, tm_publish_opts_done_fn fn, void* ctx,
                                    uint64_t* ticket_out) {
-    if (!b || !fn || (!topic && len) || !b->opts || (pub_flags & 3u) == 3u) return TM_EINVAL;
+    if (!b || !fn || (!topic && len) || !b->opts || b->admit || (pub_flags & 3u) == 3u) return TM_EINVAL;
     Req r;
     r.ofn = fn;
     r.ctx = ctx;
     r.ticket = 0;
     return submit_one(b, topic, len, r, true, pub_key, ticket_out, true, pub_flags, pub_from);
+}
+
+int tm_batcher_submit_publish_admit(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t mount_len,
+                                    uint32_t pub_key, uint32_t pub_flags, uint32_t pub_admit, uint32_t pub_from,
+                                    const tm_pub_creds* creds, tm_publish_admit_done_fn fn, void* ctx,
+                                    uint64_t* ticket_out) {
+    if (!b || !fn || (!topic && len) || !b->admit || !creds || (pub_flags & 3u) == 3u) return TM_EINVAL;
+    if (mount_len > len || (pub_admit & 0xFFu) >= b->zones.size()) return TM_EINVAL;
+    if ((creds->client_len && !creds->client_id) || (creds->user_len && !creds->username) ||
+        creds->client_len > 65535u || creds->user_len > 65535u ||
+        (creds->peer_family != 0 && creds->peer_family != 4 && creds->peer_family != 6))
+        return TM_EINVAL;
+    Req r;
+    r.afn = fn;
+    r.ctx = ctx;
+    r.ticket = 0;
+    return submit_one(b, topic, len, r, true, pub_key, ticket_out, true, pub_flags, pub_from, creds, mount_len, pub_admit);
 }
 
 int tm_batcher_flush(tm_batcher* b) {

@@ -3767,7 +3767,13 @@ struct tm_engine {
                             uint32_t strategy, const uint32_t* pub_key, uint32_t* cur, uint32_t* stk,
                             const tm_publish_caps& c,
                             uint8_t* ws, uint64_t* hdr, uint64_t* doff, uint64_t* sub_off, void* deliv, void* pairs,
-                            hipStream_t st, const tm_deliver* dv = nullptr, uint32_t* pick_word = nullptr) {
+                            hipStream_t st, const tm_deliver* dv = nullptr, uint32_t* pick_word = nullptr,
+                            const uint8_t* admit = nullptr) {
+        // admit (tm_publish_stream_gated_device; n device bytes): a topic
+        // with a non-zero byte is walked (stage 1 is ungated: raw[0] and state
+        // 1 count its ids) and then gets no routes, so aggre, the dispatch
+        // count, the share lookup, the ranked-slot passes and the pack all see
+        // zero slots for it and need no gate of their own.
         // dv (tm_publish_stream_opts_device; device pointers): the delivery
         // words too -- dv->sub_deliver parallel to pairs, pick_word parallel to
         // deliv.  The count pass stores each slot's publish index and the
@@ -3792,7 +3798,7 @@ struct tm_engine {
         uint32_t* dest = u32(L.ddest);
         HIPCHK(launch_routes(route_view(d), bytes, off, n, u32(L.rcounts), u64(L.roff), u32(L.rids),
                              reinterpret_cast<uint4*>(ws + L.rexact), u32(L.dcount), u64(L.aoff), src, dest, c.routes,
-                             raw + 1, u64(L.rscan), st, &av, u64(L.akey), gate));
+                             raw + 1, u64(L.rscan), st, &av, u64(L.akey), gate, admit));
         HIPCHK(launch_stream_check(ctl, 2, raw + 1, c.routes, st));
         // 3. aggre/1 and the local dispatch: slots = min(route total, caps.routes), read on the device
         const uint64_t R = c.routes;
@@ -6276,7 +6282,7 @@ static int publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uin
                                  tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
                                  uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
                                  tm_delivery* d_deliv, tm_pair* d_pairs, void* hip_stream, const tm_deliver* dv,
-                                 uint32_t* d_pick_word) {
+                                 uint32_t* d_pick_word, const uint8_t* d_code = nullptr) {
     if (!d_off || !d_hdr || !d_doff || !d_sub_off || !caps || !d_workspace) return TM_EINVAL;
     if (!share_strategy_ok(strategy)) return TM_EINVAL;
     if (share_strategy_keyed(strategy) && n && !d_pub_key) return TM_EINVAL;
@@ -6305,7 +6311,7 @@ static int publish_stream_device(tm_engine* e, const uint8_t* d_bytes, const uin
         uint32_t* stk = cursors ? cursors->sbuf.as<uint32_t>() : tm_engine::share_view(d).sticky;
         e->run_publish_stream(d, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cur, stk, c,
                               static_cast<uint8_t*>(d_workspace), d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, st, dv,
-                              d_pick_word);
+                              d_pick_word, d_code);
         return TM_OK;
     }, [&] { e->finish_batch(n); });
 }
@@ -6331,6 +6337,24 @@ int tm_publish_stream_opts_device(tm_engine* e, const uint8_t* d_bytes, const ui
     return publish_stream_device(e, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cursors, caps, d_workspace,
                                  workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, hip_stream, deliver,
                                  d_pick_word);
+}
+
+// the stream call behind an admission verdict: deliver and d_pick_word both
+// NULL select the plain call, both given the call with options
+int tm_publish_stream_gated_device(tm_engine* e, const uint8_t* d_bytes, const uint64_t* d_off, uint32_t n,
+                                   uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                                   tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                                   uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                                   tm_delivery* d_deliv, tm_pair* d_pairs, const tm_deliver* deliver,
+                                   uint32_t* d_pick_word, const uint8_t* d_code, void* hip_stream) {
+    if (!deliver) {
+        if (d_pick_word) return TM_EINVAL;
+    } else if (!caps || deliver_args_bad(deliver, n, caps->pairs) || (caps->routes && !d_pick_word)) {
+        return TM_EINVAL;
+    }
+    return publish_stream_device(e, d_bytes, d_off, n, topic_bytes, strategy, d_pub_key, cursors, caps, d_workspace,
+                                 workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, hip_stream, deliver,
+                                 deliver ? d_pick_word : nullptr, d_code);
 }
 
 // pick/5 with FailedSubs (share.hip tm_share_retry_resolve / tm_share_retry_pick):

@@ -134,12 +134,15 @@ hipError_t launch_scan(const uint32_t* counts, uint32_t n, uint64_t* out_off, ui
 // match lists: per topic its literal-topic routes, then each matched filter's
 // routes.  exact: n uint2, rcount: n u32, tmp: scan_tmp_elems(n).  out_cap
 // == 0: counts and offsets only.  av != null: also out_key[route] =
-// to_rank << 32 | target rank (the aggre sort key).
+// to_rank << 32 | target rank (the aggre sort key).  admit != null (n bytes,
+// tm_publish_stream_gated_device): a topic with admit[t] != 0 gets no routes,
+// so every later stage of the publish call sees zero slots for it.
 hipError_t launch_routes(const RouteView& rv, const uint8_t* bytes, const uint64_t* off, uint32_t n,
                          const uint32_t* counts, const uint64_t* ids_off, const uint32_t* ids, uint4* exact,
                          uint32_t* rcount, uint64_t* out_off, uint32_t* out_src, uint32_t* out_dest,
                          uint64_t out_cap, uint64_t* total, uint64_t* scan_tmp, hipStream_t st,
-                         const AggreView* av = nullptr, uint64_t* out_key = nullptr, const uint64_t* gate = nullptr);
+                         const AggreView* av = nullptr, uint64_t* out_key = nullptr, const uint64_t* gate = nullptr,
+                         const uint8_t* admit = nullptr);
 
 // emqx_broker:aggre/1 (aggre.hip) over a match_routes CSR (rcount, roff,
 // src, dest, key from launch_routes with av; key rows of topics with > 4096

@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(RBLOCK)
 tm_route_count(RouteView rv, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n,
                const uint32_t* __restrict__ counts, const uint64_t* __restrict__ ids_off,
                const uint32_t* __restrict__ ids, uint4* __restrict__ exact, uint32_t* __restrict__ rcount,
-               const uint64_t* __restrict__ gate) {
+               const uint64_t* __restrict__ gate, const uint8_t* __restrict__ admit) {
     __shared__ uint32_t lds_inc[RBLOCK];
     __shared__ uint32_t lds_mr[RBLOCK];
     __shared__ uint64_t lds_scan[RBLOCK / 64];
@@ -67,8 +67,11 @@ tm_route_count(RouteView rv, const uint8_t* __restrict__ bytes, const uint64_t* 
     lds_inc[threadIdx.x] = (uint32_t)(ex + c);
     lds_mr[threadIdx.x] = 0;
     uint4 xe = make_uint4(0, 0, 0, 0);
+    // a refused publish (admit[t] != 0, tm_publish_stream_gated_device) has no
+    // routes: a zero exact slot here, and its ids count nothing below
+    const bool refused = admit && threadIdx.x < tn && admit[t] != 0;
     if (threadIdx.x < tn) {
-        xe = exact_lookup(rv, bytes, off[t], (uint32_t)(off[t + 1] - off[t]));
+        if (!refused) xe = exact_lookup(rv, bytes, off[t], (uint32_t)(off[t + 1] - off[t]));
         exact[t] = xe;
     }
     __syncthreads();
@@ -76,7 +79,10 @@ tm_route_count(RouteView rv, const uint8_t* __restrict__ bytes, const uint64_t* 
     for (uint64_t j = threadIdx.x; j < agg; j += RBLOCK) {
         const uint32_t id = ids[base + j];
         const uint32_t rc = id < rv.n_filters ? rv.fr_meta[id].y : 0u;
-        if (rc) atomicAdd(&lds_mr[topic_of(lds_inc, tn, j)], rc);
+        if (rc) {
+            const uint32_t lo = topic_of(lds_inc, tn, j);
+            if (!admit || admit[t0 + lo] == 0) atomicAdd(&lds_mr[lo], rc);
+        }
     }
     __syncthreads();
     if (threadIdx.x < tn) rcount[t] = xe.y + lds_mr[threadIdx.x];
@@ -89,7 +95,8 @@ tm_route_emit(RouteView rv, AggreView av, uint32_t n, const uint32_t* __restrict
               const uint64_t* __restrict__ ids_off, const uint32_t* __restrict__ ids,
               const uint4* __restrict__ exact, const uint32_t* __restrict__ rcount,
               const uint64_t* __restrict__ out_off, uint32_t* __restrict__ out_src, uint32_t* __restrict__ out_dest,
-              uint64_t* __restrict__ out_key, uint64_t out_cap, const uint64_t* __restrict__ gate) {
+              uint64_t* __restrict__ out_key, uint64_t out_cap, const uint64_t* __restrict__ gate,
+              const uint8_t* __restrict__ admit) {
     __shared__ uint32_t lds_inc[RBLOCK];
     __shared__ uint64_t lds_m[RBLOCK];      // exclusive prefix of matched-route counts
     __shared__ uint64_t lds_scan[RBLOCK / 64];
@@ -125,7 +132,9 @@ tm_route_emit(RouteView rv, AggreView av, uint32_t n, const uint32_t* __restrict
         if (j < agg) {
             id = ids[base + j];
             lo = topic_of(lds_inc, tn, j);
-            if (id < rv.n_filters) {
+            // a refused topic's ids carry no routes: rc stays 0, so the running
+            // r agrees with lds_m (built from the gated rcount)
+            if (id < rv.n_filters && (!admit || admit[t0 + lo] == 0)) {
                 const uint4 fm = rv.fr_meta[id];   // one 16 B load: segment, count, to_rank
                 fo = fm.x;
                 rc = fm.y;
@@ -155,18 +164,19 @@ hipError_t launch_routes(const RouteView& rv, const uint8_t* bytes, const uint64
                          const uint32_t* counts, const uint64_t* ids_off, const uint32_t* ids, uint4* exact,
                          uint32_t* rcount, uint64_t* out_off, uint32_t* out_src, uint32_t* out_dest,
                          uint64_t out_cap, uint64_t* total, uint64_t* scan_tmp, hipStream_t st, const AggreView* av,
-                         uint64_t* out_key, const uint64_t* gate) {
+                         uint64_t* out_key, const uint64_t* gate, const uint8_t* admit) {
     if (n == 0) {
         hipError_t err = hipMemsetAsync(out_off, 0, 8, st);
         return err == hipSuccess ? hipMemsetAsync(total, 0, 8, st) : err;
     }
     const dim3 g(rdiv_up(n, RBLOCK)), blk(RBLOCK);
-    hipLaunchKernelGGL(tm_route_count, g, blk, 0, st, rv, bytes, off, n, counts, ids_off, ids, exact, rcount, gate);
+    hipLaunchKernelGGL(tm_route_count, g, blk, 0, st, rv, bytes, off, n, counts, ids_off, ids, exact, rcount, gate, admit);
     hipError_t err = launch_scan(rcount, n, out_off, total, scan_tmp, st);
     if (err != hipSuccess) return err;
     if (out_cap)
         hipLaunchKernelGGL(tm_route_emit, g, blk, 0, st, rv, av ? *av : AggreView{nullptr, nullptr, nullptr}, n, counts,
-                           ids_off, ids, exact, rcount, out_off, out_src, out_dest, av ? out_key : nullptr, out_cap, gate);
+                           ids_off, ids, exact, rcount, out_off, out_src, out_dest, av ? out_key : nullptr, out_cap, gate,
+                           admit);
     return hipGetLastError();
 }
 

@@ -92,8 +92,9 @@ class AclRules:
     @staticmethod
     def pack(creds, pubsubs, topics):
         """the batch as the C-ABI's arrays (name -> numpy array), in
-        tm_acl_check_batch's argument order"""
-        n = len(topics)
+        tm_acl_check_batch's argument order; topics None: everything but the
+        topic CSR, for a caller whose topics are on the device already"""
+        n = len(creds) if topics is None else len(topics)
 
         def strs(items):
             bs = [_b(x) for x in items]
@@ -101,7 +102,7 @@ class AclRules:
             if n:
                 off[1:] = np.cumsum([len(x) for x in bs])
             return np.frombuffer(b"".join(bs) + b"\0" * 8, dtype=np.uint8).copy(), off
-        tb, to = strs(topics)
+        tb, to = strs(topics) if topics is not None else (None, None)
         cb, co = strs([c.get("client_id") or b"" for c in creds])
         ub, uo = strs([c.get("username") or b"" for c in creds])
         cd = np.array([c.get("client_id") is not None for c in creds], dtype=np.uint8)
@@ -149,3 +150,60 @@ class AclRules:
         n = len(topics)
         out, rule = self.check_packed(n, self.pack(creds, pubsubs, topics))
         return [(RESULT[int(out[i])], None if rule[i] == 0xFFFFFFFF else int(rule[i])) for i in range(n)]
+
+
+# ---- publish admission: emqx_packet:validate/1, emqx_mqtt_caps:check_pub/2 and
+# check_pub_acl (src/emqx_protocol.erl:769-794) in front of emqx_broker:publish/1
+ADMIT = {0: "ok", 1: "topic_name_invalid", 2: "qos_not_supported", 3: "topic_alias_invalid",
+         4: "retain_not_supported", 5: "not_authorized"}
+
+
+class Zones:
+    """The zone table of the admission calls (tm_zone_caps records): per zone
+    the '$mqtt_pub_caps' of emqx_mqtt_caps and the two ACL switches of
+    emqx_zone.  Defaults as the reference's: QoS 2, no aliases, retain
+    available, ACL enabled, acl_nomatch = deny.  The position of a zone is the
+    index a publish's pub_admit word carries."""
+
+    def __init__(self):
+        self.names = []
+        self.caps = []
+
+    def add(self, name, max_qos_allowed=2, max_topic_alias=0, retain_available=True, enable_acl=True,
+            acl_nomatch="deny"):
+        if len(self.caps) >= L.TM_ADMIT_MAX_ZONES:
+            raise ValueError("more than %d zones" % L.TM_ADMIT_MAX_ZONES)
+        if acl_nomatch not in ("allow", "deny"):
+            raise ValueError(acl_nomatch)
+        self.names.append(name)
+        self.caps.append(L.TmZoneCaps(int(max_qos_allowed), int(bool(retain_available)), int(bool(enable_acl)),
+                                      int(acl_nomatch == "allow"), int(max_topic_alias), 0))
+        return len(self.caps) - 1
+
+    def index(self, name):
+        return self.names.index(name)
+
+    def __len__(self):
+        return len(self.caps)
+
+    def table(self):
+        """-> (ctypes array of TmZoneCaps, count) for the batch calls"""
+        return (L.TmZoneCaps * max(len(self.caps), 1))(*self.caps), len(self.caps)
+
+
+def pub_admit(zone=0, is_super=False, alias=None):
+    """the per-publish admission word: zone index, is_super, Topic-Alias
+    (None = the property is absent; an alias of 0 cannot be told from that,
+    and the codec refuses it before this stage)"""
+    return (zone & 0xFF) | (L.TM_ADMIT_SUPER if is_super else 0) | ((alias or 0) << L.TM_ADMIT_ALIAS_SHIFT)
+
+
+def admit_code(topic, qos, retain, zones, zone=0, is_super=False, alias=None, acl="nomatch"):
+    """tm_admit_code for one publish: `topic` as the client sent it
+    (unmounted), acl one of "allow" / "deny" / "nomatch" (or 1 / 0 / -1)"""
+    lib = L.load()
+    t = _b(topic)
+    a = {"allow": 1, "deny": 0, "nomatch": -1}.get(acl, acl)
+    flags = (qos & 3) | (L.TM_MSG_RETAIN if retain else 0)
+    return int(lib.tm_admit_code(t, len(t), flags, pub_admit(zone, is_super, alias),
+                                 ctypes.byref(zones.caps[zone]), int(a)))

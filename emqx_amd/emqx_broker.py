@@ -16,6 +16,9 @@ expansion, aggre and the subscriber fan-out, dispatch.hip).
                                        handle_dispatch/3 (src/emqx_session.erl:667-684, 797-819)
     publish_shared_many(Topics, ...)   the same with route/2's $share clause :187-189: the member
                                        emqx_shared_sub:dispatch/3 picks for every {To, Group} delivery
+    publish_admitted_many(...)         the same behind emqx_packet:validate/1, check_pub_caps and
+                                       check_pub_acl (src/emqx_protocol.erl:769-794): the codes, and
+                                       the admitted publishes' results; a refused one leaves no trace
     dispatch_many(Tos)                 dispatch/2 :218-238 as a remote node's forward/3 calls it
     publish_forward_many(Topics)       publish_many plus route/2's {To, Node} clause :185-186: the
                                        batch's forward/3 calls :209-216 as one bundle per remote node
@@ -184,6 +187,96 @@ class Broker:
         out = self.engine.match_publish_batch(buf, off, STRATEGIES[strategy or self.shared.strategy], keys,
                                               deliver=dv, pick_words=dv is not None)
         return self._published(topics, out[:9], out[9], out[10] if dv else None, out[11] if dv else None, dv)
+
+    # emqx_protocol:process_packet's validate + check_publish in front of do_publish — src/emqx_protocol.erl:217, 769-794
+    def publish_admitted_many(self, topics, creds, msgs, zones, acl=None, mounts=None, admit=None, strategy=None,
+                              keys=None, upgrade_qos=False, cursors=None):
+        """publish_shared_many behind the admission checks, as one chain on one
+        stream without a wait between its calls: ACL check (tm_acl_check_batch_device
+        on the unmounted topics) -> tm_admit_batch_device -> tm_publish_stream_gated_device.
+        topics[i] = MountPoint ++ T and mounts[i] the mountpoint's length (None:
+        0); creds[i] a credentials dict as emqx_access.AclRules takes it; msgs
+        as publish_many's (the QoS and retain bit feed the caps); zones an
+        emqx_access.Zones; admit[i] = (zone index, is_super, alias | None)
+        (None: zone 0, not super, no alias); acl an AclRules on this engine's
+        device (None: every check is nomatch); cursors: the publisher's
+        ShareCursors (None: the replica's built-in array).  -> (codes, rules, published):
+        codes[i] the TM_ADMIT_* code, rules[i] the index of the ACL rule that
+        matched (None without one), published[i] what publish_shared_many
+        returns for an admitted publish and None for a refused one, which
+        reached no cursor and no sticky entry."""
+        import numpy as np
+        import torch
+
+        from . import _lib as L
+        from .emqx_access import AclRules, pub_admit
+        topics = list(topics)
+        n = len(topics)
+        dv = self._deliver(msgs, n, upgrade_qos)
+        if dv is None or len(creds) != n:
+            raise ValueError("one message and one credentials dict per publish")
+        if n == 0:
+            return [], [], []
+        e, dev = self.engine, torch.device("cuda", self.engine.device)
+        st = torch.cuda.current_stream(dev)
+        signed = {1: np.int8, 4: np.int32, 8: np.int64}
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            return torch.from_numpy(a.view(signed[a.dtype.itemsize]).copy() if a.dtype.kind == "u" and
+                                    a.dtype.itemsize > 1 else a.copy()).to(dev)
+
+        def zeros(k, dt):
+            return torch.zeros(max(int(k), 1), dtype=dt, device=dev)
+        mounts = [0] * n if mounts is None else [int(m) for m in mounts]
+        admit = [(0, False, None)] * n if admit is None else list(admit)
+        buf, off = pack(topics)
+        d_b, d_o = up(buf), up(off)
+        d_ml, d_pf, d_fr = up(np.asarray(mounts, np.uint32)), up(np.asarray(dv[0], np.uint32)), \
+            up(np.asarray(dv[1], np.uint32))
+        d_pa = up(np.asarray([pub_admit(*a) for a in admit], np.uint32))
+        d_acl, d_rule = None, zeros(n, torch.int32)
+        d_code, d_ahdr = zeros(n, torch.uint8), zeros(8, torch.int64)
+        if acl is not None:
+            # the ACL sees T unmounted: the topics' own CSR unless some publish has a mountpoint
+            packed = AclRules.pack(creds, ["publish"] * n, [t[m:] for t, m in zip(topics, mounts)] if any(mounts) else None)
+            d = {k: up(v) for k, v in packed.items() if v is not None}
+            d.setdefault("topics", d_b)
+            d.setdefault("topic_off", d_o)
+            d_acl = zeros(n, torch.int8)
+            acl.check_device(n, d, d_acl, d_rule, stream=st)
+        Engine.admit_batch_device(d_b, d_o, n, d_ml, d_pf, d_pa, zones, d_acl, d_code, d_ahdr, stream=st)
+        s = STRATEGIES[strategy or self.shared.strategy]
+        d_k = None if keys is None else up(np.asarray(keys, np.uint32))
+        caps = [max(64, 4 * n)] * 4
+        nbytes = int(off[-1] - off[0])
+        doff, soff, hdr = zeros(n + 1, torch.int64), zeros(n + 1, torch.int64), zeros(L.TM_PUBLISH_HDR_WORDS, torch.int64)
+        while True:
+            wsb = e.publish_stream_opts_workspace_bytes(n, nbytes, caps)
+            ws = zeros(wsb, torch.uint8)
+            deliv, pairs = zeros(4 * caps[1], torch.int32), zeros(2 * caps[2], torch.int32)
+            pkw, prw = zeros(caps[1], torch.int32), zeros(caps[2], torch.int32)
+            e.publish_stream_gated_device(d_b, d_o, n, nbytes, s, d_k, cursors, caps, ws, wsb, hdr, doff, soff, deliv,
+                                          pairs, (d_pf, d_fr, dv[2], prw), pkw, d_code, stream=st)
+            st.synchronize()
+            h = [int(x) for x in hdr.cpu().numpy().view(np.uint64)]
+            if h[6] == 0:
+                break
+            # the stage named did not fit and no cursor moved: the totals up to it are exact, so each of
+            # those capacities grows to its need (and a quarter), the later ones stay, and the call runs again
+            need = (h[4], h[0], h[1], h[5])
+            caps = [max(c, x + x // 4 + 64) if i < h[6] else c for i, (c, x) in enumerate(zip(caps, need))]
+        u32 = lambda t: t.cpu().numpy().view(np.uint32)      # noqa: E731
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)      # noqa: E731
+        code = d_code.cpu().numpy()
+        rule = u32(d_rule) if acl is not None else np.full(n, 0xFFFFFFFF, np.uint32)
+        doff, soff = u64(doff), u64(soff)
+        rec, pr = u32(deliv).reshape(-1, 4), u32(pairs).reshape(-1, 2)
+        planes = ((doff[1:] - doff[:-1]).astype(np.uint32), doff[:-1], rec[:, 0], rec[:, 1], rec[:, 2],
+                  (soff[1:] - soff[:-1]).astype(np.uint32), soff[:-1], pr[:, 0], pr[:, 1])
+        res = self._published(topics, planes, rec[:, 3], u32(prw), u32(pkw), dv)
+        return ([int(c) for c in code], [None if int(r) == 0xFFFFFFFF else int(r) for r in rule[:n]],
+                [None if code[t] else res[t] for t in range(n)])
 
     def _pick_deliver(self, to, member, word, t, dv):
         if member == Engine.NO_MEMBER:

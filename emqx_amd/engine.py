@@ -1187,6 +1187,75 @@ class Engine:
                                                     p(d_sub_off), p(d_deliv), p(d_pairs), dv, p(d_pick_word), st)
         return self._check(rc, "tm_publish_stream_opts_device")
 
+    def publish_stream_gated_device(self, d_bytes, d_off, n, topic_bytes, strategy, d_keys, cursors, caps,
+                                    d_workspace, workspace_bytes, d_hdr, d_doff, d_sub_off, d_deliv, d_pairs, deliver,
+                                    d_pick_word, d_code, stream=None):
+        """tm_publish_stream_gated_device: the stream call behind an admission
+        verdict.  d_code: n device bytes, non-zero = refused (None: ungated).
+        deliver and d_pick_word both None select the plain call, both given
+        (deliver as publish_stream_opts_device takes it) the call with options"""
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        c = L.TmPublishCaps(*[int(x) for x in caps])
+        dv = None
+        if deliver is not None:
+            dv = ctypes.byref(self._deliver_struct(p(deliver[0]), p(deliver[1]), int(deliver[2]), p(deliver[3])))
+        rc = self.lib.tm_publish_stream_gated_device(self.h, p(d_bytes), p(d_off), n, topic_bytes, strategy,
+                                                     p(d_keys), cursors.h if cursors is not None else None,
+                                                     ctypes.byref(c), p(d_workspace), workspace_bytes, p(d_hdr),
+                                                     p(d_doff), p(d_sub_off), p(d_deliv), p(d_pairs), dv,
+                                                     p(d_pick_word), p(d_code), st)
+        return self._check(rc, "tm_publish_stream_gated_device")
+
+    # -- publish admission (admit.hip): validate/1, check_pub/2, check_pub_acl --
+    @staticmethod
+    def admit_batch(buf, off, pub_flags, zones, mount_len=None, pub_admit=None, acl_result=None):
+        """tm_admit_batch on host arrays (no device): -> (code u8[n], hdr
+        u64[8]).  zones: an emqx_access.Zones; acl_result: int8 1 / 0 / -1 per
+        publish as the ACL check writes them (None: every check nomatch)"""
+        lib = L.load()
+        n = len(off) - 1
+        code = np.zeros(max(n, 1), dtype=np.uint8)
+        hdr = np.zeros(8, dtype=np.uint64)
+        tab, nz = zones.table()
+
+        def arr(a, dt):
+            return None if a is None else np.ascontiguousarray(a, dtype=dt)
+        off = arr(off, np.uint64)
+        ml, pf, pa, ar = arr(mount_len, np.uint32), arr(pub_flags, np.uint32), arr(pub_admit, np.uint32), \
+            arr(acl_result, np.int8)
+        rc = lib.tm_admit_batch(_ptr(buf), _ptr(off), n, _ptr(ml), _ptr(pf), _ptr(pa), tab, nz, _ptr(ar), _ptr(code),
+                                _ptr(hdr))
+        if rc != L.TM_OK:
+            raise L.TopicMatchError(rc, "tm_admit_batch")
+        return code[:n], hdr
+
+    @staticmethod
+    def admit_batch_device(d_bytes, d_off, n, d_mount_len, d_pub_flags, d_pub_admit, zones, d_acl_result, d_code,
+                           d_hdr, stream=None):
+        """tm_admit_batch_device over device pointers (tensors or ints; None =
+        NULL), stream-ordered: d_code[n] bytes and d_hdr[8] = {admitted, count
+        of code 1..5, 0, 0}.  zones: an emqx_access.Zones (a host table)"""
+        lib = L.load()
+
+        def p(x):
+            if x is None:
+                return None
+            return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        st = None
+        if stream is not None:
+            st = ctypes.c_void_p(L.stream_handle(stream))
+        tab, nz = zones.table()
+        rc = lib.tm_admit_batch_device(p(d_bytes), p(d_off), n, p(d_mount_len), p(d_pub_flags), p(d_pub_admit), tab,
+                                       nz, p(d_acl_result), p(d_code), p(d_hdr), st)
+        if rc != L.TM_OK:
+            raise L.TopicMatchError(rc, "tm_admit_batch_device")
+
     def publish_pack_opts(self, n, d_counts, d_offs, d_to, d_target, d_ndisp, d_pick, out_cap, d_total, d_sub_off,
                           d_sub_to, d_sub_id, sub_cap, d_sub_total, d_hdr, d_doff, d_deliv, deliv_cap, d_pairs,
                           pair_cap, d_sub_deliver, d_pick_word_slots, d_pair_word, d_pick_word, stream=None):

@@ -1394,6 +1394,47 @@ int tm_publish_stream_opts_device(tm_engine* e, const uint8_t* d_topic_bytes, co
                                   tm_delivery* d_deliv, tm_pair* d_pairs, const tm_deliver* deliver,
                                   uint32_t* d_pick_word, void* hip_stream);
 
+/* The stream call behind an admission verdict (tm_admit_batch_device, below):
+ * a publish the checks in front of publish/1 refused never reaches
+ * emqx_broker:publish/1 in the reference, so here it leaves no trace from the
+ * route stage on.  The arguments are those of tm_publish_stream_opts_device;
+ * `deliver` and d_pick_word both NULL select the plain call
+ * (tm_publish_stream_device), both given the call with options.  The workspace
+ * need is that of the matching *_workspace_bytes function, unchanged.
+ *   d_code   n bytes of the device that owns d_topic_off, read once the work
+ *            queued before on hip_stream has run: 0 = admitted, anything else
+ *            = refused (the TM_ADMIT_* codes).  NULL: ungated.
+ * With d_code == NULL, and with a plane of zeros, every output, the header and
+ * every cursor and sticky entry are bit for bit those of the existing call.
+ * For a topic t with d_code[t] != 0: d_doff[t+1] == d_doff[t] and
+ * d_sub_off[t+1] == d_sub_off[t]; it contributes to no total from the route
+ * stage on (d_hdr[0..3] and [5]); it emits no record, no pair and no word; it
+ * ranks in no round-robin count and draws no sticky entry.  Everything else
+ * equals what the existing call leaves for the batch WITH THOSE TOPICS
+ * REMOVED: the records, the pairs and both word planes bit for bit, the two
+ * offset arrays after deleting the refused topics' entries, and the cursor and
+ * sticky arrays after the call.  Round-robin publishes count in topic-index
+ * order over the ADMITTED topics of the call.
+ * Stage 1, the walk, is not gated: refused topics are walked (refusals are
+ * rare, and an empty or wildcard topic is an ordinary input of every walk
+ * path), so d_hdr[4] and state 1 (caps.ids) COUNT THE REFUSED TOPICS' MATCH
+ * IDS TOO.  The gate sits in the route expansion: a refused topic gets no
+ * routes, hence zero delivery slots in every later stage.
+ * The state rules of the existing call hold unchanged: caps.routes, caps.pairs
+ * and caps.rr need only fit the admitted topics; with a state other than 0 no
+ * cursor or sticky entry has changed and a rerun picks what a first run would
+ * have.  TM_EINVAL: as the call selected, plus a d_pick_word without
+ * `deliver`.  d_code is not validated.  The non-stream batch calls
+ * (tm_match_publish_batch*, tm_match_dispatch_batch*) stay ungated;
+ * tm_inbox_plan_stream_device and tm_forward_plan_stream_device read only the
+ * packed outputs and take a gated call's as they are. */
+int tm_publish_stream_gated_device(tm_engine* e, const uint8_t* d_topic_bytes, const uint64_t* d_topic_off, uint32_t n,
+                                   uint64_t topic_bytes, uint32_t strategy, const uint32_t* d_pub_key,
+                                   tm_share_cursors* cursors, const tm_publish_caps* caps, void* d_workspace,
+                                   uint64_t workspace_bytes, uint64_t* d_hdr, uint64_t* d_doff, uint64_t* d_sub_off,
+                                   tm_delivery* d_deliv, tm_pair* d_pairs, const tm_deliver* deliver,
+                                   uint32_t* d_pick_word, const uint8_t* d_code, void* hip_stream);
+
 /* The retry of dispatch/4 (src/emqx_shared_sub.erl:92-111): after a nack, a
  * timeout or a 'DOWN' the broker picks again with the failed members removed.
  * out_pick[i] = pick(Strategy, _, Group_i, Topic_i, FailedSubs_i) of :211-249,
@@ -1573,6 +1614,7 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
  * Reruns: a publish state other than 0 runs the whole chain again, as without
  * the flag.  The forward plan never reruns alone, and a plan-only inbox rerun
  * (inbox state 2) leaves the forward plan as it is. */
+#define TM_BATCHER_ADMIT        4096u /* with PUBLISH | OPTS: admission in front of the publish call, tm_batcher_open_admit */
 #define TM_BATCHER_FORWARD      2048u /* with TM_BATCHER_PUBLISH: one forward plan per batch, tm_batcher_open_plans */
 
 typedef struct tm_batcher tm_batcher;
@@ -1605,6 +1647,9 @@ typedef struct tm_batcher_stats {
     /* passes beyond a batch's first, summed over batches (a publish batch
      * that did not fit its capacities runs again); tm_batcher_get_stats2 only */
     uint64_t reruns;
+    /* TM_BATCHER_ADMIT: publishes the admission stage refused (admit_code != 0),
+     * summed over batches; tm_batcher_get_stats2 only */
+    uint64_t refused;
 } tm_batcher_stats;
 #define TM_BATCHER_STATS_V1_BYTES (13u * 8u)   /* the prefix tm_batcher_get_stats writes */
 #define TM_BATCHER_STATS_RESET_MAX 1u          /* tm_batcher_get_stats2: zero the max_* fields after this read */
@@ -1755,6 +1800,153 @@ int tm_acl_check_batch_device(tm_acl* a, uint32_t n, const uint8_t* d_access, co
                               const uint8_t* d_client_defined, const uint8_t* d_usernames, const uint64_t* d_user_off,
                               const uint8_t* d_user_defined, const uint8_t* d_peers, const uint8_t* d_peer_family,
                               int8_t* d_out_result, uint32_t* d_out_rule, void* hip_stream);
+
+/* ---- publish admission (admit.hip) -------------------------------------------
+ * What a PUBLISH passes before emqx_protocol:do_publish reaches
+ * emqx_broker:publish/1.  Per publish, the code of the FIRST check that
+ * refuses, in the reference's order:
+ *   TM_ADMIT_TOPIC_NAME   emqx_packet:validate/1 (src/emqx_packet.erl:58-64): the
+ *                         topic is empty, or emqx_topic:wildcard(T): some level is
+ *                         exactly "+" or exactly "#" (src/emqx_topic.erl:41-50).
+ *                         "a/+b", "+a", "a#", "a/b+" are not wildcards; "+", "#",
+ *                         "a/+", "+/a", "a/#/b", "/+", "#/" are.  No UTF-8 check
+ *                         and no length check are made, as in this version.  A
+ *                         Topic-Alias is resolved to its topic by the caller (the
+ *                         codec's clause of :58-59), so an empty topic is invalid.
+ *   emqx_mqtt_caps:check_pub/2 (src/emqx_mqtt_caps.erl:54-75), in the order of
+ *   maps:to_list/1 over the three keys:
+ *   TM_ADMIT_QOS          QoS > max_qos_allowed
+ *   TM_ADMIT_TOPIC_ALIAS  an alias is present and not (0 < Alias =<
+ *                         max_topic_alias); with max_topic_alias = 0 every alias fails
+ *   TM_ADMIT_RETAIN       retain set and retain_available == 0
+ *   TM_ADMIT_ACL          check_pub_acl (src/emqx_protocol.erl:785-794): passed when
+ *                         is_super or enable_acl == 0; else the ACL answer (one
+ *                         module, src/emqx_access_control.erl:104-111): 1 allow
+ *                         passes, 0 deny refuses, -1 ignore follows
+ *                         acl_nomatch_allow.  (The per-connection ACL cache is a
+ *                         memo of the same answer and is not modelled.)
+ * The checks see the topic as the client sent it, before emqx_mountpoint:mount/2:
+ * with a mount_len, bytes [mount_len, len) of the mounted topic the broker sees;
+ * a '+' inside the mountpoint is no level of the topic.
+ *   pub_flags   the word the *_opts calls take: QoS in bits 0-1, retain in bit 2
+ *   pub_admit   bits 0-7 zone index, bit 8 is_super, bits 16-31 the Topic-Alias
+ *               (0 = the property is absent)
+ *   zones       host array of n_zones (1..TM_ADMIT_MAX_ZONES) records
+ *   acl_result  1, 0, -1 per publish as tm_acl_check_batch writes them; NULL =
+ *               every check nomatch
+ *   hdr[8]      {admitted, count of code 1, ..., count of code 5, 0, 0}: the
+ *               figures the broker adds to its packets/publish/ metrics
+ * tm_admit_code is the decision for one publish (topic already unmounted); it
+ * has no error channel but its code, and returns TM_ADMIT_BAD_ARG for a NULL
+ * zone and for a QoS of 3; tm_admit_batch is a loop over it on host arrays and uses no
+ * device (hdr may be NULL).  TM_EINVAL for both batch forms: NULL zones,
+ * n_zones outside 1..TM_ADMIT_MAX_ZONES, a NULL offset, flag or code array
+ * with n > 0; for the host form also decreasing offsets, a zone index >=
+ * n_zones, a QoS of 3 and a mount_len past its topic, all checked before
+ * anything is written.
+ * tm_admit_batch_device: every array but `zones` is device memory of the device
+ * that owns d_hdr; the call enqueues a clear of d_hdr and one kernel on
+ * hip_stream and returns (no synchronisation, no allocation; the zone table is
+ * copied into the kernel's arguments, so `zones` may change once the call has
+ * returned).  d_mount_len NULL: 0.  d_pub_admit NULL: zone 0, not super, no
+ * alias.  The per-publish inputs live in device memory and are NOT checked: a
+ * zone index >= n_zones reads the last zone, a mount_len past its topic leaves
+ * an empty topic (code 1), a QoS of 3 fails the QoS check.  d_topic_off holds
+ * n + 1 NON-DECREASING offsets, the caller's to guarantee as for
+ * tm_acl_check_batch_device; then no byte outside [d_topic_off[0],
+ * d_topic_off[n]) rounded out to 8-byte words aligned BY ADDRESS
+ * (d_topic_bytes itself needs no alignment), and nothing outside the zone
+ * table, is ever read.  Offsets that run backwards give meaningless codes,
+ * but each wave of 64 publishes still reads only inside [d_topic_off[t0],
+ * d_topic_off[t0 + 64]) and never past the LDS window it staged.  n == 0: a zero header.
+ * TM_EINVAL also for a NULL d_hdr and, with n > 0, a NULL d_topic_bytes (the
+ * offsets cannot be read to see that every topic is empty); TM_EDEVICE without
+ * a GPU or on a HIP error. */
+typedef struct tm_zone_caps {
+    uint8_t  max_qos_allowed, retain_available, enable_acl, acl_nomatch_allow;
+    uint16_t max_topic_alias, reserved;
+} tm_zone_caps;   /* 8 B */
+#define TM_ADMIT_MAX_ZONES   256u
+#define TM_ADMIT_OK          0u
+#define TM_ADMIT_TOPIC_NAME  1u
+#define TM_ADMIT_QOS         2u
+#define TM_ADMIT_TOPIC_ALIAS 3u
+#define TM_ADMIT_RETAIN      4u
+#define TM_ADMIT_ACL         5u
+#define TM_ADMIT_BAD_ARG     0xFFFFFFFFu   /* tm_admit_code only: NULL zone, QoS 3 */
+#define TM_ADMIT_SUPER       0x100u   /* pub_admit bit 8: is_super */
+#define TM_ADMIT_ALIAS_SHIFT 16       /* pub_admit bits 16-31: the Topic-Alias */
+uint32_t tm_admit_code(const uint8_t* topic, uint32_t len, uint32_t pub_flags, uint32_t pub_admit,
+                       const tm_zone_caps* zone, int acl_result);
+int tm_admit_batch(const uint8_t* topic_bytes, const uint64_t* topic_off, uint32_t n, const uint32_t* mount_len,
+                   const uint32_t* pub_flags, const uint32_t* pub_admit, const tm_zone_caps* zones, uint32_t n_zones,
+                   const int8_t* acl_result, uint8_t* code, uint64_t* hdr);
+int tm_admit_batch_device(const uint8_t* d_topic_bytes, const uint64_t* d_topic_off, uint32_t n,
+                          const uint32_t* d_mount_len, const uint32_t* d_pub_flags, const uint32_t* d_pub_admit,
+                          const tm_zone_caps* zones, uint32_t n_zones, const int8_t* d_acl_result, uint8_t* d_code,
+                          uint64_t* d_hdr, void* hip_stream);
+
+/* The batcher's admission mode: TM_BATCHER_ADMIT with TM_BATCHER_PUBLISH |
+ * TM_BATCHER_OPTS, and with everything those combine with (ROUND_ROBIN, STICKY,
+ * UPGRADE_QOS, INBOX, FORWARD, EAGER).  It is the path a single-topic publisher
+ * (the NIF) has to the ACL kernel and to the admission stage: a lane packs the
+ * publishes' credentials, mount lengths and admission words beside the topics
+ * in its one H2D copy (and a second topic CSR with the unmounted topics only
+ * when some publish of the batch has mount_len > 0), then enqueues on its
+ * stream, with no wait between them, tm_acl_check_batch_device (access =
+ * publish), tm_admit_batch_device, tm_publish_stream_gated_device and the plans
+ * its flags ask for.  The codes and rule indices come back in the same
+ * read-back block as the records.  A batch that did not fit its capacities
+ * runs the whole chain again: the ACL check and the admission are pure.
+ *   tm_admit_config  zones / n_zones: the zone table, copied at open.  acl: one
+ *                    rule set per replica of the engine (n_acl = the replica
+ *                    count), each opened on that replica's device; NULL (n_acl
+ *                    0) = no rule set, every check is nomatch.  The caller
+ *                    keeps the rule sets open until the batcher is closed;
+ *                    rules may be appended meanwhile (tm_acl serialises that).
+ *   tm_pub_creds     what tm_acl_check_batch takes per check: client id and
+ *                    username bytes (each at most 65535) with their defined
+ *                    flags, the peer's 16 bytes and its family (4, 6, 0 = no
+ *                    peername).  Copied by the submit.
+ * tm_batcher_submit_publish_admit: topic = MountPoint ++ T, mount_len the
+ * mountpoint's length; pub_admit as tm_admit_batch takes it.  The callback is
+ * tm_publish_opts_done_fn's arguments plus admit_code (TM_ADMIT_*) and acl_rule
+ * (the matching rule's index, 0xFFFFFFFF without one; reported for refused
+ * publishes too).  A refused publish gets status TM_OK, its code, zero counts
+ * and NULL arrays; it appears in no plan, moves no cursor and draws no sticky
+ * entry.  tickets[] of the plan callbacks still lists every publish of the
+ * batch, so plan indices keep indexing it.  On a failed batch admit_code and
+ * acl_rule are 0 and 0xFFFFFFFF.
+ * TM_EINVAL at open: the flag without PUBLISH | OPTS; a NULL ac or zone table,
+ * n_zones outside 1..TM_ADMIT_MAX_ZONES; n_acl neither 0 nor the replica count;
+ * the plan flags and callbacks not matching as tm_batcher_open_plans asks.  The
+ * older opens return TM_EINVAL with TM_BATCHER_ADMIT set, the older submits on
+ * such a batcher, and this submit on any other.  TM_EINVAL at submit: a NULL
+ * callback or creds, a QoS of 3, a zone index >= n_zones, mount_len > len, a
+ * length with a NULL pointer or above 65535, a family that is none of 0, 4, 6.
+ * On a host-only engine every callback gets TM_EDEVICE. */
+typedef struct tm_admit_config {
+    const tm_zone_caps* zones;
+    uint32_t n_zones, n_acl;
+    tm_acl* const* acl;
+} tm_admit_config;
+typedef struct tm_pub_creds {
+    const uint8_t* client_id;
+    const uint8_t* username;
+    uint32_t client_len, user_len;
+    uint8_t client_defined, user_defined, peer_family, reserved;
+    uint8_t peer[16];
+} tm_pub_creds;
+typedef void (*tm_publish_admit_done_fn)(void* ctx, uint64_t ticket, int status, const tm_delivery* deliv,
+                                         const uint32_t* pick_word, uint32_t n_deliv, const tm_pair* pairs,
+                                         const uint32_t* pair_word, uint32_t n_pairs, uint32_t admit_code,
+                                         uint32_t acl_rule);
+int tm_batcher_open_admit(tm_engine* e, const tm_batcher_config* cfg, const tm_admit_config* ac,
+                          tm_inbox_done_fn inbox_fn, tm_forward_done_fn forward_fn, void* ctx, tm_batcher** out);
+int tm_batcher_submit_publish_admit(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t mount_len,
+                                    uint32_t pub_key, uint32_t pub_flags, uint32_t pub_admit, uint32_t pub_from,
+                                    const tm_pub_creds* creds, tm_publish_admit_done_fn done, void* ctx,
+                                    uint64_t* ticket_out);
 
 /* ---- batched topic-rewrite rule selection (rewrite.hip) -------
  * emqx_mod_rewrite:match_rule/2 (src/emqx_mod_rewrite.erl:52-59) applies the
