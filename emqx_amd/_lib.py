@@ -519,6 +519,9 @@ SIGNATURES = [
     ("tm_batcher_get_stats2", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                              ctypes.c_uint32]),
     ("tm_batcher_close", None, [ctypes.c_void_p]),
+    ("tm_debug_batcher_layout", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_uint32]),
     ("tm_acl_open", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     ("tm_acl_close", None, [ctypes.c_void_p]),
     ("tm_acl_rule_begin", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]),

@@ -8,8 +8,9 @@ routes, or (deliveries=True) aggre(match_routes/1): To ids + target ids, or
 their dispatch Count and $share pick, and the (To, subscriber) pairs; with
 round_robin=True the picks are the reference's default strategy, each lane a
 publisher process with its own cursors (sticky=True: `sticky` picks, a lane
-likewise a publisher with its own entries), and stream=True runs the keyed picks
-through tm_publish_stream_device too (an A/B switch); opts=True
+likewise a publisher with its own entries); every publish batcher runs the
+stream-ordered publish call, and stream=True (TM_BATCHER_STREAM, which once
+chose that call for the keyed picks) is accepted and changes nothing; opts=True
 (submit_publish_opts) brings the delivery word of every pair and of every
 $share pick with the records; inbox=callable (with publish=True, opts=True)
 opens the inbox mode (tm_batcher_open_inbox): per batch the callable gets the

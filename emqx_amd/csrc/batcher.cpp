@@ -29,12 +29,14 @@
 // TM_BATCHER_PUBLISH carries publish/1 up to the sends (src/emqx_broker.erl:
 // 148-157, 175-192; src/emqx_shared_sub.erl:89-111, 228-249): every submit
 // brings a pick key that travels with its topic through the chunks, the lane
-// runs tm_match_publish_batch_device(TM_SHARE_KEYED) and tm_publish_pack_device
-// and reads one packed block back -- header, both offset arrays, 16 B delivery
-// records, 8 B pairs -- which the callbacks read in place.  Keyed picks are
-// stateless, so a batch whose lists outgrew the lane's buffers is simply run
-// again; round robin is not offered because that rerun would advance the set
-// cursors twice.
+// copies one block up, runs the stream-ordered publish call
+// (tm_publish_stream_gated_device, which selects the plain call, the call with
+// options and the gate by its arguments) and reads one packed block back --
+// header, both offset arrays, 16 B delivery records, 8 B pairs -- which the
+// callbacks read in place.  Every strategy and every mode below takes this one
+// path; both blocks are described once, in batcher_layout.h.  The call stores
+// its cursors only when every stage fitted, so a batch whose lists outgrew the
+// lane's buffers is simply run again, round robin and sticky included.
 //
 // TM_BATCHER_OPTS adds the session side of every send (emqx_session:
 // handle_dispatch/3, src/emqx_session.erl:667-684): a submit also brings the
@@ -78,10 +80,24 @@
 #include <vector>
 
 #include "../../include/topicmatch.h"
+#include "batcher_layout.h"
 
 namespace {
 
+using batcher_layout::DownBlock;
+using batcher_layout::Modes;
+using batcher_layout::UpBlock;
 using clk = std::chrono::steady_clock;
+
+// the typed view of a block's piece: the one place an offset meets a pointer
+template <class T>
+inline T* at(void* base, uint64_t off) {
+    return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + off);
+}
+template <class T>
+inline const T* at(const void* base, uint64_t off) {
+    return reinterpret_cast<const T*>(static_cast<const uint8_t*>(base) + off);
+}
 constexpr int NSTRIPE = 16;
 // engine workspaces reserved at open: batches up to this many topics (a
 // 256K-topic flood batch) run without growing them; larger ones grow on demand
@@ -230,11 +246,11 @@ struct Lane {
     const uint32_t* r_src = nullptr;
     const uint32_t* r_dst = nullptr;
     double ids_per_topic = 64.0;      // sizing estimate of the device result buffers
-    // TM_BATCHER_PUBLISH: the publish call's planes, pairs and per-topic pair
-    // counts (its other outputs use the buffers above; the packed block is
-    // d_out / h_out), the batch's results as the callbacks read them, and the
-    // sizing estimates of both capacities
-    Dev d_planes, d_sub, d_scount;
+    // TM_BATCHER_PUBLISH: the block that goes up (h_io / d_io) as this batch's
+    // pack_publish laid it out, the batch's results as the callbacks read them
+    // (into h_out, the packed block; bind_results), and the sizing estimates of
+    // the delivery and pair capacities
+    UpBlock up{};
     const uint64_t* r_doff = nullptr;
     const uint64_t* r_soff = nullptr;
     const tm_delivery* r_deliv = nullptr;
@@ -242,10 +258,10 @@ struct Lane {
     const uint32_t* r_pickw = nullptr;   // TM_BATCHER_OPTS: the pick words (parallel to r_deliv) and the
     const uint32_t* r_pairw = nullptr;   // pair words (parallel to r_pairs)
     double deliv_per_topic = 16.0, pairs_per_topic = 16.0;
-    // TM_BATCHER_STREAM / TM_BATCHER_ROUND_ROBIN: tm_publish_stream_device's
-    // workspace, the two further sizing estimates (match ids: ids_per_topic
-    // above; ranked slots), the lane's cursor context -- a lane is a publisher
-    // process -- and the passes beyond this batch's first
+    // the stream-ordered publish call's workspace, the two further sizing
+    // estimates (match ids: ids_per_topic above; ranked slots), the lane's
+    // cursor context (TM_BATCHER_ROUND_ROBIN / TM_BATCHER_STICKY: a lane is a
+    // publisher process) and the passes beyond this batch's first
     Dev d_ws;
     double rr_per_topic = 16.0;
     tm_share_cursors* cursors = nullptr;
@@ -266,13 +282,9 @@ struct Lane {
     const uint64_t* r_fhdr = nullptr;
     const tm_forward_group* r_fgroups = nullptr;
     const uint32_t* r_fpub = nullptr;
-    // TM_BATCHER_ADMIT: the lane's rule set (its replica's; null: none), where the admission planes sit in
-    // the block that goes up (offsets into h_io / d_io; a_utoff = 0: no publish has a mountpoint, the ACL
-    // kernel reads the topics themselves) and the codes and rule indices as the callbacks read them
+    // TM_BATCHER_ADMIT: the lane's rule set (its replica's; null: none) and the codes and rule indices as
+    // the callbacks read them (the admission planes that go up: `up` above)
     tm_acl* acl = nullptr;
-    struct AdmitUp {
-        uint64_t mlen, padmit, coff, uoff, access, cdef, udef, fam, peers, cbytes, ubytes, utoff, utbytes, end;
-    } a_up{};
     const uint64_t* r_ahdr = nullptr;
     const uint32_t* r_rule = nullptr;
     const uint8_t* r_code = nullptr;
@@ -292,8 +304,7 @@ struct tm_batcher {
     tm_engine* eng = nullptr;
     tm_batcher_config cfg{};
     bool host_only = false;
-    bool publish = false;   // TM_BATCHER_PUBLISH
-    bool stream = false;    // ... through tm_publish_stream_device (TM_BATCHER_STREAM, TM_BATCHER_ROUND_ROBIN)
+    bool publish = false;   // TM_BATCHER_PUBLISH: the stream-ordered publish call, whatever the strategy
     bool round_robin = false;
     bool sticky = false;    // TM_BATCHER_STICKY: sticky picks, a context per lane as with round robin
     bool opts = false;      // TM_BATCHER_OPTS: tm_publish_stream_opts_device, records and pairs with their words
@@ -305,6 +316,7 @@ struct tm_batcher {
     tm_forward_done_fn ffn = nullptr;
     bool admit = false;     // TM_BATCHER_ADMIT: ACL check, admission and the gated call (tm_batcher_open_admit)
     std::vector<tm_zone_caps> zones;
+    Modes modes() const { return Modes{opts, inbox, forward, admit}; }   // what shapes a lane's two blocks
     Stripe stripes[NSTRIPE];
     std::atomic<bool> sealer_idle{false};   // the sealer sleeps with nothing pending: the next submit wakes it
     std::atomic<bool> force{false};         // flush: seal whatever is pending now
@@ -623,23 +635,35 @@ struct tm_batcher {
         return TM_OK;
     }
 
-    // TM_BATCHER_PUBLISH: [offsets (n+1) u64][keys n u32, padded to 8 B][bytes]
-    // in one pinned block, up in one copy.  TM_BATCHER_OPTS: pub_flags and
-    // pub_from (n u32 each, padded alike) between the keys and the bytes, in
-    // the same copy
-    static uint64_t keyb_of(uint32_t n) { return ((uint64_t)n * 4 + 7) & ~7ull; }
-    uint64_t upb_of(uint32_t n) const { return keyb_of(n) * (opts ? 3u : 1u); }   // the u32 planes that go up
+    // TM_BATCHER_PUBLISH: the batch into the lane's pinned copy of the block that
+    // goes up (batcher_layout.h, up_block): offsets, keys, with TM_BATCHER_OPTS
+    // pub_flags and pub_from, the topic bytes, and with TM_BATCHER_ADMIT the
+    // admission planes behind them, all in one copy.  The scan over the chunks
+    // gives the layout what only they know: the credential bytes of the batch and
+    // whether any publish has a mountpoint.  false: staging memory ran out
     bool pack_publish(Lane& L) {
-        uint64_t nb = 0;
+        uint64_t nb = 0, cb = 0, ub = 0, mounted = 0;
         for (const Chunk& c : L.chunks) nb += c.nbytes();
-        const uint64_t offb = ((uint64_t)L.n + 1) * 8, keyb = keyb_of(L.n), upb = upb_of(L.n);
-        if (admit) admit_up_layout(L, offb + upb + nb + 16, nb);
-        if (!L.h_io.ensure(admit ? L.a_up.end : offb + upb + nb + 16)) return false;
-        uint64_t* ho = (uint64_t*)L.h_io.p;
-        uint32_t* hk = (uint32_t*)((uint8_t*)L.h_io.p + offb);
-        uint32_t* hf = (uint32_t*)((uint8_t*)L.h_io.p + offb + keyb);
-        uint32_t* hr = (uint32_t*)((uint8_t*)L.h_io.p + offb + 2 * keyb);
-        uint8_t* hb = (uint8_t*)L.h_io.p + offb + upb;
+        if (admit)
+            for (const Chunk& c : L.chunks) {
+                const uint8_t* p = c.cred.data() + c.chead;
+                for (size_t j = c.head; j < c.lens.size(); ++j) {
+                    CredHead h;
+                    std::memcpy(&h, p, sizeof h);
+                    cb += h.client_len;
+                    ub += h.user_len;
+                    mounted |= c.mlen[j];
+                    p += c.crlen[j];
+                }
+            }
+        const UpBlock U = L.up = batcher_layout::up_block(modes(), L.n, nb, cb, ub, mounted != 0);
+        if (!L.h_io.ensure(U.end + 8)) return false;
+        void* base = L.h_io.p;
+        uint64_t* ho = at<uint64_t>(base, U.off);
+        uint32_t* hk = at<uint32_t>(base, U.key);
+        uint32_t* hf = at<uint32_t>(base, U.pflags);
+        uint32_t* hr = at<uint32_t>(base, U.pfrom);
+        uint8_t* hb = at<uint8_t>(base, U.bytes);
         uint64_t o = 0, k = 0;
         ho[0] = 0;
         for (const Chunk& c : L.chunks) {
@@ -657,55 +681,18 @@ struct tm_batcher {
         if (admit) pack_admit(L, ho, hb);
         return true;
     }
-    // TM_BATCHER_ADMIT: the admission planes behind the topic bytes, in the same pinned block and the same
-    // copy.  [mount_len][pub_admit] n u32 each; [client_off][user_off] (n+1) u64; [access][client_defined]
-    // [user_defined][family] n u8 each; [peers 16 n]; the client ids' and usernames' bytes; and, only when
-    // some publish has a mountpoint, the unmounted topics as a CSR of their own for the ACL kernel.
-    // Every piece starts on 8 bytes and the byte pieces end with 8 spare bytes.
-    void admit_up_layout(Lane& L, uint64_t at, uint64_t topic_bytes) const {
-        const uint64_t n = L.n, offb = (n + 1) * 8, keyb = keyb_of(L.n), n8 = (n + 7) & ~7ull;
-        uint64_t cb = 0, ub = 0, mounted = 0;
-        for (const Chunk& c : L.chunks) {
-            const uint8_t* p = c.cred.data() + c.chead;
-            for (size_t j = c.head; j < c.lens.size(); ++j) {
-                CredHead h;
-                std::memcpy(&h, p, sizeof h);
-                cb += h.client_len;
-                ub += h.user_len;
-                mounted |= c.mlen[j];
-                p += c.crlen[j];
-            }
-        }
-        Lane::AdmitUp& A = L.a_up;
-        auto take = [&](uint64_t bytes) {
-            const uint64_t o = at;
-            at += (bytes + 7) & ~7ull;
-            return o;
-        };
-        at = (at + 7) & ~7ull;
-        A.mlen = take(keyb);
-        A.padmit = take(keyb);
-        A.coff = take(offb);
-        A.uoff = take(offb);
-        A.access = take(n8);
-        A.cdef = take(n8);
-        A.udef = take(n8);
-        A.fam = take(n8);
-        A.peers = take(16 * n);
-        A.cbytes = take(cb + 8);
-        A.ubytes = take(ub + 8);
-        A.utoff = mounted ? take(offb) : 0;
-        A.utbytes = mounted ? take(topic_bytes + 8) : 0;
-        A.end = at + 8;
-    }
+    // TM_BATCHER_ADMIT: the admission planes of the block, from the publishes' credential records
     void pack_admit(Lane& L, const uint64_t* ho, const uint8_t* hb) {
-        const Lane::AdmitUp& A = L.a_up;
-        uint8_t* base = (uint8_t*)L.h_io.p;
-        uint32_t* ml = (uint32_t*)(base + A.mlen);
-        uint32_t* pa = (uint32_t*)(base + A.padmit);
-        uint64_t* co = (uint64_t*)(base + A.coff);
-        uint64_t* uo = (uint64_t*)(base + A.uoff);
-        uint64_t* to = A.utoff ? (uint64_t*)(base + A.utoff) : nullptr;
+        const UpBlock& U = L.up;
+        void* base = L.h_io.p;
+        uint32_t* ml = at<uint32_t>(base, U.mlen);
+        uint32_t* pa = at<uint32_t>(base, U.padmit);
+        uint64_t* co = at<uint64_t>(base, U.coff);
+        uint64_t* uo = at<uint64_t>(base, U.uoff);
+        uint64_t* to = U.utoff ? at<uint64_t>(base, U.utoff) : nullptr;
+        uint8_t *access = at<uint8_t>(base, U.access), *cdef = at<uint8_t>(base, U.cdef), *udef = at<uint8_t>(base, U.udef);
+        uint8_t *fam = at<uint8_t>(base, U.fam), *peers = at<uint8_t>(base, U.peers), *cbytes = at<uint8_t>(base, U.cbytes);
+        uint8_t *ubytes = at<uint8_t>(base, U.ubytes), *utbytes = at<uint8_t>(base, U.utbytes);
         uint64_t k = 0, c_at = 0, u_at = 0, t_at = 0;
         co[0] = uo[0] = 0;
         if (to) to[0] = 0;
@@ -716,364 +703,84 @@ struct tm_batcher {
                 std::memcpy(&h, p, sizeof h);
                 ml[k] = c.mlen[j];
                 pa[k] = c.padmit[j];
-                base[A.access + k] = (uint8_t)TM_ACL_PUBLISH;
-                base[A.cdef + k] = h.client_defined;
-                base[A.udef + k] = h.user_defined;
-                base[A.fam + k] = h.peer_family;
-                std::memcpy(base + A.peers + 16 * k, h.peer, 16);
-                if (h.client_len) std::memcpy(base + A.cbytes + c_at, p + sizeof h, h.client_len);
-                if (h.user_len) std::memcpy(base + A.ubytes + u_at, p + sizeof h + h.client_len, h.user_len);
+                access[k] = (uint8_t)TM_ACL_PUBLISH;
+                cdef[k] = h.client_defined;
+                udef[k] = h.user_defined;
+                fam[k] = h.peer_family;
+                std::memcpy(peers + 16 * k, h.peer, 16);
+                if (h.client_len) std::memcpy(cbytes + c_at, p + sizeof h, h.client_len);
+                if (h.user_len) std::memcpy(ubytes + u_at, p + sizeof h + h.client_len, h.user_len);
                 co[k + 1] = c_at += h.client_len;
                 uo[k + 1] = u_at += h.user_len;
                 if (to) {   // T as the client sent it: the topic behind its mountpoint
                     const uint64_t len = ho[k + 1] - ho[k] - c.mlen[j];
-                    if (len) std::memcpy(base + A.utbytes + t_at, hb + ho[k] + c.mlen[j], len);
+                    if (len) std::memcpy(utbytes + t_at, hb + ho[k] + c.mlen[j], len);
                     to[k + 1] = t_at += len;
                 }
                 p += c.crlen[j];
             }
         }
     }
-    // the packed block of a publish batch (device and pinned copies alike):
-    // [hdr 4 u64][doff (n+1) u64][sub_off (n+1) u64][deliveries cap x 16 B][pairs scap x 8 B];
-    // the head is a multiple of 16 B, so the records are aligned for their stores
-    static uint64_t pk_head(uint32_t n) { return 32 + 2 * ((uint64_t)n + 1) * 8; }
-    int run_publish(Lane& L, uint64_t& results) {
-        auto chk = [](hipError_t e) { return e == hipSuccess; };
-        const uint32_t n = L.n;
-        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), head = pk_head(n);
-        const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
-        if (!L.d_io.ensure(offb + keyb + nbytes + 16) || !L.d_counts.ensure((uint64_t)n * 4 + 4) ||
-            !L.d_scount.ensure((uint64_t)n * 4 + 4) || !L.d_outoff.ensure(offb) || !L.d_total.ensure(64))
-            return TM_ENOMEM;
-        hipStream_t s = L.stream;
-        clk::time_point t0 = clk::now();
-        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, offb + keyb + nbytes + 8, hipMemcpyHostToDevice, s)))
-            return TM_EDEVICE;
-        const uint64_t* d_off = (const uint64_t*)L.d_io.p;
-        const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
-        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + keyb;
-        uint64_t* d_total = (uint64_t*)L.d_total.p;   // [0] route total, [1] pair total
-        uint64_t cap = (uint64_t)(L.deliv_per_topic * n * 1.25) + 1024;
-        uint64_t scap = (uint64_t)(L.pairs_per_topic * n * 1.25) + 1024;
-        const bool eager = n <= EAGER_TOPICS;
-        // a second pass when the batch did not fit; a third only when the first
-        // also dropped deliveries, whose pairs its header could not count
-        for (int pass = 0; pass < 3; ++pass) {
-            if (pass) t0 = clk::now();
-            const uint64_t outb = head + cap * 16 + scap * 8;
-            if (!L.d_planes.ensure(cap * 16) || !L.d_sub.ensure(scap * 8) || !L.d_out.ensure(outb) ||
-                !L.h_out.ensure(eager ? outb : head))
-                return TM_ENOMEM;
-            uint32_t* pl = (uint32_t*)L.d_planes.p;   // to, target, ndisp, pick
-            uint32_t* sp = (uint32_t*)L.d_sub.p;      // sub_to, sub_id
-            uint8_t* d = (uint8_t*)L.d_out.p;
-            uint64_t* d_soff = (uint64_t*)(d + 32 + offb);
-            int rc = tm_match_publish_batch_device(eng, d_bytes, d_off, n, nbytes, (uint32_t*)L.d_counts.p,
-                                                   (uint64_t*)L.d_outoff.p, pl, pl + cap, pl + 2 * cap, cap, d_total,
-                                                   (uint32_t*)L.d_scount.p, d_soff, sp, sp + scap, scap, d_total + 1,
-                                                   TM_SHARE_KEYED, d_key, pl + 3 * cap, s);
-            if (rc != TM_OK) return rc;
-            rc = tm_publish_pack_device(eng, n, (const uint32_t*)L.d_counts.p, (const uint64_t*)L.d_outoff.p, pl,
-                                        pl + cap, pl + 2 * cap, pl + 3 * cap, cap, d_total, d_soff, sp, sp + scap,
-                                        scap, d_total + 1, (uint64_t*)d, (uint64_t*)(d + 32), (tm_delivery*)(d + head),
-                                        cap, (tm_pair*)(d + head + cap * 16), scap, s);
-            if (rc != TM_OK) return rc;
-            // header and offsets; a small batch also reads its records back
-            // speculatively (up to the capacities) in the same round trip
-            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? outb : head, hipMemcpyDeviceToHost, s)))
-                return TM_EDEVICE;
-            L.launch_ns += ns_since(t0);
-            t0 = clk::now();
-            if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
-            L.sync_ns += ns_since(t0);
-            const uint8_t* h = (const uint8_t*)L.h_out.p;
-            const uint64_t* hdr = (const uint64_t*)h;
-            const uint64_t rtotal = hdr[0], ptotal = hdr[1], D = hdr[2], P = hdr[3];
-            if (rtotal <= cap) {   // else the pair total covers the deliveries kept only
-                L.deliv_per_topic = 0.9 * L.deliv_per_topic + 0.1 * ((double)rtotal / n);
-                L.pairs_per_topic = 0.9 * L.pairs_per_topic + 0.1 * ((double)ptotal / n);
-            }
-            if (rtotal <= cap && ptotal <= scap && D <= cap && P <= scap) {
-                if (!eager) {   // exactly D deliveries and P pairs
-                    if (!L.h_out.ensure(outb)) return TM_ENOMEM;   // may move: the head is read again below
-                    t0 = clk::now();
-                    if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, head + D * 16, hipMemcpyDeviceToHost, s)) ||
-                        (P && !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + head + cap * 16, d + head + cap * 16, P * 8,
-                                                  hipMemcpyDeviceToHost, s))) ||
-                        !chk(hipStreamSynchronize(s)))
-                        return TM_EDEVICE;
-                    L.sync_ns += ns_since(t0);
-                    h = (const uint8_t*)L.h_out.p;
-                }
-                L.r_doff = (const uint64_t*)(h + 32);
-                L.r_soff = (const uint64_t*)(h + 32 + offb);
-                L.r_deliv = (const tm_delivery*)(h + head);
-                L.r_pairs = (const tm_pair*)(h + head + cap * 16);
-                results = D;
-                return TM_OK;
-            }
-            if (rtotal > cap) cap = rtotal + rtotal / 4 + 1024;   // overflow: rerun with room (rare)
-            if (ptotal > scap) scap = ptotal + ptotal / 4 + 1024;
-        }
-        return TM_EDEVICE;
-    }
 
-    // The same batch through tm_publish_stream_device: one call, no host wait
-    // inside it.  The packed block grows by the header's four further words:
-    // [hdr 8 u64][doff (n+1) u64][sub_off (n+1) u64][deliveries][pairs].  The
-    // four capacities follow running means (ids, routes, pairs, ranked slots per
-    // topic); on state != 0 the capacity the header names grows to its exact
-    // total with a quarter of slack and the batch runs again: no cursor moved,
-    // so the rerun picks what a first run would have.  At worst one rerun per
-    // stage.
-    static uint64_t ps_head(uint32_t n) { return 64 + 2 * ((uint64_t)n + 1) * 8; }
+    // The batch through the stream-ordered publish call: one call, no host wait
+    // inside it.  The four capacities follow running means (ids, routes, pairs,
+    // ranked slots per topic); on state != 0 the capacity the header names grows
+    // to its exact total with a quarter of slack and the batch runs again: no
+    // cursor moved, so the rerun picks what a first run would have.  At worst one
+    // rerun per stage.
     static uint64_t cap_of(double per_topic, uint64_t n) { return (uint64_t)(per_topic * n * 1.25) + 1024; }
     tm_publish_caps stream_caps(const Lane& L, uint64_t n) const {
         return tm_publish_caps{cap_of(L.ids_per_topic, n), cap_of(L.deliv_per_topic, n), cap_of(L.pairs_per_topic, n),
                                (round_robin || sticky) ? cap_of(L.rr_per_topic, n) : 0};
     }
-    // The packed block of a stream batch.  Without TM_BATCHER_INBOX:
-    //   [hdr][doff][sub_off][deliveries cap x 16 B][pairs scap x 8 B][pick words cap x 4 B][pair words scap x 4 B]
-    // and all of it comes back (backb = outb).  With it the pairs and the pair
-    // words move behind what comes back, and the plan takes their place:
-    //   [hdr][doff][sub_off][deliveries][pick words][plan hdr 8 u64][records ecap x 16 B][ent_pub][ent_to]
-    //   [ent_word] | [pairs][pair words],   ecap = cap + scap (every send fits: no plan state 3 or 4)
-    // TM_BATCHER_FORWARD adds the forward plan at the end of what comes back (before the `|`):
-    //   [plan hdr 8 u64][groups cap x 16 B][pub cap x 4 B]   (pub_cap = group_cap = cap: no plan state 3 or 4)
-    struct BlockLayout {
-        uint64_t o_pairs, o_pickw, o_pairw, o_ihdr, o_inbox, o_epub, o_eto, o_ewd, backb, outb, ecap;
-        uint64_t o_fhdr, o_fgroups, o_fpub;
-        uint64_t o_ahdr, o_rule, o_code, o_aclres, a_back;   // TM_BATCHER_ADMIT; a_back: the bytes from o_ahdr that come back
+    // one pass of a batch over the device: its capacities, the packed block they
+    // shape (batcher_layout.h, down_block) and the three workspace needs
+    struct Pass {
+        uint32_t n;
+        uint64_t nbytes;
+        bool eager;   // a batch of up to EAGER_TOPICS reads everything back with the header, up to the capacities
+        tm_publish_caps caps;
+        DownBlock B;
+        uint64_t wsb, iwsb, fwsb;
     };
-    // the forward plan from `at` on; returns its end
-    uint64_t forward_layout(BlockLayout& B, uint64_t at, uint64_t cap) const {
-        if (!forward) return at;
-        B.o_fhdr = (at + 15) & ~15ull;
-        B.o_fgroups = B.o_fhdr + 8 * TM_FORWARD_STREAM_HDR_WORDS;
-        B.o_fpub = B.o_fgroups + cap * 16;
-        return B.o_fpub + cap * 4;
+    static constexpr uint64_t IHDR = 8 * TM_INBOX_STREAM_HDR_WORDS, FHDR = 8 * TM_FORWARD_STREAM_HDR_WORDS;   // plan headers, bytes
+    static bool copied(hipError_t e) { return e == hipSuccess; }
+    static bool down(const Lane& L, uint64_t off, uint64_t bytes) {   // a piece of the packed block into its pinned copy
+        return !bytes || copied(hipMemcpyAsync(at<uint8_t>(L.h_out.p, off), at<uint8_t>(L.d_out.p, off), bytes,
+                                               hipMemcpyDeviceToHost, L.stream));
     }
-    // the admission outputs from `at` on, in what comes back: [admit hdr 8 u64][rule n u32][code n u8], and
-    // the ACL results behind them; returns the end
-    uint64_t admit_layout(BlockLayout& B, uint64_t at, uint32_t n) const {
-        if (!admit) return at;
-        B.o_ahdr = (at + 15) & ~15ull;
-        B.o_rule = B.o_ahdr + 64;
-        B.o_code = B.o_rule + keyb_of(n);
-        B.o_aclres = B.o_code + (((uint64_t)n + 7) & ~7ull);
-        B.a_back = B.o_aclres - B.o_ahdr;
-        return B.o_aclres + (((uint64_t)n + 7) & ~7ull);
-    }
-    BlockLayout block_layout(uint32_t n, uint64_t cap, uint64_t scap) const {
-        BlockLayout B{};
-        const uint64_t head = ps_head(n), wb = opts ? 4 : 0;
-        if (!inbox) {
-            B.o_pairs = head + cap * 16;
-            B.o_pickw = B.o_pairs + scap * 8;
-            B.o_pairw = B.o_pickw + cap * wb;
-            B.outb = B.backb = admit_layout(B, forward_layout(B, B.o_pairw + scap * wb, cap), n);
-            return B;
-        }
-        B.ecap = cap + scap;
-        B.o_pickw = head + cap * 16;
-        B.o_ihdr = (B.o_pickw + cap * 4 + 15) & ~15ull;
-        B.o_inbox = B.o_ihdr + 8 * TM_INBOX_STREAM_HDR_WORDS;
-        B.o_epub = B.o_inbox + B.ecap * 16;
-        B.o_eto = B.o_epub + B.ecap * 4;
-        B.o_ewd = B.o_eto + B.ecap * 4;
-        B.o_pairs = B.backb = (admit_layout(B, forward_layout(B, B.o_ewd + B.ecap * 4, cap), n) + 15) & ~15ull;
-        B.o_pairw = B.o_pairs + scap * 8;
-        B.outb = B.o_pairw + scap * 4;
-        return B;
-    }
+
     int run_publish_stream(Lane& L, uint64_t& results) {
-        auto chk = [](hipError_t e) { return e == hipSuccess; };
         const uint32_t n = L.n;
-        const uint64_t offb = ((uint64_t)n + 1) * 8, keyb = keyb_of(n), upb = upb_of(n), head = ps_head(n);
-        const uint64_t nbytes = ((const uint64_t*)L.h_io.p)[n];
-        const uint64_t upbytes = admit ? L.a_up.end : offb + upb + nbytes + 8;   // one block, one copy
-        if (!L.d_io.ensure(upbytes + 8)) return TM_ENOMEM;
-        hipStream_t s = L.stream;
+        Pass P{n, at<uint64_t>(L.h_io.p, L.up.off)[n], n <= EAGER_TOPICS, stream_caps(L, n), {}, 0, 0, 0};
+        if (!L.d_io.ensure(L.up.end + 8)) return TM_ENOMEM;
         clk::time_point t0 = clk::now();
-        if (!chk(hipMemcpyAsync(L.d_io.p, L.h_io.p, upbytes, hipMemcpyHostToDevice, s)))
+        if (!copied(hipMemcpyAsync(L.d_io.p, L.h_io.p, L.up.end, hipMemcpyHostToDevice, L.stream)))   // one block, one copy
             return TM_EDEVICE;
-        const uint64_t* d_off = (const uint64_t*)L.d_io.p;
-        const uint32_t* d_key = (const uint32_t*)((const uint8_t*)L.d_io.p + offb);
-        const uint8_t* d_bytes = (const uint8_t*)L.d_io.p + offb + upb;
-        // TM_BATCHER_OPTS: the publishes' words went up with the keys, and the block
-        // that comes back grows by the two word planes (block_layout)
-        tm_deliver dv{};
-        dv.pub_flags = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + keyb);
-        dv.pub_from = (const uint32_t*)((const uint8_t*)L.d_io.p + offb + 2 * keyb);
-        dv.flags = upgrade ? TM_DELIVER_UPGRADE_QOS : 0u;
-        const uint32_t strategy = round_robin ? TM_SHARE_ROUND_ROBIN : sticky ? TM_SHARE_STICKY : TM_SHARE_KEYED;
-        tm_publish_caps caps = stream_caps(L, n);
-        const bool eager = n <= EAGER_TOPICS;
         for (int pass = 0; pass < 5; ++pass) {
             if (pass) {
                 t0 = clk::now();
                 ++L.reruns;
             }
-            const uint64_t cap = caps.routes, scap = caps.pairs;
-            const BlockLayout B = block_layout(n, cap, scap);
-            const uint64_t o_pairs = B.o_pairs, o_pickw = B.o_pickw, o_pairw = B.o_pairw, outb = B.outb;
-            const uint64_t backb = B.backb, ecap = B.ecap;
-            const uint64_t iwsb = inbox ? tm_inbox_plan_stream_workspace_bytes(n, cap, scap, ecap) : 0;
-            if (inbox && (!iwsb || !L.d_iws.ensure(iwsb) || !L.h_out.ensure(backb))) return iwsb ? TM_ENOMEM : TM_ERANGE;
-            const uint64_t wsb = opts ? tm_publish_stream_opts_workspace_bytes(eng, n, nbytes, &caps)
-                                      : tm_publish_stream_workspace_bytes(eng, n, nbytes, &caps);
-            if (!wsb) return TM_ERANGE;
-            const uint64_t fwsb = forward ? tm_forward_plan_stream_workspace_bytes(n, cap, cap) : 0;
-            if (forward && (!fwsb || !L.d_fws.ensure(fwsb))) return fwsb ? TM_ENOMEM : TM_ERANGE;
-            if (!L.d_ws.ensure(wsb) || !L.d_out.ensure(outb) || !L.h_out.ensure(eager ? backb : head)) return TM_ENOMEM;
-            uint8_t* d = (uint8_t*)L.d_out.p;
-            dv.sub_deliver = (uint32_t*)(d + o_pairw);
-            // the plan over the outputs on the device, behind the publish call on the lane's stream
-            auto plan = [&]() {
-                return tm_inbox_plan_stream_device(
-                    eng, n, (const uint64_t*)d, (const uint64_t*)(d + 64), (const uint64_t*)(d + 64 + offb),
-                    (const tm_delivery*)(d + head), (const uint32_t*)(d + o_pickw), cap, (const tm_pair*)(d + o_pairs),
-                    (const uint32_t*)(d + o_pairw), scap, L.sub_bits, L.d_iws.p, iwsb, (uint64_t*)(d + B.o_ihdr),
-                    (tm_inbox*)(d + B.o_inbox), ecap, (uint32_t*)(d + B.o_epub), (uint32_t*)(d + B.o_eto),
-                    (uint32_t*)(d + B.o_ewd), ecap, s);
-            };
-            if (admit) {   // the ACL check and the admission in front of the publish call: pure, so a rerun repeats them
-                const Lane::AdmitUp& A = L.a_up;
-                const uint8_t* u = (const uint8_t*)L.d_io.p;
-                uint32_t* d_rule = (uint32_t*)(d + B.o_rule);
-                int8_t* d_acl = (int8_t*)(d + B.o_aclres);
-                int arc = TM_OK;
-                if (L.acl)
-                    arc = tm_acl_check_batch_device(
-                        L.acl, n, u + A.access, A.utoff ? u + A.utbytes : d_bytes,
-                        A.utoff ? (const uint64_t*)(u + A.utoff) : d_off, u + A.cbytes, (const uint64_t*)(u + A.coff),
-                        u + A.cdef, u + A.ubytes, (const uint64_t*)(u + A.uoff), u + A.udef, u + A.peers, u + A.fam,
-                        d_acl, d_rule, s);
-                else if (!chk(hipMemsetAsync(d_rule, 0xFF, (uint64_t)n * 4, s)))   // no rule set: no rule matched
-                    return TM_EDEVICE;
-                if (arc != TM_OK) return arc;
-                arc = tm_admit_batch_device(d_bytes, d_off, n, (const uint32_t*)(u + A.mlen), dv.pub_flags,
-                                            (const uint32_t*)(u + A.padmit), zones.data(), (uint32_t)zones.size(),
-                                            L.acl ? d_acl : nullptr, d + B.o_code, (uint64_t*)(d + B.o_ahdr), s);
-                if (arc != TM_OK) return arc;
-            }
-            const int rc =
-                admit ? tm_publish_stream_gated_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
-                                                       L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
-                                                       (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                       (tm_pair*)(d + o_pairs), &dv, (uint32_t*)(d + o_pickw),
-                                                       d + B.o_code, s) :
-                opts ? tm_publish_stream_opts_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
-                                                     L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
-                                                     (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                     (tm_pair*)(d + o_pairs), &dv, (uint32_t*)(d + o_pickw), s)
-                     : tm_publish_stream_device(eng, d_bytes, d_off, n, nbytes, strategy, d_key, L.cursors, &caps,
-                                                L.d_ws.p, wsb, (uint64_t*)d, (uint64_t*)(d + 64),
-                                                (uint64_t*)(d + 64 + offb), (tm_delivery*)(d + head),
-                                                (tm_pair*)(d + o_pairs), s);
+            int rc = enqueue_pass(L, P);
             if (rc != TM_OK) return rc;
-            if (inbox) {
-                const int prc = plan();
-                if (prc != TM_OK) return prc;
-            }
-            if (forward) {   // behind the publish call and the inbox plan; never again without them
-                const int frc = tm_forward_plan_stream_device(
-                    eng, n, (const uint64_t*)d, (const uint64_t*)(d + 64), (const tm_delivery*)(d + head), cap,
-                    L.d_fws.p, fwsb, (uint64_t*)(d + B.o_fhdr), (tm_forward_group*)(d + B.o_fgroups), cap,
-                    (uint32_t*)(d + B.o_fpub), cap, s);
-                if (frc != TM_OK) return frc;
-            }
-            // a small batch: everything up to backb (without TM_BATCHER_INBOX the whole block) in one copy
-            if (((inbox || forward) && !eager && !L.h_out.ensure(backb))) return TM_ENOMEM;
-            if (!chk(hipMemcpyAsync(L.h_out.p, L.d_out.p, eager ? backb : head, hipMemcpyDeviceToHost, s)) ||
-                (inbox && !eager &&
-                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, 64, hipMemcpyDeviceToHost, s))) ||
-                (forward && !eager &&
-                 !chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_fhdr, d + B.o_fhdr, 64, hipMemcpyDeviceToHost, s))))
-                return TM_EDEVICE;
             L.launch_ns += ns_since(t0);
             t0 = clk::now();
-            if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
+            if (!copied(hipStreamSynchronize(L.stream))) return TM_EDEVICE;
             L.sync_ns += ns_since(t0);
-            const uint8_t* h = (const uint8_t*)L.h_out.p;
-            const uint64_t* hdr = (const uint64_t*)h;
-            const uint64_t state = hdr[6], D = hdr[2], P = hdr[3];
+            const uint64_t* hdr = at<uint64_t>(L.h_out.p, P.B.hdr);
+            const uint64_t state = hdr[6], D = hdr[2], pairs = hdr[3];
             // the totals the header holds exactly: every stage up to the one named
             auto mean = [n](double& m, uint64_t total) { m = 0.9 * m + 0.1 * ((double)total / n); };
             mean(L.ids_per_topic, hdr[4]);
             if (state == 0 || state >= 2) mean(L.deliv_per_topic, hdr[0]);
             if (state == 0 || state >= 3) mean(L.pairs_per_topic, hdr[1]);
             if ((round_robin || sticky) && (state == 0 || state == 4)) mean(L.rr_per_topic, hdr[5]);
-            if (state == 0) {
-                // TM_BATCHER_INBOX: a plan that met an id wider than the lane's sort width (plan state 2)
-                // runs again alone, at the width its header reports; the publish call is NOT repeated.
-                // ent_cap = inbox_cap = cap + scap: the plan states 3 and 4 cannot occur
-                for (int ipass = 0; inbox; ++ipass) {
-                    const uint64_t* ih = (const uint64_t*)(h + B.o_ihdr);
-                    if (ih[6] == 0) break;
-                    if (ih[6] != 2 || ipass) return TM_EDEVICE;
-                    uint32_t bits = 0;
-                    while (bits < 32 && (ih[4] >> bits)) ++bits;
-                    L.sub_bits = bits;
-                    ++L.reruns;
-                    t0 = clk::now();
-                    const int prc = plan();
-                    if (prc != TM_OK) return prc;
-                    if (!chk(hipMemcpyAsync((uint8_t*)L.h_out.p + B.o_ihdr, d + B.o_ihdr, eager ? backb - B.o_ihdr : 64,
-                                            hipMemcpyDeviceToHost, s)))
-                        return TM_EDEVICE;
-                    L.launch_ns += ns_since(t0);
-                    t0 = clk::now();
-                    if (!chk(hipStreamSynchronize(s))) return TM_EDEVICE;
-                    L.sync_ns += ns_since(t0);
-                }
-                if (!eager) {   // exactly D deliveries and P pairs (TM_BATCHER_INBOX: S records and E entries, no pairs)
-                    if (!L.h_out.ensure(backb)) return TM_ENOMEM;   // may move: the head is read again below
-                    const uint64_t* ih = inbox ? (const uint64_t*)((const uint8_t*)L.h_out.p + B.o_ihdr) : nullptr;
-                    const uint64_t E = inbox ? ih[0] : 0, S = inbox ? ih[1] : 0;
-                    const uint64_t* fh = forward ? (const uint64_t*)((const uint8_t*)L.h_out.p + B.o_fhdr) : nullptr;
-                    const uint64_t FM = forward ? fh[0] : 0, FG = forward ? fh[1] : 0;
-                    auto down = [&](uint64_t o, uint64_t bytes) {
-                        return !bytes || chk(hipMemcpyAsync((uint8_t*)L.h_out.p + o, d + o, bytes, hipMemcpyDeviceToHost, s));
-                    };
-                    t0 = clk::now();
-                    if (!down(0, head + D * 16) || (!inbox && !down(o_pairs, P * 8)) || (opts && !down(o_pickw, D * 4)) ||
-                        (opts && !inbox && !down(o_pairw, P * 4)) ||
-                        (inbox && (!down(B.o_ihdr, 64 + S * 16) || !down(B.o_epub, E * 4) || !down(B.o_eto, E * 4) ||
-                                   !down(B.o_ewd, E * 4))) ||
-                        (forward && (!down(B.o_fhdr, 64 + FG * 16) || !down(B.o_fpub, FM * 4))) ||
-                        (admit && !down(B.o_ahdr, B.a_back)) || !chk(hipStreamSynchronize(s)))
-                        return TM_EDEVICE;
-                    L.sync_ns += ns_since(t0);
-                    h = (const uint8_t*)L.h_out.p;
-                }
-                L.r_pickw = (const uint32_t*)(h + o_pickw);
-                L.r_pairw = inbox ? nullptr : (const uint32_t*)(h + o_pairw);
-                L.r_doff = (const uint64_t*)(h + 64);
-                L.r_soff = (const uint64_t*)(h + 64 + offb);
-                L.r_deliv = (const tm_delivery*)(h + head);
-                L.r_pairs = inbox ? nullptr : (const tm_pair*)(h + o_pairs);
-                if (inbox) {
-                    L.r_ihdr = (const uint64_t*)(h + B.o_ihdr);
-                    L.r_inbox = (const tm_inbox*)(h + B.o_inbox);
-                    L.r_epub = (const uint32_t*)(h + B.o_epub);
-                    L.r_eto = (const uint32_t*)(h + B.o_eto);
-                    L.r_ewd = (const uint32_t*)(h + B.o_ewd);
-                }
-                if (forward) {
-                    L.r_fhdr = (const uint64_t*)(h + B.o_fhdr);
-                    if (L.r_fhdr[6] != 0) return TM_EDEVICE;   // pub_cap = group_cap = cap: a publish state of 0 leaves none
-                    L.r_fgroups = (const tm_forward_group*)(h + B.o_fgroups);
-                    L.r_fpub = (const uint32_t*)(h + B.o_fpub);
-                }
-                if (admit) {
-                    L.r_ahdr = (const uint64_t*)(h + B.o_ahdr);
-                    L.r_rule = (const uint32_t*)(h + B.o_rule);
-                    L.r_code = h + B.o_code;
-                }
+            if (state == 0) {   // (a round-robin or sticky publish has stored its cursors: never rerun for a plan)
+                if (inbox && (rc = rerun_inbox_plan(L, P)) != TM_OK) return rc;
+                if (!P.eager && (rc = fetch_exact(L, P, D, pairs)) != TM_OK) return rc;
                 results = D;
-                return TM_OK;
+                return bind_results(L, P.B);
             }
             // the stage that overflowed: its capacity from the exact total, and its
             // mean raised to this batch's at once (a mean that creeps up by a tenth
@@ -1082,13 +789,180 @@ struct tm_batcher {
                 cap = total + total / 4 + 1024;
                 m = std::max(m, (double)total / n);
             };
-            if (state == 1) grown(caps.ids, L.ids_per_topic, hdr[4]);
-            else if (state == 2) grown(caps.routes, L.deliv_per_topic, hdr[0]);
-            else if (state == 3) grown(caps.pairs, L.pairs_per_topic, hdr[1]);
-            else if (state == 4) grown(caps.rr, L.rr_per_topic, hdr[5]);
+            if (state == 1) grown(P.caps.ids, L.ids_per_topic, hdr[4]);
+            else if (state == 2) grown(P.caps.routes, L.deliv_per_topic, hdr[0]);
+            else if (state == 3) grown(P.caps.pairs, L.pairs_per_topic, hdr[1]);
+            else if (state == 4) grown(P.caps.rr, L.rr_per_topic, hdr[5]);
             else return TM_EDEVICE;
         }
         return TM_EDEVICE;
+    }
+    // the pass's packed block and workspaces, sized by its capacities, and room for them
+    int size_pass(Lane& L, Pass& P) {
+        const uint64_t cap = P.caps.routes, scap = P.caps.pairs;
+        const DownBlock& B = P.B = batcher_layout::down_block(modes(), P.n, cap, scap);
+        P.iwsb = inbox ? tm_inbox_plan_stream_workspace_bytes(P.n, cap, scap, B.ecap) : 0;
+        if (inbox && (!P.iwsb || !L.d_iws.ensure(P.iwsb) || !L.h_out.ensure(B.backb))) return P.iwsb ? TM_ENOMEM : TM_ERANGE;
+        P.wsb = opts ? tm_publish_stream_opts_workspace_bytes(eng, P.n, P.nbytes, &P.caps)
+                     : tm_publish_stream_workspace_bytes(eng, P.n, P.nbytes, &P.caps);
+        if (!P.wsb) return TM_ERANGE;
+        P.fwsb = forward ? tm_forward_plan_stream_workspace_bytes(P.n, cap, cap) : 0;
+        if (forward && (!P.fwsb || !L.d_fws.ensure(P.fwsb))) return P.fwsb ? TM_ENOMEM : TM_ERANGE;
+        if (!L.d_ws.ensure(P.wsb) || !L.d_out.ensure(B.outb) || !L.h_out.ensure(P.eager ? B.backb : B.deliv)) return TM_ENOMEM;
+        return TM_OK;
+    }
+    // One pass on the lane's stream, with no wait between its parts: the ACL check and the admission
+    // (TM_BATCHER_ADMIT), the publish call, the inbox plan, the forward plan, and the first copy down --
+    // a small batch: everything up to backb (without TM_BATCHER_INBOX the whole block); a large one:
+    // the head and the plans' headers, which size its exact fetch.
+    // tm_publish_stream_gated_device is the one publish entry: without options `deliver` and the pick
+    // words are NULL, which selects tm_publish_stream_device; without admission d_code is NULL, which
+    // leaves the call selected ungated -- both bit for bit the other two entries (topicmatch.h).
+    int enqueue_pass(Lane& L, Pass& P) {
+        int rc = size_pass(L, P);
+        if (rc != TM_OK) return rc;
+        const DownBlock& B = P.B;
+        const UpBlock& U = L.up;
+        const void* u = L.d_io.p;
+        void* d = L.d_out.p;
+        tm_deliver dv{};
+        if (opts) {   // the publishes' words went up with the keys; the pair words go where the block keeps them
+            dv.pub_flags = at<uint32_t>(u, U.pflags);
+            dv.pub_from = at<uint32_t>(u, U.pfrom);
+            dv.sub_deliver = at<uint32_t>(d, B.pairw);
+            dv.flags = upgrade ? TM_DELIVER_UPGRADE_QOS : 0u;
+        }
+        if (admit && (rc = enqueue_admission(L, P)) != TM_OK) return rc;
+        const uint32_t strategy = round_robin ? TM_SHARE_ROUND_ROBIN : sticky ? TM_SHARE_STICKY : TM_SHARE_KEYED;
+        rc = tm_publish_stream_gated_device(
+            eng, at<uint8_t>(u, U.bytes), at<uint64_t>(u, U.off), P.n, P.nbytes, strategy, at<uint32_t>(u, U.key), L.cursors,
+            &P.caps, L.d_ws.p, P.wsb, at<uint64_t>(d, B.hdr), at<uint64_t>(d, B.doff), at<uint64_t>(d, B.sub_off),
+            at<tm_delivery>(d, B.deliv), at<tm_pair>(d, B.pairs), opts ? &dv : nullptr,
+            opts ? at<uint32_t>(d, B.pickw) : nullptr, admit ? at<uint8_t>(d, B.code) : nullptr, L.stream);
+        if (rc != TM_OK) return rc;
+        if (inbox && (rc = enqueue_inbox_plan(L, P)) != TM_OK) return rc;
+        if (forward) {   // behind the publish call and the inbox plan; never again without them
+            const uint64_t cap = P.caps.routes;
+            rc = tm_forward_plan_stream_device(eng, P.n, at<uint64_t>(d, B.hdr), at<uint64_t>(d, B.doff),
+                                               at<tm_delivery>(d, B.deliv), cap, L.d_fws.p, P.fwsb, at<uint64_t>(d, B.fhdr),
+                                               at<tm_forward_group>(d, B.fgroups), cap, at<uint32_t>(d, B.fpub), cap,
+                                               L.stream);
+            if (rc != TM_OK) return rc;
+        }
+        if ((inbox || forward) && !P.eager && !L.h_out.ensure(B.backb)) return TM_ENOMEM;
+        if (!down(L, B.hdr, P.eager ? B.backb : B.deliv) || (inbox && !P.eager && !down(L, B.ihdr, IHDR)) ||
+            (forward && !P.eager && !down(L, B.fhdr, FHDR)))
+            return TM_EDEVICE;
+        return TM_OK;
+    }
+    // the ACL check and the admission in front of the publish call: pure, so a rerun repeats them
+    int enqueue_admission(Lane& L, const Pass& P) {
+        const DownBlock& B = P.B;
+        const UpBlock& U = L.up;
+        const void* u = L.d_io.p;
+        void* d = L.d_out.p;
+        const uint8_t* d_bytes = at<uint8_t>(u, U.bytes);
+        const uint64_t* d_off = at<uint64_t>(u, U.off);
+        uint32_t* d_rule = at<uint32_t>(d, B.rule);
+        int8_t* d_acl = at<int8_t>(d, B.aclres);
+        int rc = TM_OK;
+        if (L.acl)   // on the topics as the clients sent them: the CSR of their own when some publish has a mountpoint
+            rc = tm_acl_check_batch_device(L.acl, P.n, at<uint8_t>(u, U.access), U.utoff ? at<uint8_t>(u, U.utbytes) : d_bytes,
+                                           U.utoff ? at<uint64_t>(u, U.utoff) : d_off, at<uint8_t>(u, U.cbytes),
+                                           at<uint64_t>(u, U.coff), at<uint8_t>(u, U.cdef), at<uint8_t>(u, U.ubytes),
+                                           at<uint64_t>(u, U.uoff), at<uint8_t>(u, U.udef), at<uint8_t>(u, U.peers),
+                                           at<uint8_t>(u, U.fam), d_acl, d_rule, L.stream);
+        else if (!copied(hipMemsetAsync(d_rule, 0xFF, (uint64_t)P.n * 4, L.stream)))   // no rule set: no rule matched
+            return TM_EDEVICE;
+        if (rc != TM_OK) return rc;
+        return tm_admit_batch_device(d_bytes, d_off, P.n, at<uint32_t>(u, U.mlen), at<uint32_t>(u, U.pflags),
+                                     at<uint32_t>(u, U.padmit), zones.data(), (uint32_t)zones.size(),
+                                     L.acl ? d_acl : nullptr, at<uint8_t>(d, B.code), at<uint64_t>(d, B.ahdr), L.stream);
+    }
+    // the inbox plan over the publish call's outputs on the device, behind it on the lane's stream
+    int enqueue_inbox_plan(Lane& L, const Pass& P) {
+        const DownBlock& B = P.B;
+        void* d = L.d_out.p;
+        return tm_inbox_plan_stream_device(eng, P.n, at<uint64_t>(d, B.hdr), at<uint64_t>(d, B.doff), at<uint64_t>(d, B.sub_off),
+                                           at<tm_delivery>(d, B.deliv), at<uint32_t>(d, B.pickw), P.caps.routes,
+                                           at<tm_pair>(d, B.pairs), at<uint32_t>(d, B.pairw), P.caps.pairs, L.sub_bits,
+                                           L.d_iws.p, P.iwsb, at<uint64_t>(d, B.ihdr), at<tm_inbox>(d, B.inbox), B.ecap,
+                                           at<uint32_t>(d, B.epub), at<uint32_t>(d, B.eto), at<uint32_t>(d, B.ewd), B.ecap,
+                                           L.stream);
+    }
+    // TM_BATCHER_INBOX: a plan that met an id wider than the lane's sort width (plan state 2) runs again
+    // alone, at the width its header reports, over the outputs still on the device; the publish call is
+    // NOT repeated.  ent_cap = inbox_cap = cap + scap: the plan states 3 and 4 cannot occur
+    int rerun_inbox_plan(Lane& L, const Pass& P) {
+        const DownBlock& B = P.B;
+        for (int ipass = 0;; ++ipass) {
+            const uint64_t* ih = at<uint64_t>(L.h_out.p, B.ihdr);
+            if (ih[6] == 0) return TM_OK;
+            if (ih[6] != 2 || ipass) return TM_EDEVICE;
+            uint32_t bits = 0;
+            while (bits < 32 && (ih[4] >> bits)) ++bits;
+            L.sub_bits = bits;
+            ++L.reruns;
+            clk::time_point t0 = clk::now();
+            const int rc = enqueue_inbox_plan(L, P);
+            if (rc != TM_OK) return rc;
+            if (!down(L, B.ihdr, P.eager ? B.backb - B.ihdr : IHDR)) return TM_EDEVICE;
+            L.launch_ns += ns_since(t0);
+            t0 = clk::now();
+            if (!copied(hipStreamSynchronize(L.stream))) return TM_EDEVICE;
+            L.sync_ns += ns_since(t0);
+        }
+    }
+    // a large batch, once its headers are here: exactly D deliveries and `pairs` pairs with their words
+    // (TM_BATCHER_INBOX: S records and E entries, no pairs), the forward plan's G groups and M indices,
+    // the admission header, rules and codes
+    int fetch_exact(Lane& L, const Pass& P, uint64_t D, uint64_t pairs) {
+        const DownBlock& B = P.B;
+        if (!L.h_out.ensure(B.backb)) return TM_ENOMEM;   // may move: the head comes down again below
+        const uint64_t* ih = at<uint64_t>(L.h_out.p, B.ihdr);
+        const uint64_t E = inbox ? ih[0] : 0, S = inbox ? ih[1] : 0;
+        const uint64_t* fh = at<uint64_t>(L.h_out.p, B.fhdr);
+        const uint64_t FM = forward ? fh[0] : 0, FG = forward ? fh[1] : 0;
+        const clk::time_point t0 = clk::now();
+        if (!down(L, B.hdr, B.deliv + D * 16) || (!inbox && !down(L, B.pairs, pairs * 8)) ||
+            (opts && !down(L, B.pickw, D * 4)) || (opts && !inbox && !down(L, B.pairw, pairs * 4)) ||
+            (inbox && (!down(L, B.ihdr, IHDR + S * 16) || !down(L, B.epub, E * 4) || !down(L, B.eto, E * 4) ||
+                       !down(L, B.ewd, E * 4))) ||
+            (forward && (!down(L, B.fhdr, FHDR + FG * 16) || !down(L, B.fpub, FM * 4))) ||
+            (admit && !down(L, B.ahdr, B.a_back)) || !copied(hipStreamSynchronize(L.stream)))
+            return TM_EDEVICE;
+        L.sync_ns += ns_since(t0);
+        return TM_OK;
+    }
+    // the batch's results as the callbacks read them, in the pinned copy of the packed block: the one
+    // binding, after the one-copy read-back and after the exact fetch alike
+    int bind_results(Lane& L, const DownBlock& B) {
+        const void* h = L.h_out.p;
+        L.r_doff = at<uint64_t>(h, B.doff);
+        L.r_soff = at<uint64_t>(h, B.sub_off);
+        L.r_deliv = at<tm_delivery>(h, B.deliv);
+        L.r_pickw = opts ? at<uint32_t>(h, B.pickw) : nullptr;
+        L.r_pairs = inbox ? nullptr : at<tm_pair>(h, B.pairs);   // TM_BATCHER_INBOX: the pairs stay on the device
+        L.r_pairw = opts && !inbox ? at<uint32_t>(h, B.pairw) : nullptr;
+        if (inbox) {
+            L.r_ihdr = at<uint64_t>(h, B.ihdr);
+            L.r_inbox = at<tm_inbox>(h, B.inbox);
+            L.r_epub = at<uint32_t>(h, B.epub);
+            L.r_eto = at<uint32_t>(h, B.eto);
+            L.r_ewd = at<uint32_t>(h, B.ewd);
+        }
+        if (forward) {
+            L.r_fhdr = at<uint64_t>(h, B.fhdr);
+            if (L.r_fhdr[6] != 0) return TM_EDEVICE;   // pub_cap = group_cap = cap: a publish state of 0 leaves none
+            L.r_fgroups = at<tm_forward_group>(h, B.fgroups);
+            L.r_fpub = at<uint32_t>(h, B.fpub);
+        }
+        if (admit) {
+            L.r_ahdr = at<uint64_t>(h, B.ahdr);
+            L.r_rule = at<uint32_t>(h, B.rule);
+            L.r_code = at<uint8_t>(h, B.code);
+        }
+        return TM_OK;
     }
 
     // callbacks of topics [lo, hi) of lane L's batch (gather order)
@@ -1206,7 +1080,7 @@ struct tm_batcher {
             if (rc == TM_OK && n && publish) {
                 const bool packed = pack_publish(L);
                 t_packed = clk::now();
-                rc = !packed ? TM_ENOMEM : stream ? run_publish_stream(L, results) : run_publish(L, results);
+                rc = packed ? run_publish_stream(L, results) : TM_ENOMEM;
                 t_dev = clk::now();
             } else if (rc == TM_OK && n) {
                 const bool packed = pack(L, routes);
@@ -1363,12 +1237,19 @@ struct tm_batcher {
 };
 
 namespace {
-// one topic into the calling thread's stripe (pub_key: TM_BATCHER_PUBLISH only)
+// what a publish brings beside its topic: the pick key (TM_BATCHER_PUBLISH), the message's words
+// (TM_BATCHER_OPTS), and its credentials, mount length and admission word (TM_BATCHER_ADMIT)
+struct PubExtras {
+    bool publish = false;
+    uint32_t pub_key = 0;
+    bool opts = false;
+    uint32_t pub_flags = 0, pub_from = 0;
+    const tm_pub_creds* creds = nullptr;
+    uint32_t mount_len = 0, pub_admit = 0;
+};
+// one topic into the calling thread's stripe
 inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_t* topic, uint32_t len, Req r,
-                                                     bool publish, uint32_t pub_key, uint64_t* ticket_out,
-                                                     bool opts = false, uint32_t pub_flags = 0,
-                                                     uint32_t pub_from = 0, const tm_pub_creds* creds = nullptr,
-                                                     uint32_t mount_len = 0, uint32_t pub_admit = 0) {
+                                                     const PubExtras& x, uint64_t* ticket_out) {
     if (t_stripe < 0) t_stripe = (int)(g_stripe_rr.fetch_add(1, std::memory_order_relaxed) % NSTRIPE);
     Stripe& s = b->stripes[t_stripe];
     uint64_t t, was;
@@ -1379,12 +1260,12 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
         s.cur.lens.push_back(len);
         r.ticket = t;
         s.cur.reqs.push_back(r);
-        if (publish) s.cur.keys.push_back(pub_key);
-        if (opts) {   // TM_BATCHER_OPTS
-            s.cur.pflags.push_back(pub_flags);
-            s.cur.pfrom.push_back(pub_from);
+        if (x.publish) s.cur.keys.push_back(x.pub_key);
+        if (x.opts) {   // TM_BATCHER_OPTS
+            s.cur.pflags.push_back(x.pub_flags);
+            s.cur.pfrom.push_back(x.pub_from);
         }
-        if (creds) {   // TM_BATCHER_ADMIT: the credentials copied as one record
+        if (const tm_pub_creds* creds = x.creds) {   // TM_BATCHER_ADMIT: the credentials copied as one record
             CredHead h{};
             h.client_len = creds->client_len;
             h.user_len = creds->user_len;
@@ -1397,8 +1278,8 @@ inline __attribute__((always_inline)) int submit_one(tm_batcher* b, const uint8_
             if (h.client_len) s.cur.cred.insert(s.cur.cred.end(), creds->client_id, creds->client_id + h.client_len);
             if (h.user_len) s.cur.cred.insert(s.cur.cred.end(), creds->username, creds->username + h.user_len);
             s.cur.crlen.push_back((uint32_t)sizeof h + h.client_len + h.user_len);
-            s.cur.mlen.push_back(mount_len);
-            s.cur.padmit.push_back(pub_admit);
+            s.cur.mlen.push_back(x.mount_len);
+            s.cur.padmit.push_back(x.pub_admit);
         }
         // the counters change only under the stripe lock: plain load + store
         // (no read-modify-write per publish); the 0 -> 1 step is seq_cst for
@@ -1427,7 +1308,14 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
                         void* ictx, tm_batcher** out, const tm_admit_config* ac = nullptr) {
     if (!e || !out) return TM_EINVAL;
     if (ac && (ac->n_acl != 0 && (int)ac->n_acl != tm_engine_replicas(e)) && tm_engine_replicas(e) > 0) return TM_EINVAL;
-    tm_batcher* b = new (std::nothrow) tm_batcher();
+    // whatever way the open fails, the lanes made so far are shut down before the batcher goes
+    struct Closer {
+        void operator()(tm_batcher* p) const {
+            if (!p->lanes.empty()) p->shutdown_lanes();
+            delete p;
+        }
+    };
+    std::unique_ptr<tm_batcher, Closer> b(new (std::nothrow) tm_batcher());
     if (!b) return TM_ENOMEM;
     b->eng = e;
     if (cfg) b->cfg = *cfg;
@@ -1441,48 +1329,29 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
     if (b->cfg.deadline_us == 0) b->cfg.deadline_us = 200;
     if (b->cfg.eager_us == 0) b->cfg.eager_us = 40;   // profiles/r05_f/latency.jsonl
     b->publish = (b->cfg.flags & TM_BATCHER_PUBLISH) != 0;
-    if (b->publish && (b->cfg.flags & (TM_BATCHER_ROUTES | TM_BATCHER_DELIVERIES | TM_BATCHER_CSR))) {
-        delete b;
-        return TM_EINVAL;
-    }
-    if (!b->publish && (b->cfg.flags & (TM_BATCHER_ROUND_ROBIN | TM_BATCHER_STREAM | TM_BATCHER_STICKY))) {
-        delete b;
-        return TM_EINVAL;
-    }
-    if ((b->cfg.flags & TM_BATCHER_STICKY) && (b->cfg.flags & TM_BATCHER_ROUND_ROBIN)) {   // one strategy
-        delete b;
-        return TM_EINVAL;
-    }
+    if (b->publish && (b->cfg.flags & (TM_BATCHER_ROUTES | TM_BATCHER_DELIVERIES | TM_BATCHER_CSR))) return TM_EINVAL;
+    // (TM_BATCHER_STREAM: accepted with TM_BATCHER_PUBLISH, where it changes nothing -- every publish lane
+    // takes the stream-ordered call)
+    if (!b->publish && (b->cfg.flags & (TM_BATCHER_ROUND_ROBIN | TM_BATCHER_STREAM | TM_BATCHER_STICKY))) return TM_EINVAL;
+    if ((b->cfg.flags & TM_BATCHER_STICKY) && (b->cfg.flags & TM_BATCHER_ROUND_ROBIN)) return TM_EINVAL;   // one strategy
     if (((b->cfg.flags & TM_BATCHER_OPTS) && !b->publish) ||
-        ((b->cfg.flags & TM_BATCHER_UPGRADE_QOS) && !(b->cfg.flags & TM_BATCHER_OPTS))) {
-        delete b;
+        ((b->cfg.flags & TM_BATCHER_UPGRADE_QOS) && !(b->cfg.flags & TM_BATCHER_OPTS)))
         return TM_EINVAL;
-    }
     b->round_robin = (b->cfg.flags & TM_BATCHER_ROUND_ROBIN) != 0;
     b->sticky = (b->cfg.flags & TM_BATCHER_STICKY) != 0;
     b->opts = (b->cfg.flags & TM_BATCHER_OPTS) != 0;
     b->upgrade = (b->cfg.flags & TM_BATCHER_UPGRADE_QOS) != 0;
     b->admit = ac != nullptr;
     if (ac) b->zones.assign(ac->zones, ac->zones + ac->n_zones);
-    // an options lane takes one path, the stream-ordered call, for keyed picks too
-    // (and a forward lane: its plan reads the stream-ordered call's packed records)
-    b->stream = b->round_robin || b->sticky || b->opts || b->forward || (b->cfg.flags & TM_BATCHER_STREAM) != 0;
     const uint32_t per = b->cfg.lanes_per_replica ? b->cfg.lanes_per_replica : 2u;
     const int R = tm_engine_replicas(e);
     b->host_only = R == 0;
     std::vector<int32_t> devs(R > 0 ? R : 1, -1);
-    if (R > 0 && tm_engine_devices(e, devs.data(), (uint32_t)R) != R) {
-        delete b;
-        return TM_EDEVICE;
-    }
+    if (R > 0 && tm_engine_devices(e, devs.data(), (uint32_t)R) != R) return TM_EDEVICE;
     // lanes round-robin over the replicas: lane k on replica k % R
     for (uint32_t k = 0; k < per * (uint32_t)devs.size(); ++k) {
         std::unique_ptr<Lane> L(new (std::nothrow) Lane());
-        if (!L) {
-            b->shutdown_lanes();
-            delete b;
-            return TM_ENOMEM;
-        }
+        if (!L) return TM_ENOMEM;
         L->device = devs[k % devs.size()];
         if (ac && ac->n_acl && ac->acl && R > 0) L->acl = ac->acl[k % devs.size()];   // its replica's rule set
         // normal priority (A/B: TM_BATCHER_PRIO=1 makes the lanes
@@ -1497,17 +1366,12 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
             (hipSetDevice(L->device) != hipSuccess ||
              (prio ? (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
                       hipStreamCreateWithPriority(&L->stream, hipStreamNonBlocking, greatest) != hipSuccess)
-                   : hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking) != hipSuccess))) {
-            b->shutdown_lanes();
-            delete b;
+                   : hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking) != hipSuccess)))
             return TM_EDEVICE;
-        }
         // a lane is a publisher process: its own dictionary (cursors and sticky entries) on its replica
         if ((b->round_robin || b->sticky) && L->device >= 0 &&
             tm_share_cursors_open(e, k % (uint32_t)devs.size(), &L->cursors) != TM_OK) {
             if (L->stream) (void)hipStreamDestroy(L->stream);
-            b->shutdown_lanes();
-            delete b;
             return TM_EDEVICE;
         }
         b->lanes.push_back(std::move(L));
@@ -1527,28 +1391,22 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
         (void)tm_reserve(e, (uint32_t)eng, eng * 64);
         for (auto& L : b->lanes) {
             if (L->device < 0 || hipSetDevice(L->device) != hipSuccess) continue;
-            if (b->stream) {   // the first batch's four capacities
+            if (b->publish) {
+                // the first batch's four capacities and both of its blocks, at nominal sizes per publish: a
+                // 64 B topic and, with TM_BATCHER_ADMIT, a 64 B client id, a 64 B username and no mountpoint
+                // (172 B of admission planes per publish)
                 const tm_publish_caps c = b->stream_caps(*L, pre);
-                const uint64_t io = offb + b->upb_of((uint32_t)pre) + nbytes + 16 + (b->admit ? pre * 160 : 0);
-                const tm_batcher::BlockLayout B = b->block_layout((uint32_t)pre, c.routes, c.pairs);
+                const uint64_t cred = b->admit ? pre * 64 : 0;
+                const UpBlock U = batcher_layout::up_block(b->modes(), (uint32_t)pre, nbytes, cred, cred, false);
+                const DownBlock B = batcher_layout::down_block(b->modes(), (uint32_t)pre, c.routes, c.pairs);
                 if (b->inbox)
                     (void)L->d_iws.ensure(tm_inbox_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.pairs, B.ecap));
                 if (b->forward)
                     (void)L->d_fws.ensure(tm_forward_plan_stream_workspace_bytes((uint32_t)pre, c.routes, c.routes));
-                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_out.ensure(B.outb) && L->h_out.ensure(B.backb) &&
+                (void)(L->h_io.ensure(U.end + 8) && L->d_io.ensure(U.end + 8) && L->d_out.ensure(B.outb) &&
+                       L->h_out.ensure(B.backb) &&
                        L->d_ws.ensure(b->opts ? tm_publish_stream_opts_workspace_bytes(e, (uint32_t)pre, nbytes, &c)
                                               : tm_publish_stream_workspace_bytes(e, (uint32_t)pre, nbytes, &c)));
-                continue;
-            }
-            if (b->publish) {   // the first batch's capacities (Lane::deliv_per_topic, pairs_per_topic)
-                const uint64_t pcap = (uint64_t)(L->deliv_per_topic * pre * 1.25) + 1024;
-                const uint64_t scap = (uint64_t)(L->pairs_per_topic * pre * 1.25) + 1024;
-                const uint64_t io = offb + tm_batcher::keyb_of((uint32_t)pre) + nbytes + 16;
-                const uint64_t outb = tm_batcher::pk_head((uint32_t)pre) + pcap * 16 + scap * 8;
-                (void)(L->h_io.ensure(io) && L->d_io.ensure(io) && L->d_counts.ensure(pre * 4 + 4) &&
-                       L->d_scount.ensure(pre * 4 + 4) && L->d_outoff.ensure(offb) && L->d_total.ensure(64) &&
-                       L->d_planes.ensure(pcap * 16) && L->d_sub.ensure(scap * 8) && L->d_out.ensure(outb) &&
-                       L->h_out.ensure(outb));
                 continue;
             }
             (void)(L->h_io.ensure(offb + nbytes + 16) && L->d_io.ensure(offb + nbytes + 16) &&
@@ -1560,20 +1418,19 @@ static int batcher_open(tm_engine* e, const tm_batcher_config* cfg, tm_inbox_don
         }
     }
     try {
-        for (Stripe& x : b->stripes) x.cur = b->spare();
-        for (size_t k = 0; k < b->lanes.size(); ++k) {
-            b->free_lanes.push_back((int)(b->lanes.size() - 1 - k));   // lane 0 first
-            b->lanes[k]->th = std::thread([b, k] { b->lane_loop(*b->lanes[k], (int)k); });
+        tm_batcher* const p = b.get();
+        for (Stripe& x : p->stripes) x.cur = p->spare();
+        for (size_t k = 0; k < p->lanes.size(); ++k) {
+            p->free_lanes.push_back((int)(p->lanes.size() - 1 - k));   // lane 0 first
+            p->lanes[k]->th = std::thread([p, k] { p->lane_loop(*p->lanes[k], (int)k); });
         }
-        for (uint32_t k = 0; k < std::min<uint32_t>(b->cfg.callback_threads, 256u); ++k)
-            b->cb_threads.emplace_back([b] { b->cb_loop(); });
-        b->worker = std::thread([b] { b->loop(); });
+        for (uint32_t k = 0; k < std::min<uint32_t>(p->cfg.callback_threads, 256u); ++k)
+            p->cb_threads.emplace_back([p] { p->cb_loop(); });
+        p->worker = std::thread([p] { p->loop(); });
     } catch (...) {
-        b->shutdown_lanes();
-        delete b;
         return TM_ENOMEM;
     }
-    *out = b;
+    *out = b.release();
     return TM_OK;
 }
 
@@ -1618,7 +1475,7 @@ int tm_batcher_submit(tm_batcher* b, const uint8_t* topic, uint32_t len, tm_batc
     r.fn = fn;
     r.ctx = ctx;
     r.ticket = 0;
-    return submit_one(b, topic, len, r, false, 0, ticket_out);
+    return submit_one(b, topic, len, r, PubExtras{}, ticket_out);
 }
 
 int tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
@@ -1628,7 +1485,7 @@ int tm_batcher_submit_publish(tm_batcher* b, const uint8_t* topic, uint32_t len,
     r.pfn = fn;
     r.ctx = ctx;
     r.ticket = 0;
-    return submit_one(b, topic, len, r, true, pub_key, ticket_out);
+    return submit_one(b, topic, len, r, PubExtras{true, pub_key}, ticket_out);
 }
 
 int tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t pub_key,
@@ -1639,7 +1496,7 @@ int tm_batcher_submit_publish_opts(tm_batcher* b, const uint8_t* topic, uint32_t
     r.ofn = fn;
     r.ctx = ctx;
     r.ticket = 0;
-    return submit_one(b, topic, len, r, true, pub_key, ticket_out, true, pub_flags, pub_from);
+    return submit_one(b, topic, len, r, PubExtras{true, pub_key, true, pub_flags, pub_from}, ticket_out);
 }
 
 int tm_batcher_submit_publish_admit(tm_batcher* b, const uint8_t* topic, uint32_t len, uint32_t mount_len,
@@ -1656,7 +1513,8 @@ int tm_batcher_submit_publish_admit(tm_batcher* b, const uint8_t* topic, uint32_
     r.afn = fn;
     r.ctx = ctx;
     r.ticket = 0;
-    return submit_one(b, topic, len, r, true, pub_key, ticket_out, true, pub_flags, pub_from, creds, mount_len, pub_admit);
+    return submit_one(b, topic, len, r, PubExtras{true, pub_key, true, pub_flags, pub_from, creds, mount_len, pub_admit},
+                      ticket_out);
 }
 
 int tm_batcher_flush(tm_batcher* b) {
@@ -1695,6 +1553,22 @@ void tm_batcher_close(tm_batcher* b) {
     if (b->worker.joinable()) b->worker.join();
     b->shutdown_lanes();
     delete b;
+}
+
+// diagnostic: both descriptions of a publish lane's blocks (batcher_layout.h) for the modes in `flags`
+// (TM_BATCHER_OPTS, _INBOX, _FORWARD, _ADMIT), every field in declaration order: the 19 of UpBlock,
+// then the 23 of DownBlock (tests/test_batcher_layout.py, tools/san_batcher.cpp)
+int tm_debug_batcher_layout(uint32_t flags, uint32_t n, uint64_t cap, uint64_t scap, uint64_t topic_bytes,
+                            uint64_t client_bytes, uint64_t user_bytes, int mounted, uint64_t* out, uint32_t out_words) {
+    constexpr size_t up_words = sizeof(UpBlock) / 8, down_words = sizeof(DownBlock) / 8;
+    if (!out || out_words < up_words + down_words) return TM_EINVAL;
+    const Modes m{(flags & TM_BATCHER_OPTS) != 0, (flags & TM_BATCHER_INBOX) != 0, (flags & TM_BATCHER_FORWARD) != 0,
+                  (flags & TM_BATCHER_ADMIT) != 0};
+    const UpBlock U = batcher_layout::up_block(m, n, topic_bytes, client_bytes, user_bytes, mounted != 0);
+    const DownBlock B = batcher_layout::down_block(m, n, cap, scap);
+    std::memcpy(out, &U, sizeof U);   // both are structs of u64 alone
+    std::memcpy(out + up_words, &B, sizeof B);
+    return TM_OK;
 }
 
 }  // extern "C"

@@ -1486,18 +1486,24 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
  *
  * TM_BATCHER_PUBLISH: the batch is publish/1 up to the sends
  * (src/emqx_broker.erl:148-157, 175-192; src/emqx_shared_sub.erl:89-111,
- * 228-249).  A lane copies bytes, offsets and keys up, runs
- * tm_match_publish_batch_device and tm_publish_pack_device on its stream and
- * reads the packed block back: header, offsets and -- for batches of up to
- * 32768 topics in the same round trip, up to the lane's capacities -- the
- * records; a larger batch reads the header first, then exactly D deliveries
- * and P pairs.  The capacities follow two running means (deliveries and pairs
- * per topic); a batch that did not fit is rerun with capacities taken from
- * its header (once more when the first run also dropped deliveries, whose
- * pairs its header could not count).  The pick strategy is TM_SHARE_KEYED with
- * the pub_key of each submit: `hash` with phash2(ClientId), `random` with a
- * fresh draw.  Keyed picks are stateless, so a rerun returns what a first run
- * would have.
+ * 228-249).  A lane copies offsets, keys and bytes up in one block, runs the
+ * stream-ordered publish call on its stream -- tm_publish_stream_gated_device,
+ * whose arguments select tm_publish_stream_device here, the call with options
+ * under TM_BATCHER_OPTS and the gate under TM_BATCHER_ADMIT -- and reads the
+ * packed block back: header, offsets and -- for batches of up to 32768 topics
+ * in the same copy and the same stream synchronisation, up to the lane's
+ * capacities -- the records; a larger batch reads the header first, then
+ * exactly D deliveries and P pairs.  Every strategy and every mode below takes
+ * this one path.  The call's capacities follow four running means (match ids,
+ * routes, pairs and ranked slots per topic; workspace and both blocks reserved
+ * at open for the first batch); when the header's state names a stage, that
+ * capacity grows to the exact total it reports (plus a quarter) and the batch
+ * runs again, at worst once per stage.  The pick strategy is TM_SHARE_KEYED
+ * with the pub_key of each submit: `hash` with phash2(ClientId), `random` with
+ * a fresh draw.  A rerun returns what a first run would have, and
+ * tm_batcher_stats.reruns counts it.  tm_match_publish_batch_device and
+ * tm_publish_pack_device, which this mode ran at first, compute the same
+ * records and stay in the engine as the batch API.
  * TM_BATCHER_ROUND_ROBIN (with TM_BATCHER_PUBLISH, else tm_batcher_open:
  * TM_EINVAL): the picks are `round_robin`, the reference's default strategy
  * (emqx_shared_sub:strategy/0, src/emqx_shared_sub.erl:113-115), and pub_key
@@ -1505,21 +1511,16 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
  * reference keeps its counters (:243-249): each lane opens one
  * tm_share_cursors on its replica and closes it with the batcher, and the
  * batches of one lane count on from each other; with lanes_per_replica = 1 on
- * one GPU the batcher is one publisher.  Such a batcher runs
- * tm_publish_stream_device, whose capacities follow four running means (match
- * ids, routes, pairs and ranked slots per topic; workspace and outputs
- * reserved at open for the first batch); when the header's state names a
- * stage, that capacity grows to the exact total it reports (plus a quarter)
- * and the batch runs again, at worst once per stage.  The rule that makes this
- * safe replaces the old refusal: the call stores its new cursors in its last
- * kernel and only when every stage fitted, so a batch that is rerun has not
- * moved any cursor and its rerun picks what a first run would have.  The
- * read-back is as above: header, offsets and (small batches) records in one
- * copy and one stream synchronisation per pass.
- * TM_BATCHER_STREAM (with TM_BATCHER_PUBLISH, else TM_EINVAL): a keyed batcher
- * runs tm_publish_stream_device instead of the two calls above and returns
- * the same records.  An A/B switch like TM_BATCHER_CSR, not a tuning knob: the
- * next change keeps one of the two keyed paths, on the measurements.
+ * one GPU the batcher is one publisher.  caps.rr bounds the slots round robin
+ * ranks.  What makes the rerun above safe here: the call stores its new
+ * cursors in its last kernel and only when every stage fitted, so a batch that
+ * is rerun has not moved any cursor and its rerun picks what a first run would
+ * have.
+ * TM_BATCHER_STREAM (with TM_BATCHER_PUBLISH, else TM_EINVAL): no effect.  The
+ * flag once chose between two device paths of the keyed batcher; the
+ * stream-ordered call was the faster one in every measurement and
+ * is now the only one.  It stays defined and accepted so that callers that set
+ * it still open.
  * TM_BATCHER_STICKY (with TM_BATCHER_PUBLISH and without
  * TM_BATCHER_ROUND_ROBIN, else TM_EINVAL): the picks are `sticky`
  * (src/emqx_shared_sub.erl:211-224) with the pub_key of each submit.  As with
@@ -1550,7 +1551,7 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
 #define TM_BATCHER_EAGER_TOPICS 256u
 #define TM_BATCHER_PUBLISH 16u   /* results are publish/1 up to the sends: deliveries with Count and pick, and the pairs */
 #define TM_BATCHER_ROUND_ROBIN 32u   /* publish mode: round-robin picks, one cursor context per lane */
-#define TM_BATCHER_STREAM 64u   /* publish mode: keyed picks through tm_publish_stream_device (A/B) */
+#define TM_BATCHER_STREAM 64u   /* publish mode: accepted, no effect (every publish batcher runs the stream-ordered call) */
 #define TM_BATCHER_STICKY 128u   /* publish mode: sticky picks, one context per lane */
 /* TM_BATCHER_OPTS (with TM_BATCHER_PUBLISH): the records and the pairs come
  * with their delivery words (tm_deliver, tm_share_pick_words): every send
@@ -1598,7 +1599,7 @@ int tm_share_pick_batch(tm_engine* e, uint32_t strategy, tm_share_cursors* curso
 /* TM_BATCHER_FORWARD (with TM_BATCHER_PUBLISH, through tm_batcher_open_plans
  * only): the batch's remote-node deliveries reach the caller grouped per
  * receiving node.  A lane runs the stream-ordered publish call whatever the
- * strategy (keyed picks included, as TM_BATCHER_STREAM), then
+ * strategy, then
  * tm_inbox_plan_stream_device when TM_BATCHER_INBOX is set, then
  * tm_forward_plan_stream_device, all on its stream with no wait between them,
  * and reads the forward plan (header, groups, pub) back with the rest of the

@@ -586,7 +586,13 @@ def test_batcher_four_lanes_flood(world, gpu_device):
         per = [hits[tp].get(m, 0) for m in w.sh.tab[(grp, to)]]
         # each lane's own cursor leaves its members at most 1 apart, and the lanes' counts add
         assert sum(per) == topics.count(tp) and max(per) - min(per) <= lanes, (tp, per)
-    # the keyed batcher through the new call returns what the existing keyed batcher returns, ticket for ticket
-    old = flood(Batcher(w.e, max_topics=700, deadline_us=200, publish=True, lanes_per_replica=lanes))
-    new = flood(Batcher(w.e, max_topics=700, deadline_us=200, publish=True, stream=True, lanes_per_replica=lanes))
-    assert old == new and all(x[0] == 0 for x in old)
+    # the keyed batcher, with and without the flag that once chose its device path, returns ticket for ticket what
+    # the batch API (tm_match_publish_batch_device) gives that topic with that key
+    from publish_util import slices
+    bb, bo = pack(topics)
+    out = slices(w.e.match_publish_batch(bb, bo, Engine.SHARE_KEYED, np.asarray(keys, dtype=np.uint32)), len(topics))
+    for b in (Batcher(w.e, max_topics=700, deadline_us=200, publish=True, lanes_per_replica=lanes),
+              Batcher(w.e, max_topics=700, deadline_us=200, publish=True, stream=True, lanes_per_replica=lanes)):
+        got = flood(b)
+        for t in range(len(topics)):
+            assert got[t] == (0, out[t][0], out[t][1]), t

@@ -16,10 +16,9 @@ Per batch: device_us split into launch_us and sync_us, and packed_bytes, the
 header, offsets and records a publish batch brings back (a batch of up to
 32768 topics reads up to its capacities instead, about 1.25 x + 24 KiB).
 --legs deliveries runs on a commit without the publish mode (the baseline).
-Two further legs ride the publish leg's workload: publish_stream, the same
-keyed picks through tm_publish_stream_device (TM_BATCHER_STREAM), and
-publish_rr, round robin with one cursor context per lane
-(TM_BATCHER_ROUND_ROBIN); every leg reports its reruns.
+One further leg rides the publish leg's workload: publish_rr, round robin
+with one cursor context per lane (TM_BATCHER_ROUND_ROBIN); both run the
+stream-ordered publish call, and every leg reports its reruns.
 
 Run: python tools/bench_batcher.py --publish [--topics 1000000 --rate 1e6 --rounds 3 --out FILE]"""
 import argparse
@@ -38,7 +37,7 @@ from emqx_amd import workload as W  # noqa: E402
 
 
 NODE = b"emqx@node00"
-LEGS = {"deliveries": 0, "publish": 1, "publish_stream": 2, "publish_rr": 3}   # tools/ubench/pubdrive.cpp
+LEGS = {"deliveries": 0, "publish": 1, "publish_rr": 2}   # tools/ubench/pubdrive.cpp
 GROUPS = [b"grp%d" % i for i in range(8)]
 HOT = [b"hot0", b"hot1"]
 
@@ -115,7 +114,7 @@ def publish_main(a):
                                       "callbacks_us": res[12], "results": results},
                         "reruns": int(res[14])}
                 if leg != "deliveries":    # header + both offset arrays + 16 B records + 8 B pairs
-                    line["per_batch"]["packed_bytes"] = (32 if leg == "publish" else 64) + 16 * (mean_batch + 1) + 16 * results + \
+                    line["per_batch"]["packed_bytes"] = 64 + 16 * (mean_batch + 1) + 16 * results + \
                         8 * res[8] * mean_batch
                 else:                   # total + counts + offsets + To ids + target ids
                     line["per_batch"]["result_bytes"] = 8 + 4 * mean_batch + 8 * (mean_batch + 1) + 8 * results
@@ -132,7 +131,7 @@ def publish_main(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--publish", action="store_true", help="deliveries and publish batchers on the C2 publish world")
-    ap.add_argument("--legs", default="deliveries,publish,publish_stream,publish_rr")
+    ap.add_argument("--legs", default="deliveries,publish,publish_rr")
     ap.add_argument("--runs", default="flood,paced")
     ap.add_argument("--rate", type=float, default=1e6)
     ap.add_argument("--secs", type=float, default=1.0)

@@ -11,7 +11,8 @@
 // null arrays and zero counts, then that batch's per-publish callbacks) and the flag combinations its two open calls refuse;
 // the forward mode (tm_batcher_open_plans: the open-call rules of all three
 // open calls, and per batch the inbox callback if any, the forward callback,
-// then the per-publish callbacks, each with TM_EDEVICE and no arrays).  Build
+// then the per-publish callbacks, each with TM_EDEVICE and no arrays); the
+// lane's block layouts (tm_debug_batcher_layout) over the CPU test's cases.  Build
 // and run: make san_batcher (host code under -fsanitize=address,undefined; the
 // kernels are linked as built, never run).
 #include <atomic>
@@ -236,6 +237,30 @@ static void forward_phase() {
     forward_run(true);
 }
 
+// both descriptions of a publish lane's blocks (emqx_amd/csrc/batcher_layout.h) over the cases of
+// tests/test_batcher_layout.py, so that their arithmetic runs under UBSan; the values are that test's business
+extern "C" int tm_debug_batcher_layout(uint32_t flags, uint32_t n, uint64_t cap, uint64_t scap, uint64_t topic_bytes,
+                                       uint64_t client_bytes, uint64_t user_bytes, int mounted, uint64_t* out,
+                                       uint32_t out_words);
+static void layout_phase() {
+    const uint32_t O = TM_BATCHER_OPTS, I = TM_BATCHER_INBOX, F = TM_BATCHER_FORWARD, A = TM_BATCHER_ADMIT;
+    const uint64_t caps[2][2] = {{1024, 4096}, {1045, 3003}}, creds[3][2] = {{0, 5}, {5, 8}, {8, 0}};
+    uint64_t out[64], calls = 0, sum = 0;
+    expect(tm_debug_batcher_layout(0, 1, 1, 1, 1, 0, 0, 0, nullptr, 64) == TM_EINVAL, "layout: null out");
+    expect(tm_debug_batcher_layout(0, 1, 1, 1, 1, 0, 0, 0, out, 8) == TM_EINVAL, "layout: short out");
+    for (uint32_t flags : {0u, O, O | I, F, O | F, O | I | F, O | A, O | I | A, O | F | A, O | I | F | A})
+        for (uint32_t n : {0u, 1u, 7u, 8u, 9u, 32768u, 32769u})
+            for (const auto& c : caps)
+                for (const auto& cr : creds)
+                    for (int mounted = 0; mounted < 2; ++mounted, ++calls) {
+                        expect(tm_debug_batcher_layout(flags, n, c[0], c[1], n ? 13ull * n + 3 : 0, cr[0], cr[1], mounted,
+                                                       out, 64) == TM_OK,
+                               "tm_debug_batcher_layout");
+                        sum += out[18] + out[40];   // the two ends: up.end, down.outb
+                    }
+    std::printf("%-28s ok: %llu cases (%llu)\n", "block layouts", (unsigned long long)calls, (unsigned long long)sum);
+}
+
 // `threads` producers submit `per` topics each; close_early: tm_batcher_close
 // with requests in flight instead of a flush (close completes them all)
 static void flood(const char* name, tm_batcher_config cfg, int threads, uint32_t per, bool close_early) {
@@ -340,6 +365,7 @@ int main() {
     }
     inbox_phase();
     forward_phase();
+    layout_phase();
     tm_close(E);
     std::printf("san_batcher: all phases ok\n");
     return 0;

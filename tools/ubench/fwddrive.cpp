@@ -1,7 +1,6 @@
 // fwddrive.cpp — measurement helper (not product code) for
-// tools/bench_forward_stream.py: the flood of pubdrive.cpp through a publish
-// batcher on the stream-ordered call (TM_BATCHER_PUBLISH | TM_BATCHER_STREAM),
-// two ways.
+// tools/bench_forward_stream.py: the flood of pubdrive.cpp through a keyed
+// publish batcher (TM_BATCHER_PUBLISH), two ways.
 //   mode 0  the batcher as it was: every per-publish callback appends the
 //           publish's TM_NOT_LOCAL records to its lane thread's list, and the
 //           list is regrouped per node -- a stable sort by (target, To), then a
@@ -96,7 +95,7 @@ extern "C" int tm_bench_forward_flood(tm_engine* e, const uint8_t* tb, const uin
     bc.max_topics = max_topics;
     bc.deadline_us = deadline_us;
     bc.lanes_per_replica = lanes;
-    bc.flags = TM_BATCHER_PUBLISH | TM_BATCHER_STREAM | (mode ? TM_BATCHER_FORWARD : 0u);
+    bc.flags = TM_BATCHER_PUBLISH | (mode ? TM_BATCHER_FORWARD : 0u);
     g_batch = max_topics;
     tm_batcher* b;
     int rc = mode ? tm_batcher_open_plans(e, &bc, nullptr, on_forward, nullptr, &b) : tm_batcher_open(e, &bc, &b);

@@ -50,7 +50,7 @@ inline int submit(tm_batcher* b, bool publish, const uint8_t* t, uint32_t len, u
 }  // namespace
 
 // publish != 0: TM_BATCHER_PUBLISH (TM_EINVAL when built without it) -- 2: with
-// TM_BATCHER_STREAM, 3: with TM_BATCHER_ROUND_ROBIN --, else
+// TM_BATCHER_ROUND_ROBIN --, else
 // TM_BATCHER_DELIVERIES; `eager`: TM_BATCHER_EAGER.  rate 0: a flood of the nt
 // topics; else `total` publishes at `rate` per second (the batch cycled).
 // out[15]: seconds, topics/s, batches, mean batch, p50 us, p99 us, failed,
@@ -67,9 +67,9 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     bc.flags = (eager ? TM_BATCHER_EAGER : 0u);
 #ifdef TM_BATCHER_PUBLISH
     bc.flags |= publish ? TM_BATCHER_PUBLISH : TM_BATCHER_DELIVERIES;
-#ifdef TM_BATCHER_STREAM
-    if (publish == 2) bc.flags |= TM_BATCHER_STREAM;
-    if (publish == 3) bc.flags |= TM_BATCHER_ROUND_ROBIN;
+#ifdef TM_BATCHER_ROUND_ROBIN
+    if (publish == 2) bc.flags |= TM_BATCHER_ROUND_ROBIN;
+    if (publish > 2) return TM_EINVAL;
 #else
     if (publish > 1) return TM_EINVAL;
 #endif
@@ -166,7 +166,7 @@ extern "C" int tm_bench_publish(tm_engine* e, const uint8_t* tb, const uint64_t*
     out[11] = (st.sync_ns - st0.sync_ns) / nb / 1e3;
     out[12] = (st.callback_ns - st0.callback_ns) / nb / 1e3;
     out[13] = (double)(st.results - st0.results) / nb;
-#ifdef TM_BATCHER_STREAM
+#ifdef TM_BATCHER_ROUND_ROBIN
     out[14] = (double)(st.reruns - st0.reruns);
 #else
     out[14] = 0;
