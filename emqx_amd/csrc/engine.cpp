@@ -220,6 +220,9 @@ struct SegPool {
         off = (uint32_t)v.size();
         cap = c;
         v.resize(v.size() + c, 0);
+        // the whole new segment, its unwritten tail too: an image updated by scatter then holds the
+        // host's zeros there, as one copied whole does (tm_debug_check_device compares every element)
+        t.mark_range(off, (size_t)off + c);
         return true;
     }
     void set(size_t i, uint32_t x) {
@@ -1466,7 +1469,9 @@ struct tm_engine {
                 aux[tmp_path[i - 1]].lsum = (uint16_t)sum_union(aux[tmp_path[i - 1]].lsum, a.sum);
             if (i > 0) refresh_slot_sum(tmp_path[i]);
         }
-        for (uint32_t i = 0; i < D; ++i) refresh_hf(tmp_path[i]);
+        // (path[D] too: a node created for this filter still holds empty_node()'s FILTER_NONE, not the
+        // summaries of its no children that relayout would write -- tm_debug_check_trie holds both to hf_value)
+        for (uint32_t i = 0; i <= D; ++i) refresh_hf(tmp_path[i]);
     }
 
     // ------------------------------------------------------------------
@@ -1950,7 +1955,9 @@ struct tm_engine {
     // the bag and the option map
     void sseg_rewrite(SubRec& r) {
         if (sx_pool.fit(r.off, r.cap, r.n_plain, "subscriber pool past 2^32 entries")) ++sx_seg_moves;
+        const size_t opts = sx_opt.size();
         sx_opt.resize(sx_pool.v.size(), SUBOPT_NONE);
+        t_opt.mark_range(opts, sx_opt.size());   // (a new segment's tail, as SegPool::fit)
         size_t k = r.off;
         for (const auto& x : r.bag)
             if (x.second == NO_GROUP) {
@@ -2045,7 +2052,9 @@ struct tm_engine {
     void share_seg_rewrite(ShareSet& s) {
         const size_t n = s.members.size();
         sh_pool.fit(s.off, s.cap, n, "share member pool past 2^32 entries");
+        const size_t opts = sh_opt.size();
         sh_opt.resize(sh_pool.v.size(), SUBOPT_NONE);
+        t_hopt.mark_range(opts, sh_opt.size());   // (a new segment's tail, as SegPool::fit)
         std::copy(s.members.begin(), s.members.end(), sh_pool.v.begin() + s.off);
         const SubRec* sr = share_sub_rec(s);
         for (size_t k = 0; k < n; ++k) sh_opt[s.off + k] = share_opt_word(sr, s.members[k]);
@@ -2815,33 +2824,36 @@ struct tm_engine {
     // list, so a table cannot be in one loop and missing from the other (the
     // other image epoch would then miss one commit's changes).  The one
     // asymmetry: fshape is kept and rotated always, uploaded only under
-    // option "shape_keys".
+    // option "shape_keys".  Each table has a name, and the order is fixed:
+    // the diagnostics (tm_debug_check_device, tm_debug_commit_stats) report
+    // by both.
+    static constexpr size_t N_TABLES = 24;
     template <class F>
     void for_each_table(F&& f) {
-        f(nodes, t_nodes, &Image::d_nodes, true);
-        f(cold.slots, cold.t, &Image::d_edges, true);
-        f(hot.slots, hot.t, &Image::d_hedges, true);
-        f(dict, t_dict, &Image::d_dict, true);
-        f(rt_slots.slots, rt_slots.t, &Image::d_rslots, true);
-        f(rt_arena.words, rt_arena.t, &Image::d_rarena, true);
-        f(rt_dest.v, rt_dest.t, &Image::d_rdest, true);
-        f(fr.meta, fr.t, &Image::d_fr_meta, true);
-        f(rank_src, t_rank_src, &Image::d_rank_src, true);
-        f(dt, t_dt, &Image::d_dt, true);
-        f(rank_tg, t_rank_tg, &Image::d_rank_tg, true);
-        f(fwd_tg, t_fwd, &Image::d_fwd, true);
-        f(sx_slots.slots, sx_slots.t, &Image::d_sslots, true);
-        f(sx_arena.words, sx_arena.t, &Image::d_sarena, true);
-        f(sx_pool.v, sx_pool.t, &Image::d_spool, true);
-        f(sx_opt, t_opt, &Image::d_sopt, true);
-        f(fs.meta, fs.t, &Image::d_fs_meta, true);
-        f(sh_sets.slots, sh_sets.t, &Image::d_hsets, true);
-        f(sh_tx.slots, sh_tx.t, &Image::d_htx, true);
-        f(sh_arena.words, sh_arena.t, &Image::d_harena, true);
-        f(sh_pool.v, sh_pool.t, &Image::d_hpool, true);
-        f(sh_opt, t_hopt, &Image::d_hopt, true);
-        f(sh_fx.meta, sh_fx.t, &Image::d_hfx, true);
-        f(fshape, t_fshape, &Image::d_fshape, shape_keys != 0);
+        f("nodes", nodes, t_nodes, &Image::d_nodes, true);
+        f("edges", cold.slots, cold.t, &Image::d_edges, true);
+        f("hot_edges", hot.slots, hot.t, &Image::d_hedges, true);
+        f("dict", dict, t_dict, &Image::d_dict, true);
+        f("rt_slots", rt_slots.slots, rt_slots.t, &Image::d_rslots, true);
+        f("rt_arena", rt_arena.words, rt_arena.t, &Image::d_rarena, true);
+        f("rt_dest", rt_dest.v, rt_dest.t, &Image::d_rdest, true);
+        f("fr_meta", fr.meta, fr.t, &Image::d_fr_meta, true);
+        f("rank_src", rank_src, t_rank_src, &Image::d_rank_src, true);
+        f("dt", dt, t_dt, &Image::d_dt, true);
+        f("rank_tg", rank_tg, t_rank_tg, &Image::d_rank_tg, true);
+        f("fwd", fwd_tg, t_fwd, &Image::d_fwd, true);
+        f("sx_slots", sx_slots.slots, sx_slots.t, &Image::d_sslots, true);
+        f("sx_arena", sx_arena.words, sx_arena.t, &Image::d_sarena, true);
+        f("sx_pool", sx_pool.v, sx_pool.t, &Image::d_spool, true);
+        f("sx_opt", sx_opt, t_opt, &Image::d_sopt, true);
+        f("fs_meta", fs.meta, fs.t, &Image::d_fs_meta, true);
+        f("sh_sets", sh_sets.slots, sh_sets.t, &Image::d_hsets, true);
+        f("sh_tx", sh_tx.slots, sh_tx.t, &Image::d_htx, true);
+        f("sh_arena", sh_arena.words, sh_arena.t, &Image::d_harena, true);
+        f("sh_pool", sh_pool.v, sh_pool.t, &Image::d_hpool, true);
+        f("sh_opt", sh_opt, t_hopt, &Image::d_hopt, true);
+        f("sh_fx", sh_fx.meta, sh_fx.t, &Image::d_hfx, true);
+        f("fshape", fshape, t_fshape, &Image::d_fshape, shape_keys != 0);
     }
 
     // upload a host table to one replica: the whole table after a resize (or
@@ -2850,22 +2862,82 @@ struct tm_engine {
     // the elements changed since image g was last written (this commit's log
     // and, when g missed the previous commit (two epochs), that one's too):
     // packed for one scatter, or the whole table copied when that is cheaper
+    // How a commit brings one table of an image up to date (the decision of
+    // upload_table; tm_debug_commit_stats reports it): nothing to do, a
+    // scatter of this commit's log, of this and the previous commit's, or a
+    // copy of the whole table; n: the elements a scatter writes.
+    enum : uint32_t { UP_NONE = 0, UP_SCATTER = 1, UP_SCATTER_TWO = 2, UP_COPY = 3 };
+    struct UploadPlan {
+        uint32_t how;
+        size_t n;
+    };
+    // re: the table's buffer was reallocated; the image holds commit g_epoch
+    // (when written) and this commit makes now + 1
+    static UploadPlan upload_plan(bool re, bool written, uint64_t g_epoch, uint64_t now, const Dirty& dirty,
+                                  const Dirty& prev, size_t elems, size_t elem_bytes) {
+        const bool two = written && g_epoch + 1 == now;        // the image missed exactly the previous commit
+        const bool stale = !written || g_epoch + 1 < now;      // missed more (double_buffer switched on)
+        const size_t n = dirty.idx.size() + (two ? prev.idx.size() : 0);
+        if (re || stale || dirty.all || (two && prev.all) || n * (4 + elem_bytes) * 4 > elems * elem_bytes)
+            return UploadPlan{elems ? UP_COPY : UP_NONE, 0};
+        if (n == 0) return UploadPlan{UP_NONE, 0};
+        return UploadPlan{two ? UP_SCATTER_TWO : UP_SCATTER, n};
+    }
+    // the last commit's plan per table of for_each_table, in its order
+    // (replica 0's; on a host-only engine the plan of a device with two
+    // image epochs, virt: what such a device would hold)
+    struct CommitStat {
+        uint32_t how;
+        uint64_t n, elems;
+    };
+    CommitStat commit_stats[N_TABLES] = {};
+    struct VirtImage {
+        bool written = false;
+        uint64_t epoch = 0;
+        size_t bytes[N_TABLES] = {};
+    } virt[2];
+    int virt_cur = 0;
+    // the plans of a commit on a host-only engine, from the logs before they
+    // rotate: buffer sizes grow as DevBuf::ensure_async grows them
+    void record_host_plans() {
+        const int back = double_buffer ? 1 - virt_cur : virt_cur;
+        VirtImage& g = virt[back];
+        size_t k = 0;
+        for_each_table([&](const char*, const auto& host, Track& t, DevBuf Image::*, bool upload) {
+            using T = typename std::decay_t<decltype(host)>::value_type;
+            UploadPlan p{UP_NONE, 0};
+            if (upload) {
+                const size_t need = std::max<size_t>(host.size(), 1) * sizeof(T) + NF_TAIL;
+                const bool re = need > g.bytes[k];
+                if (re) g.bytes[k] = std::max<size_t>(256, (size_t)(need * 1.25));
+                p = upload_plan(re, g.written, g.epoch, epoch, t.cur, t.prev, host.size(), sizeof(T));
+            }
+            commit_stats[k++] = CommitStat{p.how, p.n, host.size()};
+        });
+        g.written = true;
+        g.epoch = epoch + 1;
+        virt_cur = back;
+    }
+
     template <class T>
     void upload_table(DevState& d, Image& g, DevBuf& buf, const std::vector<T>& host, const Dirty& dirty,
-                      const Dirty& prev) {
+                      const Dirty& prev, CommitStat* stat) {
         static_assert(sizeof(T) % 4 == 0, "tables are scattered in 32-bit words");
         // (NF_TAIL: the node table's tail padding, see split_image)
         const bool re = buf.ensure_async(std::max<size_t>(host.size(), 1) * sizeof(T) + NF_TAIL, d.ustream);
         // g holds commit g.epoch; this one makes epoch + 1
-        const bool two = g.written && g.epoch + 1 == epoch;        // g missed exactly the previous commit
-        const bool stale = !g.written || g.epoch + 1 < epoch;      // missed more (double_buffer switched on)
-        const size_t n = dirty.idx.size() + (two ? prev.idx.size() : 0);
-        if (re || stale || dirty.all || (two && prev.all) || n * (4 + sizeof(T)) * 4 > host.size() * sizeof(T)) {
-            if (!host.empty())
-                HIPCHK(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, d.ustream));
+        const UploadPlan plan = upload_plan(re, g.written, g.epoch, epoch, dirty, prev, host.size(), sizeof(T));
+        if (stat) {
+            stat->how = plan.how;
+            stat->n = plan.n;
+        }
+        const bool two = plan.how == UP_SCATTER_TWO;
+        const size_t n = plan.n;
+        if (plan.how == UP_COPY) {
+            HIPCHK(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, d.ustream));
             return;
         }
-        if (n == 0) return;
+        if (plan.how == UP_NONE) return;
         const uint64_t off = (d.stage_host.size() + 15) & ~uint64_t(15);
         d.stage_host.resize(off + n * (4 + sizeof(T)));
         uint32_t* ix = reinterpret_cast<uint32_t*>(d.stage_host.data() + off);
@@ -2915,6 +2987,8 @@ struct tm_engine {
         if (devs.empty()) {
             (void)release_share_indices();
             sh_downed.clear();
+            record_host_plans();
+            for_each_table([](const char*, const auto& host, Track& t, DevBuf Image::*, bool) { t.rotate(host.size()); });
             ++epoch;
             dev_dirty = false;
             release_quarantine();
@@ -2947,8 +3021,12 @@ struct tm_engine {
             const int back = double_buffer ? 1 - d.cur : d.cur;
             Image& g = d.img[back];
             d.drain_image(back);   // the batches launched on it before the last flip
-            for_each_table([&](const auto& host, Track& t, DevBuf Image::*buf, bool upload) {
-                if (upload) upload_table(d, g, g.*buf, host, t.cur, t.prev);
+            size_t k = 0;
+            for_each_table([&](const char*, const auto& host, Track& t, DevBuf Image::*buf, bool upload) {
+                CommitStat* stat = &d == devs[0].get() ? &commit_stats[k] : nullptr;
+                if (stat) *stat = CommitStat{UP_NONE, 0, host.size()};
+                if (upload) upload_table(d, g, g.*buf, host, t.cur, t.prev, stat);
+                ++k;
             });
             share_cursor_prepare(d, g, six_reset, downed);
             flush_stage(d);
@@ -2987,7 +3065,7 @@ struct tm_engine {
         }
         // this commit's dirty pages become the "previous" set the other image
         // still needs at the next commit
-        for_each_table([](const auto& host, Track& t, DevBuf Image::*, bool) { t.rotate(host.size()); });
+        for_each_table([](const char*, const auto& host, Track& t, DevBuf Image::*, bool) { t.rotate(host.size()); });
         dev_dirty = false;
         ++epoch;
         release_quarantine();   // also for engines that only take forced ids (never reach new_filter's release)
@@ -6676,6 +6754,326 @@ extern "C" int tm_debug_check_filters(tm_engine* e) {
             for (size_t v = 0; v < e->nkind.size(); ++v)
                 if (e->nkind[v] != tm_engine::NK_PLAIN && (v == ROOT || e->aux[v].parent != NODE_NONE))
                     return fail("nfilter off, yet id " + std::to_string(v) + " is filtered");
+        return TM_OK;
+    });
+}
+
+// diagnostics (not part of include/topicmatch.h): how the last commit that
+// wrote an image (one with nothing to publish leaves the record alone) brought
+// each table of for_each_table up to date, in that order: out[3k] = the
+// decision (0 nothing to do, 1 scatter of that commit's log, 2 scatter of
+// that and the previous commit's, 3 whole-table copy), out[3k + 1] = the
+// elements scattered, out[3k + 2] = the table's elements (cap: the tables out
+// has room for).  Replica 0's uploads; on a host-only engine the decisions a
+// device with two image epochs would have taken.  Returns the number of
+// tables, or TM_ENOSPC when cap is smaller.  tm_debug_table_name: the name of
+// table k of for_each_table (null past the last).
+extern "C" int tm_debug_commit_stats(tm_engine* e, uint64_t* out, uint32_t cap) {
+    if (!e || !out) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        if (cap < tm_engine::N_TABLES) return TM_ENOSPC;
+        for (size_t k = 0; k < tm_engine::N_TABLES; ++k) {
+            const tm_engine::CommitStat& s = e->commit_stats[k];
+            out[3 * k] = s.how;
+            out[3 * k + 1] = s.n;
+            out[3 * k + 2] = s.elems;
+        }
+        return (int)tm_engine::N_TABLES;
+    });
+}
+extern "C" const char* tm_debug_table_name(tm_engine* e, uint32_t k) {
+    if (!e) return nullptr;
+    const char* found = nullptr;
+    std::lock_guard<std::recursive_mutex> lk(e->mu);
+    uint32_t i = 0;
+    e->for_each_table([&](const char* name, const auto&, Track&, DevBuf Image::*, bool) {
+        if (i++ == k) found = name;
+    });
+    return found;
+}
+
+// diagnostics (not part of include/topicmatch.h): the live image of every
+// replica, read back and compared byte for byte with the host tables it
+// mirrors -- every uploaded table of for_each_table, the append-only arrays
+// (word arena, word_off, word_heat) over their uploaded lengths, the split
+// halves when the view uses them, and the scalars of the captured ImageView.
+// (The share cursors and sticky entries live outside the epochs: not
+// compared.)  TM_EINVAL with uncommitted deltas or before the first image, or
+// naming the first difference in tm_last_error.
+extern "C" int tm_debug_check_device(tm_engine* e) {
+    if (!e) return TM_EINVAL;
+    auto held = lock_batches(e);
+    return guarded(e, [&]() -> int {
+        if (e->devs.empty()) throw ArgError("device image: the engine is host-only");
+        if (e->dev_dirty) throw ArgError("device image: uncommitted deltas");
+        auto hex = [](const uint8_t* p, size_t bytes) {
+            std::string s;
+            char b[12];
+            for (size_t i = 0; bytes < 4 && i < bytes; ++i) {
+                std::snprintf(b, sizeof b, "%02x", p[i]);
+                s += b;
+            }
+            for (size_t i = 0; i + 4 <= bytes && i < 32; i += 4) {
+                uint32_t w;
+                std::memcpy(&w, p + i, 4);
+                std::snprintf(b, sizeof b, "%s%08x", i ? " " : "", w);
+                s += b;
+            }
+            return s;
+        };
+        std::vector<uint8_t> back;
+        for (size_t r = 0; r < e->devs.size(); ++r) {
+            DevState& d = *e->devs[r];
+            tm_engine::Guard gd(d.device);
+            const Image& g = d.live();
+            if (!g.written) throw ArgError("device image: replica " + std::to_string(r) + " has no image yet");
+            HIPCHK(hipStreamSynchronize(d.ustream));
+            const std::string where = "device image: replica " + std::to_string(r) + ", image " +
+                                      std::to_string(d.cur) + ", epoch " + std::to_string(g.epoch) + ", ";
+            // `elems` elements of `width` bytes at `host` against the device buffer
+            auto compare = [&](const char* name, const DevBuf& buf, const void* host, size_t elems, size_t width) {
+                const size_t bytes = elems * width;
+                if (!bytes) return;
+                if (!buf.p || buf.bytes < bytes)
+                    throw ArgError(where + name + ": buffer of " + std::to_string(buf.bytes) + " B for " +
+                                   std::to_string(bytes));
+                back.resize(bytes);
+                HIPCHK(hipMemcpy(back.data(), buf.p, bytes, hipMemcpyDeviceToHost));
+                const uint8_t* h = static_cast<const uint8_t*>(host);
+                if (!std::memcmp(back.data(), h, bytes)) return;
+                size_t i = 0;
+                while (!std::memcmp(back.data() + i * width, h + i * width, width)) ++i;
+                throw ArgError(where + name + ": element " + std::to_string(i) + " of " + std::to_string(elems) +
+                               ": device " + hex(back.data() + i * width, width) + ", host " + hex(h + i * width, width));
+            };
+            e->for_each_table([&](const char* name, const auto& host, Track&, DevBuf Image::*buf, bool upload) {
+                using T = typename std::decay_t<decltype(host)>::value_type;
+                if (upload) compare(name, g.*buf, host.data(), host.size(), sizeof(T));
+            });
+            if (g.arena_uploaded != e->word_arena.size() || g.woff_uploaded != e->word_off.size())
+                throw ArgError(where + "word arena / word_off: uploaded lengths behind the host's");
+            compare("word_arena", g.d_arena, e->word_arena.data(), g.arena_uploaded, 1);
+            compare("word_off", g.d_woff, e->word_off.data(), g.woff_uploaded, 4);
+            if (g.heat_uploaded != e->heat_version || g.heat_words != e->word_heat.size())
+                throw ArgError(where + "word_heat: version behind the host's");
+            compare("word_heat", g.d_wheat, e->word_heat.data(), g.heat_words, 1);
+            const ImageView want = e->make_view(g);
+            if (g.iv.node_shift == 4) {
+                std::vector<uint8_t> half(e->nodes.size() * 16);
+                for (int h = 0; h < 2; ++h) {
+                    for (size_t v = 0; v < e->nodes.size(); ++v)
+                        std::memcpy(&half[v * 16], reinterpret_cast<const uint8_t*>(&e->nodes[v]) + 16 * h, 16);
+                    compare(h ? "leaf halves" : "inner halves", h ? g.d_leaf : g.d_inner, half.data(), e->nodes.size(), 16);
+                }
+            }
+            auto scalar = [&](const char* name, uint64_t got, uint64_t exp) {
+                if (got != exp)
+                    throw ArgError(where + "view " + name + ": " + std::to_string(got) + ", host " + std::to_string(exp));
+            };
+            scalar("node_shift", g.iv.node_shift, want.node_shift);
+            scalar("edge_slot_mask", g.iv.edge_slot_mask, want.edge_slot_mask);
+            scalar("hot_slot_mask", g.iv.hot_slot_mask, want.hot_slot_mask);
+            scalar("dict_slot_mask", g.iv.dict_slot_mask, want.dict_slot_mask);
+            scalar("hot_limit", g.iv.hot_limit, want.hot_limit);
+            scalar("root_cls", g.iv.root_cls, want.root_cls);
+            scalar("n_words", g.iv.n_words, e->word_heat.size());
+        }
+        return TM_OK;
+    });
+}
+
+// diagnostics (not part of include/topicmatch.h): the trie image on the host
+// (nodes, edge tables, Bloom masks, summaries, dictionary) against the
+// logical trie its aux records and filter registry describe; works on a
+// host-only engine.  For every live node: it is reachable from its aux
+// (parent, word) exactly as the kernels find it -- the parent's '+' field,
+// '#' field, inline lw:lc, or the probe from edge_home (in `hot` for parents
+// below hot_limit) with no empty slot before the hit; a narrow node has at
+// most one literal child; a WIDE node has lit_count slots, every child word
+// in its Bloom mask, and is WIDE only while it has literal children; every
+// used slot names a live parent and child whose aux agrees and equals
+// slot_for() of now (summary and class), `used` counts them and the load is
+// within 1 / edge_div; a '#' child has its slot, hash_filter2 is its filter,
+// hash_filter == hf_value(); self_filter and FilterRec::node name each other;
+// edge_count / lit_count are the counted children; free ids are distinct, dead
+// and no extension slots; the stored summaries contain the exact ones
+// (recomputed bottom-up from the live filters) and lsum the literal
+// children's stored ones.  The dictionary is append-only (no code path
+// removes a word, so there is no deletion to leave a hole in a probe run):
+// every interned word is found from its home slot by the tokenizer's probe,
+// tag / heads / len / arena bytes are the word's, dict_used counts the used
+// slots and the load is at most 1/2.  TM_OK, or TM_EINVAL naming the first
+// defect in tm_last_error.
+extern "C" int tm_debug_check_trie(tm_engine* e) {
+    if (!e) return TM_EINVAL;
+    return guarded(e, [&]() -> int {
+        auto fail = [](const std::string& what) -> int { throw ArgError("trie image: " + what); };
+        auto S = [](uint64_t x) { return std::to_string(x); };
+        const size_t N = e->nodes.size();
+        if (e->aux.size() != N) return fail("aux size");
+        auto live = [&](uint32_t v) {
+            return v < N && !e->is_ext(v) && (v == ROOT || e->aux[v].parent != NODE_NONE);
+        };
+        // ---- nodes: reachability, counts
+        std::vector<uint32_t> n_edges(N, 0), n_lit(N, 0), n_slots(N, 0);
+        size_t n_live = 0;
+        for (uint32_t v = 0; v < N; ++v) {
+            if (!live(v)) continue;
+            ++n_live;
+            if (v == ROOT) continue;
+            const uint32_t p = e->aux[v].parent, w = e->aux[v].word;
+            if (!live(p)) return fail("node " + S(v) + ": parent " + S(p) + " is not live");
+            const Node& x = e->nodes[p];
+            ++n_edges[p];
+            if (w == WORD_PLUS) {
+                if ((x.plus & NODE_MASK) != v) return fail("node " + S(v) + ": not its parent's '+' child");
+                continue;
+            }
+            if (w == WORD_HASH) {
+                if (x.hash != v) return fail("node " + S(v) + ": not its parent's '#' child");
+            } else {
+                if (w >= e->word_off.size()) return fail("node " + S(v) + ": word " + S(w) + " not interned");
+                ++n_lit[p];
+                if (!(x.plus & WIDE)) {
+                    if (x.lw != w || x.lc != v) return fail("node " + S(v) + ": not its narrow parent's inline child");
+                    continue;
+                }
+                const uint64_t b = word_bloom(w), mask = ((uint64_t)x.lc << 32) | x.lw;
+                if ((mask & b) != b) return fail("node " + S(p) + ": Bloom mask lacks child word " + S(w));
+            }
+            const size_t s = e->edge_find_slot(p, w);   // the kernels' probe: stops at the first empty slot
+            if (s == SIZE_MAX || e->tab(p).slots[s].child != v)
+                return fail("node " + S(v) + ": the probe of (" + S(p) + ", " + S(w) + ") does not find it");
+        }
+        if (n_live != e->live_nodes) return fail("live_nodes " + S(e->live_nodes) + " != nodes " + S(n_live));
+        // ---- edge slots
+        for (const tm_engine::EdgeTable* t : {&e->cold, &e->hot}) {
+            size_t used = 0;
+            for (size_t s = 0; s < t->slots.size(); ++s) {
+                const EdgeSlot& x = t->slots[s];
+                if (x.parent == EDGE_EMPTY) continue;
+                ++used;
+                const std::string at = std::string(t == &e->hot ? "hot" : "cold") + " slot " + S(s);
+                if (!live(x.parent) || !live(x.child)) return fail(at + ": parent or child not live");
+                if (&e->tab(x.parent) != t) return fail(at + ": parent " + S(x.parent) + " belongs in the other table");
+                if (e->aux[x.child].parent != x.parent || e->aux[x.child].word != x.word)
+                    return fail(at + ": child " + S(x.child) + " has another (parent, word)");
+                const EdgeSlot want = e->slot_for(x.parent, x.word, x.child);
+                if (std::memcmp(&x, &want, sizeof x))
+                    return fail(at + ": child " + S(x.child) + " carries summary word " + S(x.plus) + ", now " + S(want.plus));
+                if (x.word != WORD_HASH) ++n_slots[x.parent];
+            }
+            if (used != t->used) return fail(std::string(t == &e->hot ? "hot" : "cold") + " used " + S(t->used) + " != " + S(used));
+            if (t->slots.size() & (t->slots.size() - 1)) return fail("edge table size not a power of two");
+            if (used * e->edge_div > t->slots.size()) return fail("edge table load past 1 / edge_div");
+        }
+        // ---- per node: layout of its children, filters
+        size_t n_filters = 0;
+        for (uint32_t v = 0; v < N; ++v) {
+            if (!live(v)) continue;
+            const Node& x = e->nodes[v];
+            const NodeAux& a = e->aux[v];
+            if (a.edge_count != n_edges[v]) return fail("node " + S(v) + ": edge_count " + S(a.edge_count) + " != " + S(n_edges[v]));
+            if (a.lit_count != n_lit[v]) return fail("node " + S(v) + ": lit_count " + S(a.lit_count) + " != " + S(n_lit[v]));
+            if (x.plus & WIDE) {
+                if (a.lit_count == 0) return fail("node " + S(v) + ": WIDE without literal children");
+                if (n_slots[v] != a.lit_count) return fail("node " + S(v) + ": " + S(n_slots[v]) + " slots for " + S(a.lit_count) + " literal children");
+            } else {
+                if (a.lit_count > 1) return fail("node " + S(v) + ": narrow with " + S(a.lit_count) + " literal children");
+                if (n_slots[v]) return fail("node " + S(v) + ": narrow with literal slots");
+                if (a.lit_count == 0 && (x.lw != WORD_NONE || x.lc != NODE_NONE)) return fail("node " + S(v) + ": inline pair without a child");
+            }
+            const uint32_t pc = x.plus & NODE_MASK;
+            if (pc != NODE_NONE && (!live(pc) || e->aux[pc].parent != v || e->aux[pc].word != WORD_PLUS))
+                return fail("node " + S(v) + ": '+' field names " + S(pc));
+            if (x.hash != NODE_NONE && (!live(x.hash) || e->aux[x.hash].parent != v || e->aux[x.hash].word != WORD_HASH))
+                return fail("node " + S(v) + ": '#' field names " + S(x.hash));
+            if (x.hash_filter2 != (x.hash != NODE_NONE ? e->nodes[x.hash].self_filter : FILTER_NONE))
+                return fail("node " + S(v) + ": hash_filter2 is not the '#' child's filter");
+            if (x.hash_filter != e->hf_value(v)) return fail("node " + S(v) + ": hash_filter " + S(x.hash_filter) + " != " + S(e->hf_value(v)));
+            if (x.self_filter != FILTER_NONE) {
+                ++n_filters;
+                if (x.self_filter >= e->filters.size() || e->filters[x.self_filter].node != v)
+                    return fail("node " + S(v) + ": filter " + S(x.self_filter) + " does not end here");
+            }
+        }
+        for (size_t f = 0; f < e->filters.size(); ++f) {
+            const uint32_t v = e->filters[f].node;
+            if (v != NODE_NONE && (!live(v) || e->nodes[v].self_filter != f)) return fail("filter " + S(f) + ": node " + S(v) + " does not hold it");
+        }
+        if (n_filters != e->live_filters) return fail("live_filters " + S(e->live_filters) + " != " + S(n_filters));
+        // ---- free ids
+        {
+            std::vector<uint8_t> seen(N, 0);
+            for (uint32_t f : e->free_nodes) {
+                if (f >= N || f == ROOT || e->is_ext(f) || e->aux[f].parent != NODE_NONE) return fail("free id " + S(f) + " is live or an extension slot");
+                if (seen[f]++) return fail("free id " + S(f) + " listed twice");
+            }
+            size_t dead = 0;
+            for (uint32_t v = 0; v < N; ++v) dead += !e->is_ext(v) && !live(v);
+            if (dead != e->free_nodes.size()) return fail(S(dead) + " dead ids, " + S(e->free_nodes.size()) + " free-listed");
+        }
+        // ---- summaries: exact S bottom-up (parents before children in BFS order, reversed)
+        {
+            std::vector<uint32_t> start(N + 1, 0), order;
+            for (uint32_t v = 1; v < N; ++v)
+                if (live(v)) ++start[e->aux[v].parent + 1];
+            for (size_t v = 0; v < N; ++v) start[v + 1] += start[v];
+            std::vector<uint32_t> kids(start[N]), fill(start.begin(), start.end() - 1);
+            for (uint32_t v = 1; v < N; ++v)
+                if (live(v)) kids[fill[e->aux[v].parent]++] = v;
+            order.push_back(ROOT);
+            for (size_t i = 0; i < order.size(); ++i)
+                for (uint32_t k = start[order[i]]; k < start[order[i] + 1]; ++k) order.push_back(kids[k]);
+            if (order.size() != n_live) return fail(S(n_live - order.size()) + " live nodes not below the root");
+            std::vector<uint16_t> sum(N, (uint16_t)SUM_NONE), lit(N, (uint16_t)SUM_NONE);
+            for (size_t i = order.size(); i-- > 0;) {
+                const uint32_t v = order[i];
+                const NodeAux& a = e->aux[v];
+                if (e->nodes[v].self_filter != FILTER_NONE) sum[v] = (uint16_t)sum_union(sum[v], sum_end0());
+                const uint32_t hm = (sum[v] >> 11) & 15u, hs = (a.sum >> 11) & 15u;
+                if ((a.sum & sum[v] & 0x7FFu) != (sum[v] & 0x7FFu) || hs > hm)
+                    return fail("node " + S(v) + ": summary " + S(a.sum) + " does not contain the exact " + S(sum[v]));
+                if (a.lit_count && sum_union(a.lsum, lit[v]) != a.lsum)
+                    return fail("node " + S(v) + ": lsum " + S(a.lsum) + " does not contain its literal children's " + S(lit[v]));
+                if (v == ROOT) continue;
+                sum[a.parent] = (uint16_t)sum_union(sum[a.parent], sum_shift(sum[v]));
+                if (a.word == WORD_HASH && e->nodes[v].self_filter != FILTER_NONE)
+                    sum[a.parent] = (uint16_t)sum_union(sum[a.parent], sum_hash0(SUM_NONE));
+                if (a.word < WORD_MAX) lit[a.parent] = (uint16_t)sum_union(lit[a.parent], a.sum);   // the stored ones
+            }
+        }
+        // ---- dictionary
+        {
+            const size_t W = e->word_off.size(), mask = e->dict.size() - 1;
+            if (e->dict.size() & mask) return fail("dictionary size not a power of two");
+            std::vector<uint8_t> seen(W, 0);
+            size_t used = 0;
+            for (size_t s = 0; s <= mask; ++s) {
+                const DictSlot& d = e->dict[s];
+                if (d.word == WORD_NONE) continue;
+                ++used;
+                if (d.word >= W || seen[d.word]++) return fail("dict slot " + S(s) + ": word " + S(d.word) + " unknown or twice");
+                const size_t off = e->word_off[d.word], padded = std::max<size_t>(8, (d.len + 7) & ~size_t(7));
+                if (off % 8 || off + padded > e->word_arena.size()) return fail("word " + S(d.word) + ": arena span");
+                const uint8_t* p = &e->word_arena[off];
+                for (size_t i = d.len; i < padded; ++i)
+                    if (p[i]) return fail("word " + S(d.word) + ": arena padding");
+                const uint64_t h = word_hash(p, d.len);
+                uint8_t head[16] = {0};
+                std::memcpy(head, p, std::min<size_t>(16, d.len));
+                if (d.tag != dict_tag(h, d.len) || std::memcmp(&d.head0, head, 8) || std::memcmp(&d.head1, head + 8, 8) || d.pad)
+                    return fail("dict slot " + S(s) + ": tag or heads are not word " + S(d.word) + "'s");
+                size_t q = h & mask;   // the tokenizer's probe: the first slot that is this word, no empty one before
+                while (e->dict[q].word < W &&
+                       !(e->dict[q].tag == d.tag && e->dict[q].len == d.len &&
+                         std::memcmp(&e->word_arena[e->word_off[e->dict[q].word]], p, d.len) == 0))
+                    q = (q + 1) & mask;
+                if (q != s) return fail("word " + S(d.word) + ": the probe from its home slot ends at " + S(q) + ", not " + S(s));
+            }
+            if (used != e->dict_used || used != W) return fail("dict_used " + S(e->dict_used) + ", slots " + S(used) + ", words " + S(W));
+            if (used * 2 > e->dict.size()) return fail("dictionary load past 1/2");
+        }
         return TM_OK;
     });
 }

@@ -382,6 +382,40 @@ class Engine:
         tm_debug_check_routes): raises TopicMatchError naming the first defect"""
         return self._check(self.lib.tm_debug_check_routes(self.h), "tm_debug_check_routes")
 
+    def debug_check_device(self):
+        """the live image of every replica read back and compared byte for byte
+        with the host tables (diagnostic, tm_debug_check_device): raises
+        TopicMatchError naming the first difference, or when deltas are
+        uncommitted or no image is written yet"""
+        self.lib.tm_debug_check_device.argtypes = [ctypes.c_void_p]
+        return self._check(self.lib.tm_debug_check_device(self.h), "tm_debug_check_device")
+
+    def debug_check_trie(self):
+        """host-side check of the trie image (nodes, edge tables, Bloom masks,
+        summaries, dictionary) against the logical trie (diagnostic,
+        tm_debug_check_trie): raises TopicMatchError naming the first defect"""
+        self.lib.tm_debug_check_trie.argtypes = [ctypes.c_void_p]
+        return self._check(self.lib.tm_debug_check_trie(self.h), "tm_debug_check_trie")
+
+    # the upload decisions tm_debug_commit_stats reports
+    UP_NONE, UP_SCATTER, UP_SCATTER_TWO, UP_COPY = 0, 1, 2, 3
+
+    def debug_commit_stats(self):
+        """how the last commit uploaded each image table (diagnostic,
+        tm_debug_commit_stats): {table name: (decision, elements scattered,
+        table elements)}, decision one of UP_NONE / UP_SCATTER (that commit's
+        log) / UP_SCATTER_TWO (that and the previous one's) / UP_COPY"""
+        cap = 64
+        out = (ctypes.c_uint64 * (3 * cap))()
+        f, name = self.lib.tm_debug_commit_stats, self.lib.tm_debug_table_name
+        f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+        name.restype, name.argtypes = ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_uint32]
+        n = f(self.h, out, cap)
+        if n < 0:
+            self._check(n, "tm_debug_commit_stats")
+        return {name(self.h, k).decode(): (int(out[3 * k]), int(out[3 * k + 1]), int(out[3 * k + 2]))
+                for k in range(n)}
+
     def dest_target(self, dest: bytes, kind: int, key: bytes) -> int:
         """declare dest's aggre target: a node atom (TARGET_NODE, key = its
         text) or a $share group (TARGET_GROUP, key = the group binary)"""

@@ -17,6 +17,7 @@ from emqx_amd import Engine  # noqa: E402
 from emqx_amd import workload as W  # noqa: E402
 from emqx_amd.emqx_router import Router  # noqa: E402
 from oracle import pytrie  # noqa: E402
+from trie_churn import read_back  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -234,7 +235,8 @@ def test_route_image_churn_on_device_vs_oracle(gpu_device, double_buffer):
     behind the router's back; every burst's match_routes/1 and
     aggre(match_routes/1) equal the oracle's, with two image epochs and with
     one (double_buffer 0)"""
-    rng = random.Random(31 + double_buffer)
+    rng, mini = random.Random(31 + double_buffer), random.Random(131)
+    copies, scatters = {}, {}
     e = Engine(device=gpu_device)
     e.set_option("route_gc", 64)
     e.set_option("double_buffer", double_buffer)
@@ -265,10 +267,30 @@ def test_route_image_churn_on_device_vs_oracle(gpu_device, double_buffer):
                 e.insert(t)
         if burst % 4 == 3:
             e.debug_check_routes()
+        # the image read back after the burst's commit (mostly whole-table copies: 700 ops on small
+        # tables), then two bursts of ten ops: their commits scatter the changed elements
+        read_back(e, copies)
+        for _ in range(2):
+            for _ in range(10):
+                t = mini.choice(sorted(live))
+                d = mini.choice(DESTS)
+                if d in live[t] and len(live[t]) > 1:
+                    r.del_route(t, d)
+                    o.del_route(t, d)
+                    live[t].discard(d)
+                else:
+                    r.add_route(t, d)
+                    o.add_route(t, d)
+                    live[t].add(d)
+            read_back(e, scatters)
         topics = _topics(rng, 200) + [t for t in pool[:50] if b"+" not in t and b"#" not in t]
         got = r.match_deliveries_many(topics, tagged=True)
         for tp, row in zip(topics, got):
             assert row == o.match_deliveries(tp), (burst, tp)
         for tp, row in zip(topics, r.match_routes_many(topics)):
             assert [(x.topic, x.dest) for x in row] == o.match_routes(tp), (burst, tp)
+    # the exact table, the dest pool and fr_meta each took the scatter path (one log with one image
+    # epoch, this and the previous commit's with two) at least once
+    for t in ("rt_slots", "rt_dest", "fr_meta"):
+        assert scatters[t] & {1, 2} == {2 if double_buffer else 1}, (t, scatters[t], copies[t])
     e.close()

@@ -21,6 +21,7 @@ from emqx_amd.emqx_broker import Broker  # noqa: E402
 from emqx_amd.emqx_router import Router  # noqa: E402
 from emqx_amd.engine import pack  # noqa: E402
 from oracle import pytrie  # noqa: E402
+from trie_churn import read_back  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -331,7 +332,8 @@ def test_subscriber_image_churn_on_device_vs_oracle(gpu_device, double_buffer):
     (route_gc tiny), exact-table regrowth, a filter deleted and re-inserted
     behind the broker's back; every burst's publishes equal the oracle's,
     with two image epochs and with one"""
-    rng = random.Random(53 + double_buffer)
+    rng, mini = random.Random(53 + double_buffer), random.Random(153)
+    copies, scatters = {}, {}
     e = Engine(device=gpu_device)
     e.set_option("route_gc", 64)
     e.set_option("double_buffer", double_buffer)
@@ -366,7 +368,28 @@ def test_subscriber_image_churn_on_device_vs_oracle(gpu_device, double_buffer):
         if burst % 4 == 3:
             e.debug_check_subs()
             e.debug_check_routes()
+        # the image read back after the burst's commit (mostly whole-table copies: 700 ops on small
+        # tables), then two bursts of ten ops: their commits scatter the changed elements
+        read_back(e, copies)
+        for _ in range(2):
+            for k in range(10):
+                if k % 2 == 0:      # a new plain subscriber of a topic that has some
+                    t, s = mini.choice(live)[0], 6000 + mini.randrange(1000)
+                    b.subscribe(t, s, None)
+                    bag.insert_subscriber(None, t, s)
+                    o.add_route(t, dest(None))
+                    live.append((t, s, None))
+                else:
+                    t, s, g = live.pop(mini.randrange(len(live)))
+                    b.unsubscribe(t, s, g)
+                    if bag.delete_object(g, t, s) == 0:
+                        o.del_route(t, dest(g))
+            read_back(e, scatters)
         topics = _topics(rng, 200) + [t for t in pool[:50] if b"+" not in t and b"#" not in t] + pool[400:420]
         totals = _check(b, o, bag, topics, burst)
         assert sum(totals) > 0
+    # the exact table, the subscriber pool and fs_meta each took the scatter path (one log with one
+    # image epoch, this and the previous commit's with two) at least once
+    for t in ("sx_slots", "sx_pool", "fs_meta"):
+        assert scatters[t] & {1, 2} == {2 if double_buffer else 1}, (t, scatters[t], copies[t])
     e.close()

@@ -24,6 +24,7 @@ from emqx_amd.emqx_broker import Broker  # noqa: E402
 from emqx_amd.emqx_router import Router  # noqa: E402
 from emqx_amd.engine import pack  # noqa: E402
 from oracle import pytrie  # noqa: E402
+from trie_churn import read_back  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -536,8 +537,10 @@ def test_one_small_delta_per_commit_reaches_both_image_epochs(gpu_device):
               _topics(rng, 64))[:64]
     assert len(topics) == 64
 
+    seen = {}
+
     def check(tag):
-        w.e.commit()
+        read_back(w.e, seen)     # the commit, and the live image read back against the host tables
         for tp, pub in zip(topics, w.b.publish_many(topics)):
             counts, pairs = route_dispatch(w.o, w.bag, b"n1", tp)
             assert [(d.to, d.target) for d in pub.deliveries] == w.o.match_deliveries(tp), (tag, tp)
@@ -559,6 +562,30 @@ def test_one_small_delta_per_commit_reaches_both_image_epochs(gpu_device):
         w.e.delete(wild[4 + k])                                  # one trie filter, behind the tables
         w.e.insert(wild[4 + k])
         check(("filter", k))
+    # Tables of dozens mostly copy whole (a scatter has to stay within a quarter of the table's bytes), so:
+    # one large burst -- 150 more topics, half of them wildcard filters, each with a route, a subscriber
+    # and a member -- then two bursts of ten ops.  The second small commit's two logs are both small: the
+    # set and topic tables, the member pool and fx take the scatter path.
+    big = [b"u/%d/+" % i if i % 2 else b"u/%d" % i for i in range(150)]
+    for i, f in enumerate(big):
+        w.route(f, ("g1", "n1"))
+        w.members(b"g1", f, [2000 + i])
+        w.e.sub_add(f, 3000 + i)
+        w.bag.insert_subscriber(None, f, 3000 + i)
+    check("large burst")
+    seen.clear()
+    for k in range(2):
+        w.route(wild[6 + k], "n3")
+        w.e.sub_add(exact[5 + k], 950 + k)
+        w.bag.insert_subscriber(None, exact[5 + k], 950 + k)
+        w.member(b"g1", big[k], 2500 + k)                        # a second member of a set
+        w.route(b"v/%d" % k, ("g2", "n1"))                       # a new exact topic with a set
+        w.member(b"g2", b"v/%d" % k, 2600 + k)
+        w.e.delete(wild[8 + 2 * k])                              # a filter with a set, behind the tables
+        w.e.insert(wild[8 + 2 * k])
+        check(("small burst", k))
+    for t in ("sh_sets", "sh_tx", "sh_pool", "sh_fx", "fs_meta", "fr_meta"):
+        assert 2 in seen[t], (t, seen[t])
     w.e.debug_check_routes()
     w.e.debug_check_subs()
     w.e.debug_check_shares()
